@@ -16,7 +16,9 @@ configs[2] (the configuration the metric is quoted on; it fits one GPU), random-
 `python bench.py --gpus N` with N > 1 and no torchrun environment re-launches itself through torch.distributed.run on
 127.0.0.1 (one rank per GPU) and relays rank 0's JSON line.
 
-The JSON line also carries
+A plain run does only what the headline figure needs: set-up (with the start-up GEMM calibration below), warm-up, the
+timed steps, --dump-outputs DIR if given, and one JSON line with the contract keys and `config`.  With --full the JSON
+line also carries (each measured after the timed steps or, for the roofline's event pairs, inside them)
   roofline     — the dominant HIP kernel (the bf16 MFMA GEMM): algorithmic FLOPs of every launch in the timed region
                  / its HIP-event duration on the launch stream, against the 2.5 PFLOP/s dense bf16 MFMA peak;
                  .region        the tower + SVA part of the step (what the north star's ">= 40 %" is about): its
@@ -126,6 +128,17 @@ def parse():
                     help="no model step: run only the gradient-exchange collectives of the configured parameter set (GradSync "
                          "all-reduce, or the ZeRO-2 reduce-scatter + all-gather with --zero2) for --steps steps and print the bus "
                          "bandwidth per bucket — the communication breakdown beside a scaling curve")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: roofline (event pairs in the timed region, the two profiled GEMM "
+                         "steps, the kernel A/B), the letter-boxed masked case, the N > 1 rank spread and communication pass, box "
+                         "identity, parity and CPU baseline.  Off by default: a plain run sets up, warms up, times --steps steps "
+                         "and prints the contract keys")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as float32 .npy files in DIR: loss, "
+                         "seeded rows of the logits (taken before the backward overwrites them), and seeded samples of the "
+                         "trainable parameters after the update and of their gradients (< 64 MB in all; rank 0).  The logits "
+                         "rows are copied inside the last timed step (an index_select of 64 rows before its backward), so "
+                         "compare ms_per_step only between runs that both dump or both do not")
     return ap.parse_args()
 
 
@@ -695,8 +708,45 @@ def emit(full: dict, verbose: bool) -> None:
     print(json.dumps(full if verbose else compact_line(full)), flush=True)
 
 
+DUMP_LOGIT_ROWS = 64          # --dump-outputs: rows of the [B * S, V] logits at seeded positions (64 x 128256 fp32 = 33 MB)
+DUMP_PARAM_SAMPLE = 1 << 20   # --dump-outputs: elements of the trainable parameters / gradients at seeded positions (4 MB each)
+
+
+def dump_outputs(path, loss, kept, params):
+    """--dump-outputs: what the last timed step computed, as float32 .npy files under ``path``.  ``kept`` holds what step()
+    kept of that step: ``logits`` (the seeded rows, copied before the backward writes dlogits over the logits) and ``grads``
+    (references to the gradients, before zero_grad dropped them).  The parameter / gradient samples share one seeded set
+    of positions in the concatenation of the trainable parameters (model order); a gradient that is None counts as zero."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss.detach().float().reshape(1)}
+    if kept.get("logits") is not None:
+        arrays["logits_sample"] = kept["logits"]
+    sizes = [p.numel() for p in params]
+    bounds = torch.tensor(sizes, dtype=torch.int64).cumsum(0)
+    g = torch.Generator().manual_seed(0)
+    flat_idx = torch.randint(int(bounds[-1]), (min(DUMP_PARAM_SAMPLE, int(bounds[-1])),), generator=g).sort().values
+    owner = torch.searchsorted(bounds, flat_idx, right=True)
+    psample, gsample = [], []
+    for i in owner.unique().tolist():
+        local = (flat_idx[owner == i] - (int(bounds[i - 1]) if i > 0 else 0)).to(params[i].device)
+        psample.append(params[i].detach().reshape(-1)[local].float())
+        grad = kept["grads"][i]
+        gsample.append(grad.reshape(-1)[local].float() if grad is not None else torch.zeros_like(psample[-1]))
+    arrays["params_sample"] = torch.cat(psample)
+    arrays["grads_sample"] = torch.cat(gsample)
+    total = 0
+    for name, t in arrays.items():
+        a = t.cpu().numpy().astype(np.float32)
+        total += a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+    assert total <= 64 * 2 ** 20, f"--dump-outputs wrote {total} bytes"
+
+
 def main():
     args = parse()
+    if args.gemm_report and not args.full:
+        raise SystemExit("--gemm-report needs --full: the table comes from the two profiled GEMM steps that only --full runs")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         raise SystemExit(self_spawn(args))
     from cambrian_amd.train.dp import GradSync, init_distributed
@@ -790,11 +840,14 @@ def main():
 
     sync_events = None   # a list while the timed region runs
 
-    def step(kw_=None):
+    def step(kw_=None, keep=None):
         kw_ = kw if kw_ is None else kw_
         if feed is not None:
             kw_["images"] = next(feed)["images"]
         out = model(**kw_)
+        if keep is not None and out.logits is not None:   # --dump-outputs: seeded rows, before the backward overwrites them
+            flat = out.logits.detach().reshape(-1, out.logits.shape[-1])
+            keep["logits"] = flat.index_select(0, (keep["row_frac"] * flat.shape[0]).long()).float()
         out.loss.backward()
         ops.region_close()   # (roofline.region: the towers + connector span's backward ends with backward())
         if z3_units is not None:
@@ -809,6 +862,8 @@ def main():
             else:
                 sync.finish()
         opt.step()
+        if keep is not None:
+            keep["grads"] = [p.grad for p in params]
         opt.zero_grad(set_to_none=True)
         return out.loss
 
@@ -850,19 +905,23 @@ def main():
         step()
     prof = None
     spans = None
-    if not args.no_roofline and rank == 0:
+    if args.full and not args.no_roofline and rank == 0:
         prof = ops.GEMM_PROFILE = []
         ops.GEMM_PROFILE_TILE = 256  # the timed region times only the dominant kernel's launches (an event pair per launch)
         spans = ops.REGION_PROFILE = []
+    keep = None
+    if args.dump_outputs and rank == 0:   # positions of the logits rows the last step keeps, as fractions of B * S
+        keep = {"row_frac": torch.rand(DUMP_LOGIT_ROWS, dtype=torch.float64,
+                                       generator=torch.Generator().manual_seed(0)).sort().values.to(dev)}
 
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    sync_events = []
+    sync_events = [] if args.full else None
     t0 = time.perf_counter()
     loss = None
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss = step(keep=keep if i == args.steps - 1 else None)
     torch.cuda.synchronize()
     elapsed_rank = time.perf_counter() - t0   # this rank alone, before the barrier (rank_step_ms_min / max)
     if world > 1:
@@ -871,15 +930,18 @@ def main():
     ops.GEMM_PROFILE = None
     ops.REGION_PROFILE = None
     timed_sync_events, sync_events = sync_events, None
+    if keep is not None:
+        dump_outputs(args.dump_outputs, loss, keep, params)
+        keep = None
     multi_gpu = None
-    if world > 1:
+    if world > 1 and args.full:
         multi_gpu = multi_gpu_fields(args, rank, world, dev, elapsed_rank, timed_sync_events, sync, opt)
 
     # ---- two extra steps with an event pair around EVERY own GEMM launch (all_own_gemm / --gemm-report): kept out of the
     # timed region, where ~1200 extra event pairs per step would cost the stream about half a percent
     prof_all = None
     gemm_pass_steps = 2
-    if not args.no_roofline and not args.no_gemm_pass:   # EVERY rank steps (the steps carry collectives); rank 0 records
+    if args.full and not args.no_roofline and not args.no_gemm_pass:   # EVERY rank steps (the steps carry collectives); rank 0 records
         if rank == 0:
             prof_all = ops.GEMM_PROFILE = []
             ops.GEMM_PROFILE_TILE = 0
@@ -895,7 +957,7 @@ def main():
     # second case (NOT the headline): letter-boxed images -> the collator's key-padding mask in the decoder attention and
     # partially masked SVA windows.  Same step, same timing brackets, 2 steps.
     masked = None
-    if not args.no_masked_case:
+    if args.full and not args.no_masked_case:
         sizes = [(336, 224) if i % 2 == 0 else (224, 336) for i in range(B)]
         mb = synthetic_batch(B, seed=4321 + rank, image_position=pos0, image_sizes=sizes)
         mkw = dict(kw, input_ids=mb["input_ids"].to(dev), labels=mb["labels"] if args.scored_rows else mb["labels"].to(dev),
@@ -1079,19 +1141,22 @@ def main():
             rows.sort(key=lambda r: -r["ms_per_step"])
             with open(args.gemm_report, "w") as f:
                 json.dump(rows, f, indent=0)
-        line["box"] = box_identity(dev)
-        if "roofline" in line and not args.no_ab:
-            try:
-                line["roofline"]["ab"] = gemm_ab(dev)
-            except Exception as e:  # a side measurement must never take the line down
-                line["roofline"]["ab"] = {"error": repr(e)[:300]}
-        line["parity"] = PARITY
-        if not args.no_cpu_baseline and world == 1:
-            try:
-                line["cpu_baseline"] = cpu_baseline()
-            except Exception as e:  # the baseline must never take the measurement down
-                line["cpu_baseline"] = {"value": None, "error": repr(e)}
-        emit(line, args.verbose_line)
+        if not args.full:
+            print(json.dumps(line), flush=True)
+        else:
+            line["box"] = box_identity(dev)
+            if "roofline" in line and not args.no_ab:
+                try:
+                    line["roofline"]["ab"] = gemm_ab(dev)
+                except Exception as e:  # a side measurement must never take the line down
+                    line["roofline"]["ab"] = {"error": repr(e)[:300]}
+            line["parity"] = PARITY
+            if not args.no_cpu_baseline and world == 1:
+                try:
+                    line["cpu_baseline"] = cpu_baseline()
+                except Exception as e:  # the baseline must never take the measurement down
+                    line["cpu_baseline"] = {"value": None, "error": repr(e)}
+            emit(line, args.verbose_line)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -47,6 +47,38 @@ __device__ __forceinline__ bf16x8_t cvt8_bf16(float a0, float a1, float a2, floa
     if (e__ != hipSuccess) return CMB_ERR_LAUNCH;            \
   } while (0)
 
+// ---- deterministic cross-workgroup sums ----------------------------------------------------
+// A float atomicAdd per column and workgroup adds in whatever order the workgroups finish, so bias / LayerNorm / position-
+// table gradients changed in their last bits from run to run (and AdamW's first updates, close to lr * sign(g), turned that
+// into parameter differences of order lr).  Instead a workgroup stores its partial row at part[slot * n + i] (every slot
+// and i it owns, zeros included) and det_sum_kernel adds the slots to out[i] in a fixed order: the same bits on every run.
+// `part` is the caller's fp32 workspace (allocated by the binding, so it counts in the framework's memory statistics).
+template <int WAVES>
+__global__ void __launch_bounds__(WAVES * 64) det_sum_kernel(const float* __restrict__ part, int64_t slots, int64_t n,
+                                                             float* __restrict__ out) {
+  __shared__ float red[WAVES][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t i = (int64_t)blockIdx.x * 64 + lane;
+  float s = 0.f;
+  if (i < n)
+    for (int64_t k = wave; k < slots; k += WAVES) s += part[k * n + i];
+  red[wave][lane] = s;
+  __syncthreads();
+  if (wave == 0 && i < n) {
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) t += red[w][lane];
+    out[i] += t;
+  }
+}
+
+// out[0..n) += sum over slots of part[slot * n + i], in slot order; false if the launch failed
+static inline bool det_sum(const float* part, int64_t slots, int64_t n, float* out, hipStream_t s) {
+  if (out && n > 0 && slots > 0)
+    hipLaunchKernelGGL(det_sum_kernel<16>, dim3((unsigned)((n + 63) / 64)), dim3(16 * 64), 0, s, part, slots, n, out);
+  return hipGetLastError() == hipSuccess;
+}
+
 static inline bool cmb_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
 // run-time kernel-selection knobs (cmb_knob_set, include/cambrian_amd.h): storage in elementwise.hip

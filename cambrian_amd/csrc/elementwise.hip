@@ -100,12 +100,13 @@ __global__ void __launch_bounds__(256) weight_prep_kernel(const cmb_prep_job one
 }
 
 // ---------------------------------------------------------------------------------------------
-// colsum: out[c] += sum_r in[r, c]  (fp32 atomics, one per column per block); with a row scale (cmb_colsum_scaled):
-// out[c] += sum_r scale[r, c / group] * in[r, c], group % 8 == 0 (the 8 columns of a lane share one factor)
+// colsum: out[c] += sum_r in[r, c]  (each block writes its partial row part[blockIdx.y, c] into the caller's workspace;
+// det_sum adds the rows in order); with a row scale (cmb_colsum_scaled): out[c] += sum_r scale[r, c / group] * in[r, c], group % 8 == 0 (the 8
+// columns of a lane share one factor)
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 __global__ void __launch_bounds__(256) colsum_kernel(const T* __restrict__ in, int64_t R, int64_t C, int64_t ld_in,
-                                                     float* __restrict__ out, int rows_per_block,
+                                                     float* __restrict__ part, int rows_per_block,
                                                      const float* __restrict__ scale = nullptr, int64_t ld_scale = 0, int group = 8) {
   __shared__ float red[4][512];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -132,7 +133,7 @@ __global__ void __launch_bounds__(256) colsum_kernel(const T* __restrict__ in, i
   __syncthreads();
   for (int i = threadIdx.x; i < 512; i += 256) {
     const int64_t col = (int64_t)blockIdx.x * 512 + i;
-    if (col < C) atomicAdd(out + col, red[0][i] + red[1][i] + red[2][i] + red[3][i]);
+    if (col < C) part[(int64_t)blockIdx.y * C + col] = red[0][i] + red[1][i] + red[2][i] + red[3][i];
   }
 }
 
@@ -289,11 +290,12 @@ __global__ void __launch_bounds__(256) embed_splice_fwd_kernel(const int64_t* __
   }
 }
 
-// dfeat gather + dnewline reduction.  grid.x over (b, i) grid rows.
+// dfeat gather + dnewline reduction.  grid.x over (b, i) grid rows; each block writes its newline row's gradient (zeros when
+// the row is cut off) to dnew_part[blockIdx.x, :] (the caller's workspace) and det_sum adds the rows to dnewline in order.
 template <typename T>
 __global__ void __launch_bounds__(256) embed_splice_bwd_kernel(const T* __restrict__ dout, const int32_t* __restrict__ pos,
                                                                int64_t B, int S, int H, int side, T* __restrict__ dfeat,
-                                                               float* __restrict__ dnewline) {
+                                                               float* __restrict__ dnew_part) {
   const int nv = H >> 3;
   const int64_t b = blockIdx.x / side;
   const int i = blockIdx.x - (int)(b * side);
@@ -307,9 +309,9 @@ __global__ void __launch_bounds__(256) embed_splice_bwd_kernel(const T* __restri
       if (valid) Vec8<T>::load(dout + ((int64_t)b * S + t) * H + c * 8, v);
       if (j < side) {
         Vec8<T>::store(dfeat + ((int64_t)b * side * side + i * side + j) * H + c * 8, v);
-      } else if (valid && dnewline) {
+      } else if (dnew_part) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) atomicAdd(dnewline + c * 8 + e, v[e]);
+        for (int e = 0; e < 8; ++e) dnew_part[(int64_t)blockIdx.x * H + c * 8 + e] = v[e];
       }
     }
   }
@@ -479,7 +481,7 @@ extern "C" int cmb_weight_prep(const cmb_prep_job* jobs_device, int32_t n_jobs, 
 
 // rows per workgroup of the column sums: 256 for the tall inputs (221 184 rows), fewer when that would leave most of the chip
 // idle — the SVA query-side inputs are 13 824 x 1024: 108 workgroups of 256 rows ran 27-60 us for 28 MB.  The launch aims at
-// CMB_KNOB_COLSUM_WGS workgroups (one atomicAdd per column and workgroup either way; 0 = always 256 rows, rounds 1-5)
+// CMB_KNOB_COLSUM_WGS workgroups (one partial row per workgroup either way; 0 = always 256 rows, rounds 1-5)
 static int colsum_rows_per_block(int64_t R, int64_t C) {
   const int target = cmb_knob(CMB_KNOB_COLSUM_WGS);
   if (target <= 0) return 256;
@@ -490,26 +492,40 @@ static int colsum_rows_per_block(int64_t R, int64_t C) {
   return (int)rpb;
 }
 
-extern "C" int cmb_colsum(int dtype, const void* in, int64_t R, int64_t C, int64_t ld_in, float* out, void* stream) {
+extern "C" int64_t cmb_colsum_workspace(int64_t R, int64_t C) {
+  if (R <= 0 || C <= 0) return 0;
+  const int rows_per_block = colsum_rows_per_block(R, C);
+  return (R + rows_per_block - 1) / rows_per_block * C;
+}
+
+extern "C" int cmb_colsum(int dtype, const void* in, int64_t R, int64_t C, int64_t ld_in, float* out, float* workspace,
+                          int64_t workspace_floats, void* stream) {
   if (!in || !out || R < 0 || C <= 0 || (C & 7) || (ld_in & 7)) return CMB_ERR_BAD_ARG;
   if (R == 0) return CMB_OK;
   const int rows_per_block = colsum_rows_per_block(R, C);
   dim3 grid((unsigned)((C + 511) / 512), (unsigned)((R + rows_per_block - 1) / rows_per_block));
+  if (dtype != CMB_BF16 && dtype != CMB_F32) return CMB_ERR_BAD_ARG;
+  if (!workspace || workspace_floats < (int64_t)grid.y * C) return CMB_ERR_WORKSPACE;
+  float* part = workspace;
   DT_SWITCH(dtype, hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)in, R, C,
-                                      ld_in, out, rows_per_block));
-  CMB_CHECK_LAUNCH();
+                                      ld_in, part, rows_per_block));
+  if (!det_sum(part, grid.y, C, out, (hipStream_t)stream)) return CMB_ERR_LAUNCH;
   return CMB_OK;
 }
 
 extern "C" int cmb_colsum_scaled(int dtype, const void* in, int64_t R, int64_t C, int64_t ld_in, const float* row_scale,
-                                 int64_t ld_scale, int32_t group, float* out, void* stream) {
+                                 int64_t ld_scale, int32_t group, float* out, float* workspace, int64_t workspace_floats,
+                                 void* stream) {
   if (!in || !out || !row_scale || R < 0 || C <= 0 || (C & 7) || group <= 0 || (group & 7) || C % group) return CMB_ERR_BAD_ARG;
   if (R == 0) return CMB_OK;
   const int rows_per_block = colsum_rows_per_block(R, C);
   dim3 grid((unsigned)((C + 511) / 512), (unsigned)((R + rows_per_block - 1) / rows_per_block));
-  DT_SWITCH(dtype, hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)in, R, C, ld_in, out,
+  if (dtype != CMB_BF16 && dtype != CMB_F32) return CMB_ERR_BAD_ARG;
+  if (!workspace || workspace_floats < (int64_t)grid.y * C) return CMB_ERR_WORKSPACE;
+  float* part = workspace;
+  DT_SWITCH(dtype, hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)in, R, C, ld_in, part,
                                       rows_per_block, row_scale, ld_scale, (int)group));
-  CMB_CHECK_LAUNCH();
+  if (!det_sum(part, grid.y, C, out, (hipStream_t)stream)) return CMB_ERR_LAUNCH;
   return CMB_OK;
 }
 
@@ -587,13 +603,18 @@ extern "C" int cmb_embed_splice_fwd(int dtype, const int64_t* ids, int64_t B, in
 }
 
 extern "C" int cmb_embed_splice_bwd(int dtype, const void* dout, const int32_t* pos, int64_t B, int64_t S, int64_t H,
-                                    int32_t side, void* dfeat, float* dnewline, void* stream) {
+                                    int32_t side, void* dfeat, float* dnewline, float* workspace, int64_t workspace_floats,
+                                    void* stream) {
   if (!dout || !pos || !dfeat || B < 0 || S <= 0 || H <= 0 || (H & 7) || side <= 0) return CMB_ERR_BAD_ARG;
   if (B == 0) return CMB_OK;
+  if (dtype != CMB_BF16 && dtype != CMB_F32) return CMB_ERR_BAD_ARG;
+  if (dnewline && (!workspace || workspace_floats < B * side * H)) return CMB_ERR_WORKSPACE;
+  float* part = dnewline ? workspace : nullptr;
   DT_SWITCH(dtype, hipLaunchKernelGGL(embed_splice_bwd_kernel<T>, dim3((unsigned)(B * side)), dim3(256), 0,
                                       (hipStream_t)stream, (const T*)dout, pos, B, (int)S, (int)H, side, (T*)dfeat,
-                                      dnewline));
-  CMB_CHECK_LAUNCH();
+                                      part));
+  if (!part) { CMB_CHECK_LAUNCH(); return CMB_OK; }
+  if (!det_sum(part, B * side, H, dnewline, (hipStream_t)stream)) return CMB_ERR_LAUNCH;
   return CMB_OK;
 }
 

@@ -379,7 +379,9 @@ __global__ void __launch_bounds__(256) row_stats_kernel(const T* __restrict__ x,
 // position-table row: blockIdx.y = pos (0..grid_r^2-1), and "window" w enumerates
 // (b, qy, qx); token row = b*side^2 + (qy*grid_r+py)*side + qx*grid_r+px.  With grid_r == 1 this
 // is the identity enumeration.  Per-lane partial sums of dgamma / dbeta / dadd live in registers,
-// are combined across the block's 4 waves through LDS and leave as one atomicAdd per column per block.
+// are combined across the block's 4 waves through LDS and leave as one partial row per block (dgamma / dbeta: row
+// blockIdx.y * gridDim.x + blockIdx.x of [blocks * npos, D]; dadd: [blockIdx.x][pos] of [blocks, npos, D]), which det_sum
+// adds up in a fixed order.
 // ------------------------------------------------------------------------------------------------
 template <typename T, typename TDx, int NCH, bool ACCUM>
 __global__ void __launch_bounds__(256) layernorm_bwd_kernel(
@@ -474,8 +476,8 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(
     }
   }
 
-  // block-level combine of the partial sums, one quantity at a time through sred[4][D]
-  auto combine = [&](float (&part)[NCH][8], float* out) {
+  // block-level combine of the partial sums, one quantity at a time through sred[4][D], into this block's partial row
+  auto combine = [&](float (&part)[NCH][8], float* row) {
     __syncthreads();
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
@@ -486,14 +488,13 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(
       }
     }
     __syncthreads();
-    for (int col = threadIdx.x; col < D; col += 256) {
-      const float t = sred[col] + sred[D + col] + sred[2 * D + col] + sred[3 * D + col];
-      if (t != 0.f) atomicAdd(out + col, t);
-    }
+    for (int col = threadIdx.x; col < D; col += 256)
+      row[col] = sred[col] + sred[D + col] + sred[2 * D + col] + sred[3 * D + col];
   };
-  if (gamma && dgamma) combine(pg, dgamma);
-  if (gamma && dbeta) combine(pb, dbeta);
-  if (ar && dadd) combine(pa, dadd + (int64_t)pos * D);
+  const int64_t slot = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+  if (gamma && dgamma) combine(pg, dgamma + slot * D);
+  if (gamma && dbeta) combine(pb, dbeta + slot * D);
+  if (ar && dadd) combine(pa, dadd + ((int64_t)blockIdx.x * gridDim.y + pos) * D);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -624,7 +625,8 @@ layernorm_bwd_multi_kernel(const T* __restrict__ x, int64_t ldx, int64_t rows, i
       }
     }
   }
-  // block-level combine of each layer's partial sums through sred[4][D], then one atomicAdd per column per workgroup
+  // block-level combine of each layer's partial sums through sred[4][D] into the workgroup's partial row of mp.dadd[l]
+  // ([blockIdx.x][pos] of [blocks, npos, D]: workspace that det_sum adds up in a fixed order)
 #pragma unroll
   for (int l = 0; l < LC; ++l) {
     if (l < mp.layers && mp.add[l] && mp.dadd[l]) {   // block-uniform
@@ -638,11 +640,9 @@ layernorm_bwd_multi_kernel(const T* __restrict__ x, int64_t ldx, int64_t rows, i
         }
       }
       __syncthreads();
-      float* out = mp.dadd[l] + (int64_t)pos * D;
-      for (int col = threadIdx.x; col < D; col += 256) {
-        const float t = sred[col] + sred[D + col] + sred[2 * D + col] + sred[3 * D + col];
-        if (t != 0.f) atomicAdd(out + col, t);
-      }
+      float* row = mp.dadd[l] + ((int64_t)blockIdx.x * gridDim.y + pos) * D;
+      for (int col = threadIdx.x; col < D; col += 256)
+        row[col] = sred[col] + sred[D + col] + sred[2 * D + col] + sred[3 * D + col];
     }
   }
 }
@@ -967,22 +967,41 @@ int ln_fwd(const void* x, int64_t rows, int64_t D, int64_t ldx, const float* add
   return CMB_OK;
 }
 
-template <typename T, typename TDx, bool ACCUM>
-int ln_bwd(const void* dy, int64_t lddy, const void* x, int64_t ldx, int64_t rows, int64_t D, const float* add,
-           int side, int grid_r, const float* gamma, const float* mean, const float* rstd, void* dx,
-           int64_t lddx, float* dgamma, float* dbeta, float* dadd, hipStream_t s) {
-  const int nch = nch_for(D);
-  if (nch > 8) return CMB_ERR_SHAPE;  // register budget: the backward supports D <= 4096 (ConvNeXt-XXL stage 4: 3072)
-  const int npos = grid_r * grid_r;
-  const int64_t nwin = rows / npos;
-  int64_t blocks = (nwin + 63) / 64;  // ~16 rows per wave: amortises the end-of-block atomics
-  // ... unless that leaves the chip mostly idle (the SVA query-side LayerNorms: 13 824 rows = 216 workgroups, 61 us = 0.16 of
-  // the HBM peak, profiles/r03_hbm_kernels_table.md): then ~4 rows per wave
-  // (CMB_KNOB_LN_BWD_ROWS rows per workgroup: every workgroup ends with one atomicAdd per column and parameter)
+// workgroups along the windows of cmb_layernorm_bwd: ~16 rows per wave (amortises the end-of-workgroup partial rows) ...
+// unless that leaves the chip mostly idle (the SVA query-side LayerNorms: 13 824 rows = 216 workgroups, 61 us = 0.16 of
+// the HBM peak, profiles/r03_hbm_kernels_table.md): then CMB_KNOB_LN_BWD_ROWS rows per workgroup (~4 rows per wave)
+static int64_t ln_bwd_blocks(int64_t nwin) {
+  int64_t blocks = (nwin + 63) / 64;
   if (blocks < 1024) blocks = (nwin + cmb_knob(CMB_KNOB_LN_BWD_ROWS) - 1) / cmb_knob(CMB_KNOB_LN_BWD_ROWS);
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
+  return blocks;
+}
+
+template <typename T, typename TDx, bool ACCUM>
+int ln_bwd(const void* dy, int64_t lddy, const void* x, int64_t ldx, int64_t rows, int64_t D, const float* add,
+           int side, int grid_r, const float* gamma, const float* mean, const float* rstd, void* dx,
+           int64_t lddx, float* dgamma, float* dbeta, float* dadd, float* workspace, int64_t workspace_floats,
+           hipStream_t s) {
+  const int nch = nch_for(D);
+  if (nch > 8) return CMB_ERR_SHAPE;  // register budget: the backward supports D <= 4096 (ConvNeXt-XXL stage 4: 3072)
+  const int npos = grid_r * grid_r;
+  const int64_t blocks = ln_bwd_blocks(rows / npos);
   const size_t smem = (size_t)4 * D * sizeof(float);
+  // partial rows in the caller's workspace, one [blocks * npos, D] slab per wanted output (dgamma / dbeta: row
+  // blockIdx.y * blocks + blockIdx.x; dadd: [blocks, npos, D]), added up in a fixed order by det_sum below
+  const int64_t slots = blocks * npos;
+  float* const dgamma_out = gamma ? dgamma : nullptr;
+  float* const dbeta_out = gamma ? dbeta : nullptr;
+  float* const dadd_out = add ? dadd : nullptr;
+  const int nslab = (dgamma_out != nullptr) + (dbeta_out != nullptr) + (dadd_out != nullptr);
+  if (nslab && (!workspace || workspace_floats < nslab * slots * D)) return CMB_ERR_WORKSPACE;
+  float* slab = workspace;
+  dgamma = dgamma_out ? slab : nullptr;
+  if (dgamma_out) slab += slots * D;
+  dbeta = dbeta_out ? slab : nullptr;
+  if (dbeta_out) slab += slots * D;
+  dadd = dadd_out ? slab : nullptr;
   if (nch == 2)
     hipLaunchKernelGGL((layernorm_bwd_kernel<T, TDx, 2, ACCUM>), dim3((unsigned)blocks, npos), dim3(256), smem, s,
                        (const T*)dy, lddy, (const T*)x, ldx, rows, (int)D, add, side, grid_r, gamma, mean, rstd,
@@ -996,6 +1015,9 @@ int ln_bwd(const void* dy, int64_t lddy, const void* x, int64_t ldx, int64_t row
                        (const T*)dy, lddy, (const T*)x, ldx, rows, (int)D, add, side, grid_r, gamma, mean, rstd,
                        (TDx*)dx, lddx, dgamma, dbeta, dadd);
   CMB_CHECK_LAUNCH();
+  if (dgamma && !det_sum(dgamma, slots, D, dgamma_out, s)) return CMB_ERR_LAUNCH;
+  if (dbeta && !det_sum(dbeta, slots, D, dbeta_out, s)) return CMB_ERR_LAUNCH;
+  if (dadd && !det_sum(dadd, blocks, npos * D, dadd_out, s)) return CMB_ERR_LAUNCH;
   return CMB_OK;
 }
 
@@ -1080,7 +1102,7 @@ extern "C" int cmb_layernorm_bwd(int dtype, const void* dy, int64_t lddy, const 
                                  int64_t rows, int64_t D, const float* add, int32_t side, int32_t grid_r,
                                  const float* gamma, const float* mean, const float* rstd, void* dx,
                                  int64_t lddx, int32_t dx_accumulate, float* dgamma, float* dbeta,
-                                 float* dadd, void* stream) {
+                                 float* dadd, float* workspace, int64_t workspace_floats, void* stream) {
   if (!dy || !x || !dx || !mean || !rstd || rows < 0 || D <= 0 || (D & 7)) return CMB_ERR_BAD_ARG;
   if (add && (side <= 0 || grid_r <= 0 || side % grid_r)) return CMB_ERR_BAD_ARG;
   if (rows == 0) return CMB_OK;
@@ -1090,18 +1112,50 @@ extern "C" int cmb_layernorm_bwd(int dtype, const void* dy, int64_t lddy, const 
   if (dtype == CMB_BF16) {
     if (dx_accumulate)
       return ln_bwd<bf16_t, float, true>(dy, lddy, x, ldx, rows, D, add, side, grid_r, gamma, mean, rstd, dx,
-                                         lddx, dgamma, dbeta, dadd, s);
+                                         lddx, dgamma, dbeta, dadd, workspace, workspace_floats, s);
     return ln_bwd<bf16_t, bf16_t, false>(dy, lddy, x, ldx, rows, D, add, side, grid_r, gamma, mean, rstd, dx,
-                                         lddx, dgamma, dbeta, dadd, s);
+                                         lddx, dgamma, dbeta, dadd, workspace, workspace_floats, s);
   }
   if (dtype == CMB_F32) {
     if (dx_accumulate)
       return ln_bwd<float, float, true>(dy, lddy, x, ldx, rows, D, add, side, grid_r, gamma, mean, rstd, dx,
-                                        lddx, dgamma, dbeta, dadd, s);
+                                        lddx, dgamma, dbeta, dadd, workspace, workspace_floats, s);
     return ln_bwd<float, float, false>(dy, lddy, x, ldx, rows, D, add, side, grid_r, gamma, mean, rstd, dx,
-                                       lddx, dgamma, dbeta, dadd, s);
+                                       lddx, dgamma, dbeta, dadd, workspace, workspace_floats, s);
   }
   return CMB_ERR_BAD_ARG;
+}
+
+extern "C" int64_t cmb_layernorm_bwd_workspace(int64_t rows, int64_t D, int32_t grid_r) {
+  if (rows <= 0 || D <= 0 || grid_r <= 0) return 0;
+  const int64_t npos = (int64_t)grid_r * grid_r;
+  return ln_bwd_blocks(rows / npos) * npos * D;
+}
+
+// workgroups along the windows (~8 rows per wave: amortises the end-of-workgroup combine) and layers per launch
+// (CMB_KNOB_LN_MULTI_CHUNK, 4 ... 7; <= 6: two waves per SIMD) of cmb_layernorm_bwd_multi
+static int64_t ln_multi_blocks(int64_t nwin) {
+  int64_t blocks = (nwin + 31) / 32;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  return blocks;
+}
+static int ln_multi_chunk() {
+  const int k = cmb_knob(CMB_KNOB_LN_MULTI_CHUNK);
+  return (k < 4 || k > 7) ? 4 : k;
+}
+
+extern "C" int64_t cmb_layernorm_bwd_multi_workspace(const cmb_ln_multi_desc* d) {
+  if (!d || d->rows <= 0 || d->D <= 0 || d->layers <= 0 || d->layers > CMB_LN_MULTI_MAX) return 0;
+  bool any_dadd = false, any_add = false;
+  for (int l = 0; l < d->layers; ++l) {
+    any_add = any_add || d->add[l];
+    any_dadd = any_dadd || (d->add[l] && d->dadd[l]);
+  }
+  if (!any_dadd || d->grid_r <= 0) return 0;
+  const int64_t npos = any_add ? (int64_t)d->grid_r * d->grid_r : 1;
+  const int64_t chunk = d->layers < ln_multi_chunk() ? d->layers : ln_multi_chunk();
+  return chunk * ln_multi_blocks(d->rows / npos) * npos * d->D;
 }
 
 extern "C" int cmb_layernorm_bwd_multi(const cmb_ln_multi_desc* d, void* stream) {
@@ -1122,13 +1176,11 @@ extern "C" int cmb_layernorm_bwd_multi(const cmb_ln_multi_desc* d, void* stream)
   if (nch != 2) return CMB_ERR_SHAPE;   // D <= 1024 (the SVA feature width): 7 layers x 16 partial sums per lane
   const size_t smem = (size_t)4 * d->D * sizeof(float);
   const int npos = grid_r * grid_r;
-  const int64_t nwin = d->rows / npos;
-  int64_t blocks = (nwin + 31) / 32;   // ~8 rows per wave: amortises the end-of-workgroup combine
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
+  const int64_t blocks = ln_multi_blocks(d->rows / npos);
+  if (d->workspace_floats < cmb_layernorm_bwd_multi_workspace(d) || (cmb_layernorm_bwd_multi_workspace(d) && !d->workspace))
+    return CMB_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  int kChunk = cmb_knob(CMB_KNOB_LN_MULTI_CHUNK);   // layers per launch (4 ... 7; <= 6: two waves per SIMD)
-  if (kChunk < 4 || kChunk > 7) kChunk = 4;
+  const int kChunk = ln_multi_chunk();
   for (int l0 = 0; l0 < d->layers; l0 += kChunk) {
     LnMultiParams mp;
     mp.layers = d->layers - l0 < kChunk ? d->layers - l0 : kChunk;
@@ -1139,7 +1191,9 @@ extern "C" int cmb_layernorm_bwd_multi(const cmb_ln_multi_desc* d, void* stream)
       mp.add[l] = on ? d->add[l0 + l] : nullptr;
       mp.mean[l] = on ? d->mean[l0 + l] : nullptr;
       mp.rstd[l] = on ? d->rstd[l0 + l] : nullptr;
-      mp.dadd[l] = on ? d->dadd[l0 + l] : nullptr;
+      // the kernel writes [blocks, npos, D] partial rows per layer into a slab of the caller's workspace (reused by the
+      // next launch: same stream); det_sum adds them to the caller's dadd below
+      mp.dadd[l] = (on && d->add[l0 + l] && d->dadd[l0 + l]) ? d->workspace + (int64_t)l * blocks * npos * d->D : nullptr;
     }
     const bool acc = d->accumulate || l0 > 0;
 #define LN_MULTI_LAUNCH(T_, ACC_, LC_)                                                                                  \
@@ -1158,6 +1212,8 @@ extern "C" int cmb_layernorm_bwd_multi(const cmb_ln_multi_desc* d, void* stream)
 #undef LN_MULTI_T
 #undef LN_MULTI_LAUNCH
     CMB_CHECK_LAUNCH();
+    for (int l = 0; l < mp.layers; ++l)
+      if (mp.dadd[l] && !det_sum(mp.dadd[l], blocks, npos * d->D, d->dadd[l0 + l], s)) return CMB_ERR_LAUNCH;
   }
   return CMB_OK;
 }

@@ -25,7 +25,7 @@ ACT_CODES = {None: ACT_NONE, "none": ACT_NONE, "gelu": ACT_GELU_ERF, "gelu_erf":
              "quick_gelu": ACT_QUICK_GELU, "silu": ACT_SILU}
 SVA_MAX_TOWERS = 8
 KNOB_LN_FWD, KNOB_DWCONV, KNOB_VIT_ATTN, KNOB_SVA_ABS, KNOB_LN_MULTI_CHUNK, KNOB_FLASH, KNOB_COLSUM_WGS, KNOB_LN_BWD_ROWS = 0, 1, 2, 3, 4, 5, 6, 7   # enum cmb_knob_id
-ABI_VERSION = 10   # CMB_ABI_VERSION of the include/cambrian_amd.h this binding was written against
+ABI_VERSION = 11   # CMB_ABI_VERSION of the include/cambrian_amd.h this binding was written against
 
 STATUS = {0: "CMB_OK", -1: "CMB_ERR_BAD_ARG", -2: "CMB_ERR_ALIGNMENT", -3: "CMB_ERR_SHAPE",
           -4: "CMB_ERR_WORKSPACE", -5: "CMB_ERR_LAUNCH"}
@@ -114,6 +114,7 @@ class LnMultiDesc(C.Structure):
         ("dx", C.c_void_p), ("lddx", C.c_int64),
         ("accumulate", C.c_int32), ("reserved", C.c_int32),
         ("dx_out", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_floats", C.c_int64),
     ]
 
 
@@ -168,18 +169,21 @@ SIGNATURES = {
     "cmb_gemm_tail_rows": (_i64, [_i64, _i64]),
     "cmb_quantize_fp8_rows": (C.c_int, [C.c_int, _p, _i64, _i64, _i64, _p, _i64, _p, _p]),
     "cmb_transpose": (C.c_int, [C.c_int, _p, _i64, _i64, _i64, _p, _i64, _p]),
-    "cmb_colsum": (C.c_int, [C.c_int, _p, _i64, _i64, _i64, _p, _p]),
-    "cmb_colsum_scaled": (C.c_int, [C.c_int, _p, C.c_int64, C.c_int64, C.c_int64, _p, C.c_int64, C.c_int32, _p, _p]),
+    "cmb_colsum_workspace": (C.c_int64, [_i64, _i64]),
+    "cmb_colsum": (C.c_int, [C.c_int, _p, _i64, _i64, _i64, _p, _p, _i64, _p]),
+    "cmb_colsum_scaled": (C.c_int, [C.c_int, _p, C.c_int64, C.c_int64, C.c_int64, _p, C.c_int64, C.c_int32, _p, _p, _i64, _p]),
     "cmb_cast": (C.c_int, [C.c_int, _p, C.c_int, _p, _i64, _p]),
     "cmb_weight_prep_tiles": (_i64, [_i64, _i64]),
     "cmb_weight_prep_one": (C.c_int, [C.POINTER(PrepJob), _p]),
     "cmb_weight_prep": (C.c_int, [_p, _i32, _i64, _p]),
     "cmb_row_stats": (C.c_int, [C.c_int, _p, _i64, _i64, _i64, _f, _p, _p, _p]),
+    "cmb_layernorm_bwd_multi_workspace": (C.c_int64, [C.POINTER(LnMultiDesc)]),
     "cmb_layernorm_bwd_multi": (C.c_int, [C.POINTER(LnMultiDesc), _p]),
     "cmb_layernorm_fwd_multi": (C.c_int, [C.POINTER(LnFwdMultiDesc), _p]),
     "cmb_layernorm_fwd": (C.c_int, [C.c_int, _p, _i64, _i64, _i64, _p, _i32, _i32, _p, _p, _f, _p, _i64, _p, _p, _p]),
+    "cmb_layernorm_bwd_workspace": (C.c_int64, [_i64, _i64, _i32]),
     "cmb_layernorm_bwd": (C.c_int, [C.c_int, _p, _i64, _p, _i64, _i64, _i64, _p, _i32, _i32, _p, _p, _p, _p, _i64,
-                                    _i32, _p, _p, _p, _p]),
+                                    _i32, _p, _p, _p, _p, _i64, _p]),
     "cmb_rmsnorm_fwd": (C.c_int, [C.c_int, _p, _i64, _i64, _p, _f, _p, _p, _p]),
     "cmb_rmsnorm_bwd": (C.c_int, [C.c_int, _p, _p, _i64, _i64, _p, _p, _p, _p, _p]),
     "cmb_add_rmsnorm_fwd": (C.c_int, [C.c_int, _p, _p, _i64, _i64, _p, _f, _p, _p, _p, _p]),
@@ -191,7 +195,7 @@ SIGNATURES = {
     "cmb_sva_abs_fwd": (C.c_int, [C.POINTER(SvaAbsDesc), _p]),
     "cmb_sva_abs_bwd": (C.c_int, [C.POINTER(SvaAbsDesc), _p]),
     "cmb_embed_splice_fwd": (C.c_int, [C.c_int, _p, _i64, _i64, _i64, _i64, _p, _i64, _p, _i32, _p, _p, _p, _p]),
-    "cmb_embed_splice_bwd": (C.c_int, [C.c_int, _p, _p, _i64, _i64, _i64, _i32, _p, _p, _p]),
+    "cmb_embed_splice_bwd": (C.c_int, [C.c_int, _p, _p, _i64, _i64, _i64, _i32, _p, _p, _p, _i64, _p]),
     "cmb_sva_fold_kv_fwd": (C.c_int, [_p] * 6 + [_i64, _i64, _p, _p, _p]),
     "cmb_sva_fold_kv_bwd": (C.c_int, [_p] * 8 + [_i64, _i64] + [_p] * 7 + [_i64, _p]),
     "cmb_sva_fold_kv_bwd_workspace": (_i64, [_i64, _i64]),

@@ -488,15 +488,18 @@ def k_colsum(x: torch.Tensor, out: Optional[torch.Tensor] = None, row_scale: Opt
     R, Cc = x.shape
     if out is None:
         out = torch.zeros((Cc,), dtype=torch.float32, device=x.device)
+    # partial rows of the fixed-order (run-to-run identical) cross-workgroup sum
+    ws = torch.empty((max(L.load().cmb_colsum_workspace(R, Cc), 1),), dtype=torch.float32, device=x.device)
     if row_scale is not None:
         if row_scale.dtype != torch.float32 or row_scale.dim() != 2 or row_scale.stride(1) != 1 or row_scale.shape != (R, Cc // group):
             raise L.CambrianAmdError("colsum row_scale must be fp32 [R, C / group]")
         rc = L.load().cmb_colsum_scaled(L.dtype_code(x.dtype), x.data_ptr(), R, Cc, x.stride(0), row_scale.data_ptr(),
-                                        row_scale.stride(0), group, out.data_ptr(), L.stream_ptr(x.device))
+                                        row_scale.stride(0), group, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                        L.stream_ptr(x.device))
         L.check(rc, "cmb_colsum_scaled")
         return out
-    rc = L.load().cmb_colsum(L.dtype_code(x.dtype), x.data_ptr(), R, Cc, x.stride(0), out.data_ptr(),
-                             L.stream_ptr(x.device))
+    rc = L.load().cmb_colsum(L.dtype_code(x.dtype), x.data_ptr(), R, Cc, x.stride(0), out.data_ptr(), ws.data_ptr(),
+                             ws.numel(), L.stream_ptr(x.device))
     L.check(rc, "cmb_colsum")
     return out
 
@@ -583,10 +586,14 @@ def k_layernorm_bwd(dy, x, mean, rstd, gamma=None, add=None, side=1, grid_r=1, d
         dx, acc = dx_acc, 1
     else:
         dx, acc = torch.empty((rows, D), dtype=x.dtype, device=dev), 0
+    # one slab of partial rows per wanted output (fixed-order, run-to-run identical cross-workgroup sums)
+    nslab = (dgamma is not None) + (dbeta is not None) + (dadd is not None)
+    per = L.load().cmb_layernorm_bwd_workspace(rows, D, grid_r if add is not None else 1) if rows > 0 else 0
+    ws = torch.empty((max(nslab * per, 1),), dtype=torch.float32, device=dev)
     rc = L.load().cmb_layernorm_bwd(L.dtype_code(x.dtype), dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), rows, D,
                                     L.ptr(add), side, grid_r, L.ptr(gamma), mean.data_ptr(), rstd.data_ptr(),
-                                    dx.data_ptr(), D, acc, L.ptr(dgamma), L.ptr(dbeta), L.ptr(dadd),
-                                    L.stream_ptr(dev))
+                                    dx.data_ptr(), D, acc, L.ptr(dgamma), L.ptr(dbeta), L.ptr(dadd), ws.data_ptr(),
+                                    ws.numel(), L.stream_ptr(dev))
     L.check(rc, "cmb_layernorm_bwd")
     return (None if dx_acc is not None else dx), dgamma, dbeta, dadd
 
@@ -1046,6 +1053,9 @@ def k_layernorm_bwd_multi(x: torch.Tensor, items, side: int, grid_r: int, dx: to
             d.dadd[i] = None if (add is None or slot < 0 or dadd_out[slot] is None) else dadd_out[slot].data_ptr()
         d.dx, d.lddx, d.accumulate = dx.data_ptr(), dx.stride(0), 1 if (accumulate or lo > 0) else 0
         d.dx_out = dx_out.data_ptr() if (dx_out is not None and lo + L.LN_MULTI_MAX >= len(items)) else None
+        ws = torch.empty((max(L.load().cmb_layernorm_bwd_multi_workspace(C.byref(d)), 1),), dtype=torch.float32,
+                         device=x.device)   # partial rows of the fixed-order table-gradient sums
+        d.workspace, d.workspace_floats = ws.data_ptr(), ws.numel()
         L.check(L.load().cmb_layernorm_bwd_multi(C.byref(d), L.stream_ptr(x.device)), "cmb_layernorm_bwd_multi")
 
 
@@ -1588,8 +1598,10 @@ class EmbedSpliceFn(torch.autograd.Function):
             dtable = dtable.to(tab_dtype)
         dfeat = torch.empty((B, side * side, H), dtype=dt, device=dout.device)
         dnl = torch.zeros((H,), dtype=torch.float32, device=dout.device)
+        ws = torch.empty((max(B * side * H, 1),), dtype=torch.float32, device=dout.device)   # newline partial rows
         rc = L.load().cmb_embed_splice_bwd(L.dtype_code(dt), dout.data_ptr(), pos.data_ptr(), B, S, H, side,
-                                           dfeat.data_ptr(), dnl.data_ptr(), L.stream_ptr(dout.device))
+                                           dfeat.data_ptr(), dnl.data_ptr(), ws.data_ptr(), ws.numel(),
+                                           L.stream_ptr(dout.device))
         L.check(rc, "cmb_embed_splice_bwd")
         return None, dtable, dfeat, dnl.to(nl_dtype), None, None
 

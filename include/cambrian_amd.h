@@ -63,10 +63,11 @@ typedef struct cmb_rowmap {
 const char* cmb_version(void);
 /* ABI revision: bumped whenever an entry point's signature or a descriptor's layout changes (round 2's key_valid
  * arguments = 2, round 3's fold_kv workspace = 3, the batch fields of cmb_gemm_desc = 4,
- * the kernel-selection knobs of round 4 = 5, cmb_layernorm_fwd_multi = 9, cmb_ln_multi_desc.dx_out = 10).  Bindings must compare it with the revision they
+ * the kernel-selection knobs of round 4 = 5, cmb_layernorm_fwd_multi = 9, cmb_ln_multi_desc.dx_out = 10, the workspaces of
+ * the deterministic column sums = 11).  Bindings must compare it with the revision they
  * were written against (CMB_ABI_VERSION; cambrian_amd/lib.py::load raises on a mismatch): every symbol of a stale
  * library still resolves, and a shifted argument list corrupts memory instead of failing. */
-#define CMB_ABI_VERSION 10
+#define CMB_ABI_VERSION 11
 int cmb_abi_version(void);
 
 /* Run-time kernel-selection knobs: which of several kernels that compute the SAME function an entry point launches
@@ -212,15 +213,19 @@ int cmb_gemm_policy_clear(void);
 int cmb_transpose(int dtype, const void* in, int64_t R, int64_t C, int64_t ld_in,
                   void* out, int64_t R_pad, void* stream);
 
-/* out[c] (fp32) += sum_r in[r, c]   — bias gradients (atomic accumulate; caller zero-fills). */
+/* out[c] (fp32) += sum_r in[r, c]   — bias gradients (caller zero-fills).  Deterministic: every workgroup writes its partial
+ * row into `workspace` (fp32, at least cmb_colsum_workspace(R, C) floats, else CMB_ERR_WORKSPACE) and the rows are added
+ * to out in a fixed order — the same bits on every run (float atomics added them in completion order). */
+int64_t cmb_colsum_workspace(int64_t R, int64_t C);
 int cmb_colsum(int dtype, const void* in, int64_t R, int64_t C, int64_t ld_in,
-               float* out, void* stream);
+               float* out, float* workspace, int64_t workspace_floats, void* stream);
 /* out[c] += sum_r row_scale[r * ld_scale + c / group] * in[r, c]  (fp32 accumulation; out must be zero-filled by the caller;
  * group % 8 == 0, C % group == 0).  The bias gradients of the absorbed SVA projections: d b_k[c] = sum_q d(cb)[q, h(c)] q[q, c],
  * d b_v[c] = sum_q m3[q, h(c)] d out[q, c] with group = 64 = one head (vision_sampler.py:187-189's k_proj / v_proj biases,
- * restated per head: DESIGN.md section 4.5) — one pass over the rows instead of a broadcast product + reduction. */
+ * restated per head: DESIGN.md section 4.5) — one pass over the rows instead of a broadcast product + reduction.  Workspace
+ * and fixed summation order as cmb_colsum. */
 int cmb_colsum_scaled(int dtype, const void* in, int64_t R, int64_t C, int64_t ld_in, const float* row_scale,
-                      int64_t ld_scale, int32_t group, float* out, void* stream);
+                      int64_t ld_scale, int32_t group, float* out, float* workspace, int64_t workspace_floats, void* stream);
 
 /* y = (T)x elementwise casts between fp32 and bf16 (n elements). to_dtype/from_dtype are CMB_*. */
 int cmb_cast(int from_dtype, const void* in, int to_dtype, void* out, int64_t n, void* stream);
@@ -268,13 +273,17 @@ int cmb_layernorm_fwd(int dtype, const void* x, int64_t rows, int64_t D, int64_t
 /* dx (+)= LN backward.  dy: [rows,D]; xhat is recomputed from x (+add), mean, rstd.
  * dx_accumulate != 0: dx += result (gradient accumulation across the 13 SVA layers that share
  * the aux features, SURVEY.md §7 "hard parts").  dgamma/dbeta/dadd are fp32 and are
- * *accumulated into* (atomics), caller zero-fills; any may be NULL. */
+ * *accumulated into*, caller zero-fills; any may be NULL (dgamma / dbeta need gamma, dadd needs add).  Every workgroup
+ * writes its partial rows into `workspace` (fp32): cmb_layernorm_bwd_workspace(rows, D, grid_r) floats (grid_r = 1 without
+ * add) per wanted output, else CMB_ERR_WORKSPACE; they are added in a fixed order — the same bits on every run. */
+int64_t cmb_layernorm_bwd_workspace(int64_t rows, int64_t D, int32_t grid_r);
 int cmb_layernorm_bwd(int dtype, const void* dy, int64_t lddy, const void* x, int64_t ldx,
                       int64_t rows, int64_t D,
                       const float* add, int32_t side, int32_t grid_r,
                       const float* gamma, const float* mean, const float* rstd,
                       void* dx, int64_t lddx, int32_t dx_accumulate,
-                      float* dgamma, float* dbeta, float* dadd, void* stream);
+                      float* dgamma, float* dbeta, float* dadd, float* workspace, int64_t workspace_floats,
+                      void* stream);
 
 /* Backward of SEVERAL non-affine LayerNorms of one input in one pass (the 13 SVA layers each normalise the same aux feature
  * tensor with their own position table: vision_sampler.py:304-309 reached 13 times per step, cambrian_llama.py:168-207):
@@ -304,7 +313,10 @@ typedef struct cmb_ln_multi_desc {
   void* dx_out;           /* optional (round 6): the call's LAST launch writes the finished sum here in x's dtype (dense rows,
                            * leading dimension D) instead of updating dx — the cast of the fp32 accumulator at the end of the
                            * deferred backward; dx then holds the sum without the last launch's layers */
+  float* workspace;       /* fp32 partial rows of the dadd sums (added in a fixed order: the same bits on every run), */
+  int64_t workspace_floats;   /* at least cmb_layernorm_bwd_multi_workspace(d) floats, else CMB_ERR_WORKSPACE */
 } cmb_ln_multi_desc;
+int64_t cmb_layernorm_bwd_multi_workspace(const cmb_ln_multi_desc* d);
 int cmb_layernorm_bwd_multi(const cmb_ln_multi_desc* d, void* stream);
 
 /* Forward of SEVERAL non-affine LayerNorms of one input in one pass (round 6): y_l[r,:] = normalise(x[r,:] + add_l[pos(r),:]),
@@ -450,9 +462,11 @@ int cmb_embed_splice_fwd(int dtype, const int64_t* ids, int64_t B, int64_t S, in
                          const void* feat, int32_t side, const void* newline,
                          void* out, int32_t* pos, void* stream);
 /* dfeat[b,i*side+j,:] = dout[b, p_b+i*(side+1)+j, :];  dnewline (fp32 [H], accumulated) +=
- * sum_{b,i} dout[b, p_b+i*(side+1)+side, :]. */
+ * sum_{b,i} dout[b, p_b+i*(side+1)+side, :], summed in a fixed order through `workspace` (fp32, B * side * H floats when
+ * dnewline is not NULL, else CMB_ERR_WORKSPACE). */
 int cmb_embed_splice_bwd(int dtype, const void* dout, const int32_t* pos, int64_t B, int64_t S,
-                         int64_t H, int32_t side, void* dfeat, float* dnewline, void* stream);
+                         int64_t H, int32_t side, void* dfeat, float* dnewline, float* workspace,
+                         int64_t workspace_floats, void* stream);
 
 /* K|V weight folding of one tower of one SVA layer (vision_sampler.py:173-174,188-189: k_proj_i / v_proj_i = LayerNorm ->
  * Linear; the two LayerNorms share their statistics, so their affines are folded into one projection):

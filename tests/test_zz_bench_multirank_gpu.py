@@ -21,7 +21,7 @@ def test_two_ranks_one_json_line(dev, mode):
     port = 29600 + os.getpid() % 300 + {"": 0, "--zero3": 7, "--bf16-buckets": 13}[mode[0] if mode else ""]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "2", "--llm-layers", "2", "--no-cpu-baseline", "--no-masked-case"] + mode
+           "--batch", "2", "--llm-layers", "2", "--full", "--no-cpu-baseline", "--no-masked-case"] + mode
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -31,6 +31,28 @@ def test_two_ranks_one_json_line(dev, mode):
     assert d["value"] == pytest.approx(4 / (d["ms_per_step"] * 1e-3), rel=1e-6)    # whole-job images / max-over-ranks time
     assert ("zero3" in d["config"]["parallelism"]) == (mode == ["--zero3"])
     assert ("bf16 copies" in d["config"].get("NOT_HEADLINE", "")) == (mode == ["--bf16-buckets"])   # opt-in wire dtype: never headline
+
+
+def test_plain_line_and_dumped_outputs(dev, tmp_path):
+    """A plain run (no --full) prints the contract keys and nothing measured beside them; --dump-outputs writes the last
+    timed step's loss, logits rows and parameter / gradient samples as float32 .npy files, < 64 MB in all."""
+    import numpy as np
+    env = dict(os.environ, CAMBRIAN_AMD_RANDOM_INIT="1")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2",
+           "--llm-layers", "2", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["value"] == pytest.approx(2 / (d["ms_per_step"] * 1e-3), rel=1e-6)
+    assert not {"roofline", "masked_case", "box", "parity", "cpu_baseline", "multi_gpu"} & set(d)
+    arrays = {n: np.load(tmp_path / f"{n}.npy") for n in ("loss", "logits_sample", "params_sample", "grads_sample")}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 2 ** 20
+    assert arrays["loss"][0] == pytest.approx(d["config"]["loss"], rel=1e-6)
+    assert arrays["logits_sample"].shape[0] == 64 and arrays["params_sample"].shape == arrays["grads_sample"].shape
+    assert np.abs(arrays["grads_sample"]).max() > 0
 
 
 def test_plain_launch_spawns_its_own_ranks(dev):

@@ -15,7 +15,7 @@ run_verb() {
   local verb=$1; shift
   case "$verb" in
     bench)
-      timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 "$@" > $O/bench_$TAG.json 2> $O/bench_$TAG.err
+      timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full "$@" > $O/bench_$TAG.json 2> $O/bench_$TAG.err
       echo "bench rc=$? $(wc -c < $O/bench_$TAG.json) bytes"; cp gpurun_out/bench_line_full.json $O/bench_full_$TAG.json 2>/dev/null
       python - <<P
 import json
@@ -51,7 +51,7 @@ P
       done
       ;;
     shapes)  # per-shape table of every own GEMM launch of a step (an event pair per launch) -> gemm_shapes_<tag>.json
-      timeout 500 python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-ab --no-masked-case --gemm-report $O/gemm_shapes_$TAG.json > $O/gemm_report_run_$TAG.json 2> $O/gemm_report_run_$TAG.err
+      timeout 500 python bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-ab --no-masked-case --gemm-report $O/gemm_shapes_$TAG.json > $O/gemm_report_run_$TAG.json 2> $O/gemm_report_run_$TAG.err
       echo "gemm report rc=$?"; python - <<P
 import json
 rows=sorted(json.load(open("$O/gemm_shapes_$TAG.json")), key=lambda r: -r["ms_per_step"])

@@ -7,7 +7,7 @@ VAR=$2; OLD=$3; NEW=$4
 for rep in 1 2; do
   for v in old new; do
     VAL=$NEW; [ $v == old ] && VAL=$OLD
-    env $VAR=$VAL timeout 600 python bench.py --gpus 1 --steps 8 --warmup 3 --no-cpu-baseline --no-ab --no-masked-case --no-gemm-pass > $O/ab_${VAR}_${v}_$rep.json 2> $O/ab_${VAR}_${v}_$rep.err
+    env $VAR=$VAL timeout 600 python bench.py --gpus 1 --steps 8 --warmup 3 --full --no-cpu-baseline --no-ab --no-masked-case --no-gemm-pass > $O/ab_${VAR}_${v}_$rep.json 2> $O/ab_${VAR}_${v}_$rep.err
     python - <<P
 import json
 try:

@@ -5,7 +5,7 @@ O=gpurun_out/r06; mkdir -p $O
 for rep in 1 2; do
   for v in old new; do
     K=""; [ $v == old ] && K="6=0,7=16"
-    CAMBRIAN_AMD_KNOBS=$K timeout 600 python bench.py --gpus 1 --steps 8 --warmup 3 --no-cpu-baseline --no-ab --no-masked-case --no-gemm-pass > $O/ab_knobs_${v}_$rep.json 2> $O/ab_knobs_${v}_$rep.err
+    CAMBRIAN_AMD_KNOBS=$K timeout 600 python bench.py --gpus 1 --steps 8 --warmup 3 --full --no-cpu-baseline --no-ab --no-masked-case --no-gemm-pass > $O/ab_knobs_${v}_$rep.json 2> $O/ab_knobs_${v}_$rep.err
     python - <<P
 import json
 d=json.loads(open("$O/ab_knobs_${v}_$rep.json").read().strip().splitlines()[-1]); r=d["roofline"]

@@ -12,7 +12,7 @@ done
 for rep in 1 2; do
   for v in old new; do
     K=""; F=5; [ $v == old ] && K="4=4" && F=4
-    CAMBRIAN_AMD_KNOBS=$K CAMBRIAN_AMD_DEFER_LN_FLUSH=$F timeout 600 python bench.py --gpus 1 --steps 8 --warmup 3 --no-cpu-baseline --no-ab --no-masked-case --no-gemm-pass > $O/ab_lnchunk_${v}_$rep.json 2> $O/ab_lnchunk_${v}_$rep.err
+    CAMBRIAN_AMD_KNOBS=$K CAMBRIAN_AMD_DEFER_LN_FLUSH=$F timeout 600 python bench.py --gpus 1 --steps 8 --warmup 3 --full --no-cpu-baseline --no-ab --no-masked-case --no-gemm-pass > $O/ab_lnchunk_${v}_$rep.json 2> $O/ab_lnchunk_${v}_$rep.err
     python - <<P
 import json
 d=json.loads(open("$O/ab_lnchunk_${v}_$rep.json").read().strip().splitlines()[-1]); r=d["roofline"]
