@@ -194,6 +194,13 @@ class KeyPadding:
         return self._dense
 
 
+def use_decode_kernel(x: torch.Tensor, nh: int, nkv: int, hd: int) -> bool:
+    """Whether a decode step runs on ``ops.decode_attention``: GPU tensors, a geometry the kernel takes, nothing to
+    back-propagate, and not switched off with ``CAMBRIAN_AMD_DECODE_ATTN=0`` (A/B against the SDPA body)."""
+    return (x.is_cuda and ops.decode_attention_enabled() and ops.decode_attention_supported(x.dtype, nh, nkv, hd)
+            and not (torch.is_grad_enabled() and x.requires_grad))
+
+
 class LlamaAttention(nn.Module):
     def __init__(self, cfg, device, dtype):
         super().__init__()
@@ -244,8 +251,22 @@ class LlamaAttention(nn.Module):
     def decode(self, x, cos, sin, kcache, vcache, t: int, key_mask):
         """One new token per sequence against the cache (decode steps never see the SVA hook: cambrian_llama.py:174,
         ``prepare_inputs`` early-outs for length-1 inputs).  x [B,1,H]; k/v caches [B,nkv,Lmax,hd], slot t is filled here;
-        key_mask bool [B, t+1]."""
+        key_mask bool [B, >= t+1] (columns past t are ignored).  On the GPU the whole step between the projections and
+        o_proj is one ``ops.decode_attention`` call (decode_attn.hip); geometries it does not take, and
+        ``CAMBRIAN_AMD_DECODE_ATTN=0``, run the stock SDPA body below."""
         B = x.shape[0]
+        if use_decode_kernel(x, self.nh, self.nkv, self.hd):
+            nq, nk = self.nh * self.hd, self.nkv * self.hd
+            w_qkv = _fused_frozen_weight(self, "_w_qkv", (self.q_proj, self.k_proj, self.v_proj))
+            if w_qkv is not None:
+                row = F.linear(x.reshape(B, -1), w_qkv)                       # q heads | k heads | v heads per token
+                q, k, v = row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:]
+            else:
+                x2 = x.reshape(B, -1)
+                q, k, v = self.q_proj(x2), self.k_proj(x2), self.v_proj(x2)
+            o = ops.decode_attention(q, k, v, cos, sin, kcache, vcache, t, key_mask)
+            return self.o_proj(o.view(B, 1, nq))
+        key_mask = key_mask[:, :t + 1]
         q = ops.rope(self.q_proj(x).view(B, self.nh, self.hd), cos, sin).view(B, 1, self.nh, self.hd).transpose(1, 2)
         k = ops.rope(self.k_proj(x).view(B, self.nkv, self.hd), cos, sin)
         kcache[:, :, t] = k
@@ -638,7 +659,7 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
             cos, sin = ops.rope_table((n_tok + step)[:, None], hd, theta)
             x = model.embed_tokens(nxt)[:, None, :].to(model.llm_dtype)
             for layer, (kc, vc) in zip(model.layers, caches):
-                x = layer.decode(x, cos, sin, kc, vc, t, key_mask[:, :t + 1])
+                x = layer.decode(x, cos, sin, kc, vc, t, key_mask)      # [B, Lmax]: the step reads columns 0..t
             logits = self.lm_head(model.norm(x)[:, 0]).float()
         return torch.stack(out_ids, 1)
 

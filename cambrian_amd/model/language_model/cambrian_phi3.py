@@ -92,8 +92,16 @@ class Phi3Attention(nn.Module):
         return _lin(self.o_proj, o.transpose(1, 2).reshape(B, S, self.nh * self.hd))
 
     def decode(self, x, cos, sin, kcache, vcache, t: int, key_mask):
-        """One new token per sequence against the cache (see LlamaAttention.decode)."""
+        """One new token per sequence against the cache (see LlamaAttention.decode): the kernel takes q / k / v as views
+        into the packed ``qkv_proj`` row."""
         B = x.shape[0]
+        from .cambrian_llama import use_decode_kernel
+        if use_decode_kernel(x, self.nh, self.nkv, self.hd):
+            nq, nk = self.nh * self.hd, self.nkv * self.hd
+            row = self.qkv_proj(x.reshape(B, -1))
+            o = ops.decode_attention(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t, key_mask)
+            return self.o_proj(o.view(B, 1, nq))
+        key_mask = key_mask[:, :t + 1]
         q, k, v = ops.qkv_rope(self.qkv_proj(x).contiguous(), cos, sin, self.nh, self.nkv, self.hd)   # [B,h,1,hd]
         kcache[:, :, t] = k[:, :, 0]
         vcache[:, :, t] = v[:, :, 0]

@@ -2103,6 +2103,84 @@ def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_vali
     return CausalAttnFn.apply(q, k, v, None, None, key_valid)
 
 
+# ================================================================================================
+# decode step of generate(): attention of one new token per sequence against the K/V cache (decode_attn.hip)
+# ================================================================================================
+_DECODE_WS: dict = {}   # device -> fp32 workspace of the split partials, grown on demand and reused by every layer and step
+
+
+def decode_attention_supported(dtype: torch.dtype, nh: int, nkv: int, hd: int) -> bool:
+    """The geometries ``cmb_decode_attn`` takes: bf16 / fp32, head_dim 64 / 96 / 128, at most 8 query heads per KV head."""
+    return (dtype in (torch.bfloat16, torch.float32) and hd in (64, 96, 128) and nkv > 0 and nh > 0 and nh % nkv == 0
+            and nh // nkv <= 8)
+
+
+def decode_attention_plan(B: int, nkv: int, t: int, splits: int = 0) -> Tuple[int, int]:
+    """(splits, chunk) of a decode step over cache keys 0..t: the key range is cut into ``splits`` chunks of ``chunk`` keys
+    (the last one shorter), ``splits * chunk >= t + 1 > (splits - 1) * chunk``.  ``splits`` = 0 asks for the library's
+    choice, a pure function of (B, nkv, t, CU count); a forced count is reduced when t + 1 is short."""
+    s, ch = C.c_int32(0), C.c_int64(0)
+    L.check(L.load().cmb_decode_attn_plan(B, nkv, t, splits, C.byref(s), C.byref(ch), None), "cmb_decode_attn_plan")
+    return s.value, ch.value
+
+
+def decode_attention_max_splits() -> int:
+    mx = C.c_int32(0)
+    L.load().cmb_decode_attn_plan(1, 1, 0, 0, None, None, C.byref(mx))
+    return mx.value
+
+
+def decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                     kcache: torch.Tensor, vcache: torch.Tensor, t: int, key_valid: torch.Tensor,
+                     scale: Optional[float] = None, splits: int = 0) -> torch.Tensor:
+    """One new token per sequence: q [B, nh*hd], k / v [B, nkv*hd] (rows of the projections, un-roped; views into one
+    packed row are fine), cos / sin fp32 [B, hd/2], k / v caches [B, nkv, Lmax, hd] -> out [B, nh*hd].  Ropes q and k, stores
+    roped k and v into cache slot ``t`` and attends to slots 0..t under ``key_valid`` (bool / uint8 [B, >= t+1], slot t
+    always open).  Inference only: there is no backward."""
+    L.require_gpu(q, k, v, cos, sin, kcache, vcache, key_valid)
+    if torch.is_grad_enabled() and any(x.requires_grad for x in (q, k, v, kcache, vcache)):
+        raise L.CambrianAmdError("decode_attention has no backward: call it under torch.no_grad()")
+    B, nkv, Lmax, hd = kcache.shape
+    nh = q.shape[1] // hd
+    dt = q.dtype
+    if not decode_attention_supported(dt, nh, nkv, hd) or q.shape != (B, nh * hd) or k.shape != (B, nkv * hd) \
+            or v.shape != k.shape or vcache.shape != kcache.shape or not (k.dtype == v.dtype == kcache.dtype == vcache.dtype == dt):
+        raise L.CambrianAmdError(f"decode_attention: unsupported geometry q {tuple(q.shape)} k {tuple(k.shape)} "
+                                 f"cache {tuple(kcache.shape)} {dt}")
+    if not 0 <= t < Lmax or key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] < t + 1:
+        raise L.CambrianAmdError("decode_attention: slot t outside the cache or the key mask")
+    if q.stride(1) != 1 or k.stride(1) != 1 or v.stride(1) != 1 or kcache.stride(3) != 1 \
+            or vcache.stride() != kcache.stride() or key_valid.stride(1) != 1:
+        raise L.CambrianAmdError("decode_attention: rows of q / k / v, the caches and the key mask must be contiguous")
+    if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape != (B, hd // 2) or sin.shape != cos.shape \
+            or not cos.is_contiguous() or not sin.is_contiguous():
+        raise L.CambrianAmdError("decode_attention: cos / sin are the contiguous fp32 [B, hd/2] tables of rope_table")
+    if key_valid.dtype == torch.bool:
+        key_valid = key_valid.view(torch.uint8)
+    elif key_valid.dtype != torch.uint8:
+        raise L.CambrianAmdError("decode_attention: key_valid is a bool / uint8 mask")
+    scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
+    lib = L.load()
+    need = lib.cmb_decode_attn_ws(B, nh, nkv, hd, t, splits)
+    if need < 0:
+        L.check(int(need), "cmb_decode_attn_ws")
+    ws = _DECODE_WS.get(q.device)
+    if need > 0 and (ws is None or ws.numel() < need):
+        ws = _DECODE_WS[q.device] = torch.empty(int(need), dtype=torch.float32, device=q.device)
+    out = torch.empty((B, nh * hd), dtype=dt, device=q.device)
+    rc = lib.cmb_decode_attn(L.dtype_code(dt), q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+                             cos.data_ptr(), sin.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), kcache.stride(0),
+                             kcache.stride(1), kcache.stride(2), B, nh, nkv, hd, t, key_valid.data_ptr(), key_valid.stride(0),
+                             scale, splits, L.ptr(ws) if need > 0 else None, int(need), out.data_ptr(), L.stream_ptr(q.device))
+    L.check(rc, "cmb_decode_attn")
+    return out
+
+
+def decode_attention_enabled() -> bool:
+    """``CAMBRIAN_AMD_DECODE_ATTN=0`` in the environment: decode steps take the stock SDPA branch (A/B runs)."""
+    return os.environ.get("CAMBRIAN_AMD_DECODE_ATTN", "1") != "0"
+
+
 class AddRmsNormFn(torch.autograd.Function):
     """(s, y) = (x + delta, rmsnorm(x + delta) * w) in one pass — the decoder layer's "h = h + attn; mlp_in = norm(h)".
     Backward: d(x) = d(delta) = g_s + rmsnorm_backward(g_y), also one pass when the weight is frozen."""

@@ -64,10 +64,11 @@ const char* cmb_version(void);
 /* ABI revision: bumped whenever an entry point's signature or a descriptor's layout changes (round 2's key_valid
  * arguments = 2, round 3's fold_kv workspace = 3, the batch fields of cmb_gemm_desc = 4,
  * the kernel-selection knobs of round 4 = 5, cmb_layernorm_fwd_multi = 9, cmb_ln_multi_desc.dx_out = 10, the workspaces of
- * the deterministic column sums = 11).  Bindings must compare it with the revision they
+ * the deterministic column sums = 11, cmb_decode_attn and its plan / workspace queries = 12).  Bindings must compare it
+ * with the revision they
  * were written against (CMB_ABI_VERSION; cambrian_amd/lib.py::load raises on a mismatch): every symbol of a stale
  * library still resolves, and a shifted argument list corrupts memory instead of failing. */
-#define CMB_ABI_VERSION 11
+#define CMB_ABI_VERSION 12
 int cmb_abi_version(void);
 
 /* Run-time kernel-selection knobs: which of several kernels that compute the SAME function an entry point launches
@@ -588,6 +589,30 @@ int cmb_flash_attn_bwd(const void* q, const void* k, const void* v, const void* 
                        int64_t q_sb, int64_t q_ss, int64_t q_sh, int64_t kv_sb, int64_t kv_ss, int64_t kv_sh,
                        float scale, int32_t causal, int64_t kv_len, const uint8_t* key_valid, float* dvec, void* dq, void* dk,
                        void* dv, void* stream);
+/* One decode step of a decoder layer's attention against the K/V cache (generate(); HF LlamaAttention / Phi3Attention with
+ * use_cache reached from cambrian_llama.py:157-166), everything between the QKV projection and o_proj in one call:
+ * RoPE (rotate-half, tables of cmb_rope_table, cos_t / sin_t [B, hd/2]) on the new token's q [B, nh*hd] and k [B, nkv*hd],
+ * roped k and raw v [B, nkv*hd] stored into slot t of kcache / vcache [B, nkv, Lmax, hd] (element strides c_sb, c_sh, c_st, last
+ * dimension contiguous), then out [B, nh*hd] (contiguous, compute dtype) = softmax(scale * q.K^T).V per query head over cache
+ * keys 0..t, query head h reading KV head h / (nh / nkv).  q / k / v have row strides in elements and may point into one
+ * packed projection row.  key_valid: bytes [B, >= t+1] with row stride kv_ld, non-zero = attendable; slot t is always
+ * attendable (the "diagonal open" rule of cmb_flash_attn_fwd), so no row is empty.  Masked slots are not attended to
+ * whatever they hold; slots past t are not read.  The attended k of slot t is the value stored (rounded to the cache dtype).
+ * dtype CMB_BF16 | CMB_F32 (fp32 scores, running max / sum and accumulators in both); hd 64 | 96 | 128; nh % nkv == 0 and
+ * nh / nkv <= 8; B, nkv <= 65535; all pointers and strides 16-byte aligned (CMB_ERR_ALIGNMENT).
+ * The key range is cut into `splits` contiguous chunks, one workgroup per (batch row, KV head, chunk) holding all nh / nkv
+ * query heads, so a cache row is read once per step; splits > 1 writes un-normalised fp32 partials to `ws` and a second small
+ * launch merges them in chunk order (no atomics: bit-reproducible).  splits == 0 is the library's choice, a pure function of
+ * (B, nkv, t, CU count); 1 .. max_splits forces one (fewer are used when t + 1 is short: cmb_decode_attn_plan reports the
+ * effective count and the chunk length, splits * chunk >= t + 1 > (splits - 1) * chunk).  cmb_decode_attn_ws: floats of
+ * `ws` the call needs (0 when it runs unsplit; ws may then be NULL), or a negative status.  Both queries are host functions. */
+int cmb_decode_attn(int dtype, const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v, int64_t v_ld,
+                    const float* cos_t, const float* sin_t, void* kcache, void* vcache, int64_t c_sb, int64_t c_sh,
+                    int64_t c_st, int64_t B, int32_t nh, int32_t nkv, int32_t hd, int64_t t, const uint8_t* key_valid,
+                    int64_t kv_ld, float scale, int32_t splits, float* ws, int64_t ws_floats, void* out, void* stream);
+int64_t cmb_decode_attn_ws(int64_t B, int32_t nh, int32_t nkv, int32_t hd, int64_t t, int32_t splits);
+int cmb_decode_attn_plan(int64_t B, int32_t nkv, int64_t t, int32_t splits, int32_t* splits_out, int64_t* chunk_out,
+                         int32_t* max_splits_out);
 /* Backward of h = silu(g) * u (Llama MLP gate; forward is cmb_act_mul with CMB_ACT_SILU):
  * dg = dh * u * silu'(g), du = dh * silu(g); all [rows, D] with row strides. */
 int cmb_swiglu_bwd(int dtype, const void* dh, int64_t lddh, const void* g, int64_t ldg, const void* u, int64_t ldu,
