@@ -2,6 +2,7 @@
 // activation helpers, token mean, embedding splice (bit-exact gather/scatter), patch gathers and the
 // bilinear token-grid resampler.  All use 16/32-byte vector accesses along the contiguous dimension.
 #include "common.h"
+#include "resample_core.h"
 
 namespace {
 
@@ -395,15 +396,7 @@ __global__ void __launch_bounds__(256) patchify2x2_kernel(const T* __restrict__ 
 // ---------------------------------------------------------------------------------------------
 // bilinear resample, align_corners = False, fp32 lerp (torch upsample_bilinear2d semantics)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void lerp_index(int o, float scale, int in_size, int& i0, int& i1, float& l1) {
-  float src = scale * ((float)o + 0.5f) - 0.5f;
-  if (src < 0.f) src = 0.f;
-  i0 = (int)src;
-  if (i0 > in_size - 1) i0 = in_size - 1;
-  i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
-  l1 = src - (float)i0;
-}
-
+// per-axis index / weight arithmetic: resample_core.h (shared with the adjoint below and with tests/csrc/resample_sim.cpp)
 template <typename T>
 __global__ void __launch_bounds__(256) resample_kernel(const T* __restrict__ in, int64_t B, int Hi, int Wi, int C,
                                                        int64_t ld_in, int64_t bs_in, T* __restrict__ out, int Ho,
@@ -432,6 +425,49 @@ __global__ void __launch_bounds__(256) resample_kernel(const T* __restrict__ in,
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = hy * (hx * v00[e] + lx * v01[e]) + ly * (hx * v10[e] + lx * v11[e]);
     Vec8<T>::store(out + b * bs_out + ((int64_t)oy * Wo + ox) * ld_out + cv * 8, o);
+  }
+}
+
+// adjoint of resample_kernel in gather form: one thread per (batch, input cell, 8-channel vector) sums, in fp32 and in the
+// fixed order oy ascending then ox ascending, the outputs whose lerp_index names the cell — no atomics, no memset, every
+// cell of din written once (an exact 0 where no output refers to it), bit-reproducible.  The candidate outputs of a cell
+// come from cmb_resample_window; they are trimmed to the run of non-zero weights before the loads.
+template <typename T>
+__global__ void __launch_bounds__(256) resample_bwd_kernel(const T* __restrict__ dout, int64_t B, int Ho, int Wo, int C,
+                                                           int64_t ld_dout, int64_t bs_dout, T* __restrict__ din, int Hi,
+                                                           int Wi, int64_t ld_din, int64_t bs_din) {
+  const int nv = C >> 3;
+  const int64_t total = B * Hi * Wi * (int64_t)nv;
+  const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int cv = (int)(i % nv);
+    int64_t rest = i / nv;
+    const int ix = (int)(rest % Wi);
+    rest /= Wi;
+    const int iy = (int)(rest % Hi);
+    const int64_t b = rest / Hi;
+    int ylo, yhi, xlo, xhi;
+    cmb_resample_window(iy, Hi, Ho, ylo, yhi);
+    cmb_resample_window(ix, Wi, Wo, xlo, xhi);
+    while (ylo <= yhi && cmb_resample_weight(ylo, sy, Hi, iy) == 0.f) ++ylo;
+    while (yhi >= ylo && cmb_resample_weight(yhi, sy, Hi, iy) == 0.f) --yhi;
+    while (xlo <= xhi && cmb_resample_weight(xlo, sx, Wi, ix) == 0.f) ++xlo;
+    while (xhi >= xlo && cmb_resample_weight(xhi, sx, Wi, ix) == 0.f) --xhi;
+    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (xlo <= xhi) {
+      const T* base = dout + b * bs_dout + cv * 8;
+      for (int oy = ylo; oy <= yhi; ++oy) {
+        const float wy = cmb_resample_weight(oy, sy, Hi, iy);
+        for (int ox = xlo; ox <= xhi; ++ox) {
+          const float w = wy * cmb_resample_weight(ox, sx, Wi, ix);
+          float g[8];
+          Vec8<T>::load(base + ((int64_t)oy * Wo + ox) * ld_dout, g);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[e] += w * g[e];
+        }
+      }
+    }
+    Vec8<T>::store(din + b * bs_din + ((int64_t)iy * Wi + ix) * ld_din + cv * 8, acc);
   }
 }
 
@@ -683,6 +719,21 @@ extern "C" int cmb_resample_bilinear(int dtype, const void* in, int64_t B, int32
   DT_SWITCH(dtype, hipLaunchKernelGGL(resample_kernel<T>, dim3(grid_for(total, 256, 32768)), dim3(256), 0,
                                       (hipStream_t)stream, (const T*)in, B, Hi, Wi, (int)C, ld_in, batch_stride_in,
                                       (T*)out, Ho, Wo, ld_out, batch_stride_out));
+  CMB_CHECK_LAUNCH();
+  return CMB_OK;
+}
+
+extern "C" int cmb_resample_bilinear_bwd(int dtype, const void* dout, int64_t B, int32_t Ho, int32_t Wo, int64_t C,
+                                         int64_t ld_dout, int64_t batch_stride_dout, void* din, int32_t Hi, int32_t Wi,
+                                         int64_t ld_din, int64_t batch_stride_din, void* stream) {
+  if (!dout || !din || B < 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || (C & 7) || (ld_dout & 7) ||
+      (ld_din & 7))
+    return CMB_ERR_BAD_ARG;
+  if (B == 0) return CMB_OK;
+  const int64_t total = B * Hi * Wi * (C / 8);
+  DT_SWITCH(dtype, hipLaunchKernelGGL(resample_bwd_kernel<T>, dim3(grid_for(total, 256, 32768)), dim3(256), 0,
+                                      (hipStream_t)stream, (const T*)dout, B, Ho, Wo, (int)C, ld_dout, batch_stride_dout,
+                                      (T*)din, Hi, Wi, ld_din, batch_stride_din));
   CMB_CHECK_LAUNCH();
   return CMB_OK;
 }

@@ -411,10 +411,8 @@ class CambrianMetaForCausalLM(ABC):
                 q2 = vq.view(1, vh).expand(bs * query_num, vh).contiguous()
                 out = getattr(model, f"vision_sampler_{g}").forward_fused(q2, ctx_b, feats, masks_g, holders, bs, qside)
                 if qside != side:                                                    # :395-401 (S5): fp32 bilinear to the
-                    out = out.view(bs, qside, qside, -1).permute(0, 3, 1, 2)         # final grid, align_corners=False
-                    out = torch.nn.functional.interpolate(out.float(), size=(side, side), mode="bilinear",
-                                                          align_corners=False).to(dtype)
-                    out = out.permute(0, 2, 3, 1).reshape(bs * side * side, -1)
+                    out = ops.resample_bilinear(out.view(bs, qside * qside, -1), qside, qside, side, side)   # final grid
+                    out = out.reshape(bs * side * side, -1)
                 group_out.append(out)
             image_features = group_out[0] if len(group_out) == 1 else torch.cat(group_out, -1)
             sva_ctx = SvaContext(feats, masks_u8, holders, ctx_b, bs, side)
@@ -471,10 +469,7 @@ class CambrianMetaForCausalLM(ABC):
                 out = getattr(model, f"vision_sampler_{g}")(q.contiguous(), ctx_g.contiguous(), *kv, *masks)
                 out = out.view(bs, query_num, -1)
                 if qside != side:                                                      # :395-401
-                    out = out.permute(0, 2, 1).contiguous().view(bs, -1, qside, qside)
-                    out = torch.nn.functional.interpolate(out.float(), size=(side, side), mode="bilinear",
-                                                          align_corners=False).to(dtype)
-                    out = out.permute(0, 2, 3, 1).contiguous().flatten(1, 2)
+                    out = ops.resample_bilinear(out, qside, qside, side, side)
                 group_out.append(out)
             image_features = torch.cat(group_out, -1)
             kv_final, mask_final = self.rearrange_vision_tower_features_inference(feats, side, image_sizes, unpad=True)

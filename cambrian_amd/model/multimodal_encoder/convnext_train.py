@@ -10,7 +10,9 @@ from operators that carry a backward:
                                   taps reversed; dW = ``cmb_dwconv7x7_wgrad`` (LDS-tiled, per-slot partials, column-summed);
                                   d(bias) = column sum of dY
   LayerNorm, fc1+GELU, fc2      : ``ops.layernorm`` / ``ops.linear``
-  LayerScale gamma, residual, multi-stage bilinear resize + concat (clip_convnext_encoder.py:99-119,143): torch ops.
+  multi-stage bilinear resize + concat (clip_convnext_encoder.py:99-119,143): ``ops.resample_concat`` — one resample launch
+                                  per stage into the concatenated buffer, the adjoint kernel per stage in backward
+  LayerScale gamma, residual    : torch ops.
 bf16 compute only.
 """
 from __future__ import annotations
@@ -148,9 +150,4 @@ class TrainableConvNeXt(nn.Module):
             if len(stages) != 1:
                 raise L.CambrianAmdError("multi-stage output needs a common output grid (interp size)")
             return stages[0].reshape(B, -1, stages[0].shape[-1])
-        outs = []
-        for s in stages:
-            y = s.permute(0, 3, 1, 2)
-            y = F.interpolate(y.float(), size=(out_side, out_side), mode="bilinear", align_corners=False).to(s.dtype)
-            outs.append(y.permute(0, 2, 3, 1).flatten(1, 2))
-        return torch.cat(outs, -1)
+        return ops.resample_concat(stages, out_side)

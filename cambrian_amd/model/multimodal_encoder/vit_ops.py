@@ -89,6 +89,19 @@ def k_resample(x: torch.Tensor, hi: int, wi: int, out: torch.Tensor, ho: int, wo
     L.check(rc, "cmb_resample_bilinear")
 
 
+def k_resample_bwd(dout: torch.Tensor, ho: int, wo: int, dx: torch.Tensor, hi: int, wi: int, col_offset: int = 0) -> None:
+    """Adjoint of ``k_resample``: dout[:, :, col_offset:col_offset+C] with dout [B, ho*wo, Ctot] -> dx [B, hi*wi, C], written in
+    full (cells no output refers to get 0).  Gather form in a fixed order: no atomics, bit-reproducible."""
+    L.require_gpu(dout, dx)
+    B, T, C = dx.shape
+    assert T == hi * wi and dout.shape[0] == B and dout.shape[1] == ho * wo and dx.stride(2) == 1 and dout.stride(2) == 1
+    assert dout.dtype == dx.dtype and 0 <= col_offset and col_offset + C <= dout.shape[2]
+    gptr = dout.data_ptr() + col_offset * dout.element_size()
+    rc = L.load().cmb_resample_bilinear_bwd(L.dtype_code(dx.dtype), gptr, B, ho, wo, C, dout.stride(1), dout.stride(0),
+                                            dx.data_ptr(), hi, wi, dx.stride(1), dx.stride(0), L.stream_ptr(dx.device))
+    L.check(rc, "cmb_resample_bilinear_bwd")
+
+
 def k_act_mul(a: torch.Tensor, b: Optional[torch.Tensor], act: int) -> torch.Tensor:
     """y = act(a) * b over 2-D (possibly column-sliced) operands."""
     L.require_gpu(a, b)

@@ -13,7 +13,8 @@ the autograd-aware operators the SVA side already trains with:
   self-attention                        : ``ops.vit_attention`` — the decoder's flash forward / dQ / dK+dV kernels in
                                           their bidirectional form (tokens and head_dim zero-padded to 128-multiples)
   SwiGLU (DINOv2-g)                     : ``ops.swiglu`` (HIP forward + backward)
-  CLS / position rows, LayerScale, token-grid resize : plain torch ops on the GPU (small, pointwise / tiny)
+  token-grid resize                     : ``ops.resample_bilinear`` (HIP forward + adjoint backward)
+  CLS / position rows, LayerScale       : plain torch ops on the GPU (small, pointwise / tiny)
 
 Weights that need padding for the GEMM's K-step (14x14x3 patches -> 640 columns, SigLIP's 4304-wide MLP -> 4352) are
 padded on the fly from the masters, so gradients land on the un-padded parameters.  bf16 compute only.
@@ -43,15 +44,14 @@ def _key(name: str) -> str:
 
 
 def resample_tokens_autograd(x: torch.Tensor, target_tokens: int) -> torch.Tensor:
-    """clip_encoder.py:70-96 / siglip_encoder.py:67-93 / dino_encoder.py:128-154 verbatim in torch (fp32 bilinear,
-    align_corners=False) so that it back-propagates; the frozen path uses the HIP resample kernel instead."""
+    """clip_encoder.py:70-96 / siglip_encoder.py:67-93 / dino_encoder.py:128-154 (fp32 bilinear, align_corners=False) so that
+    it back-propagates: ``ops.resample_bilinear`` — the frozen path's resample kernel forward, its adjoint kernel backward;
+    the ATen body of the reference under ``CAMBRIAN_AMD_RESAMPLE_BWD=0``."""
     B, T, C = x.shape
     if T == target_tokens:
         return x
     hi, ho = int(T ** 0.5), int(target_tokens ** 0.5)
-    y = x.view(B, hi, hi, C).permute(0, 3, 1, 2).contiguous()
-    y = F.interpolate(y.to(torch.float32), size=(ho, ho), mode="bilinear", align_corners=False).to(x.dtype)
-    return y.permute(0, 2, 3, 1).contiguous().flatten(1, 2)
+    return ops.resample_bilinear(x, hi, hi, ho, ho)
 
 
 class TrainableViT(nn.Module):

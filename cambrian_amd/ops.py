@@ -2181,6 +2181,121 @@ def decode_attention_enabled() -> bool:
     return os.environ.get("CAMBRIAN_AMD_DECODE_ATTN", "1") != "0"
 
 
+# ================================================================================================
+# bilinear token-grid resample that back-propagates on our own kernels (elementwise.hip: resample_kernel and its adjoint
+# resample_bwd_kernel) — the trainable towers' 27^2 -> 24^2 / multi-stage -> 96^2 resize and the S5 query-group resize
+# ================================================================================================
+def resample_enabled() -> bool:
+    """``CAMBRIAN_AMD_RESAMPLE_BWD=0`` in the environment: every resize that carries a gradient (and the eval-path query-group
+    resize) takes the ATen body — permute, fp32 up-cast, ``F.interpolate``, cast, permute (A/B runs)."""
+    return os.environ.get("CAMBRIAN_AMD_RESAMPLE_BWD", "1") != "0"
+
+
+def resample_supported(dtype: torch.dtype, channels: int) -> bool:
+    """What ``cmb_resample_bilinear`` / ``_bwd`` take: bf16 / fp32 rows of a multiple of 8 channels."""
+    return dtype in (torch.bfloat16, torch.float32) and channels > 0 and channels % 8 == 0
+
+
+def _resample_aten(x: torch.Tensor, hi: int, wi: int, ho: int, wo: int) -> torch.Tensor:
+    """The reference's own resize (clip_encoder.py:83-88, cambrian_arch.py:395-401): NCHW, fp32, align_corners=False."""
+    B, _, C = x.shape
+    y = x.reshape(B, hi, wi, C).permute(0, 3, 1, 2)
+    y = F.interpolate(y.to(torch.float32), size=(ho, wo), mode="bilinear", align_corners=False).to(x.dtype)
+    return y.permute(0, 2, 3, 1).reshape(B, ho * wo, C)
+
+
+def _vec8_rows(t: torch.Tensor) -> torch.Tensor:
+    """``t`` itself when the kernels' 16-byte row accesses can walk it in place (unit last stride, every other stride a
+    multiple of 8 elements, an aligned base), else a contiguous copy."""
+    if t.stride(-1) == 1 and all(st % 8 == 0 for st in t.stride()[:-1]) and t.data_ptr() % 16 == 0:
+        return t
+    return t.contiguous()
+
+
+class ResampleBilinearFn(torch.autograd.Function):
+    """x [B, hi*wi, C] (strided rows are read in place) -> [B, ho*wo, C]; backward = the adjoint gather kernel."""
+
+    @staticmethod
+    def forward(ctx, x, hi: int, wi: int, ho: int, wo: int):
+        from .model.multimodal_encoder import vit_ops
+        x = _vec8_rows(x)
+        B, _, C = x.shape
+        out = torch.empty((B, ho * wo, C), dtype=x.dtype, device=x.device)
+        vit_ops.k_resample(x, hi, wi, out, ho, wo)
+        ctx.grids = (hi, wi, ho, wo)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        from .model.multimodal_encoder import vit_ops
+        hi, wi, ho, wo = ctx.grids
+        g = _vec8_rows(g)
+        dx = torch.empty((g.shape[0], hi * wi, g.shape[2]), dtype=g.dtype, device=g.device)
+        vit_ops.k_resample_bwd(g, ho, wo, dx, hi, wi)
+        return dx, None, None, None, None
+
+
+def resample_bilinear(x: torch.Tensor, hi: int, wi: int, ho: int, wo: int) -> torch.Tensor:
+    """Bilinear resize (fp32 lerp, align_corners=False) of the token grid x [B, hi*wi, C] to [B, ho*wo, C], channels-last both
+    ways; ``x`` itself when the grids are equal.  Differentiable: forward ``cmb_resample_bilinear``, backward its exact adjoint
+    ``cmb_resample_bilinear_bwd`` (deterministic, no fp32 NCHW copies).  The ATen body runs instead under
+    ``CAMBRIAN_AMD_RESAMPLE_BWD=0`` and for inputs the kernels do not take."""
+    if x.dim() != 3 or x.shape[1] != hi * wi:
+        raise L.CambrianAmdError(f"resample_bilinear: x {tuple(x.shape)} is not [B, {hi}*{wi}, C]")
+    if (hi, wi) == (ho, wo):
+        return x
+    if not (resample_enabled() and resample_supported(x.dtype, x.shape[2])):
+        return _resample_aten(x, hi, wi, ho, wo)
+    return ResampleBilinearFn.apply(x, hi, wi, ho, wo)
+
+
+class ResampleConcatFn(torch.autograd.Function):
+    """maps[s] NHWC [B, Hs, Ws, Cs] -> [B, side*side, sum Cs]: one forward launch per map into its column slice of the one
+    buffer, one backward launch per map that needs a gradient, reading its slice of the incoming gradient in place."""
+
+    @staticmethod
+    def forward(ctx, side: int, *maps):
+        from .model.multimodal_encoder import vit_ops
+        B = maps[0].shape[0]
+        out = torch.empty((B, side * side, sum(m.shape[3] for m in maps)), dtype=maps[0].dtype, device=maps[0].device)
+        off = 0
+        for m in maps:
+            _, Hs, Ws, Cs = m.shape
+            vit_ops.k_resample(_vec8_rows(m.reshape(B, Hs * Ws, Cs)), Hs, Ws, out, side, side, col_offset=off)
+            off += Cs
+        ctx.side, ctx.shapes = side, [tuple(m.shape) for m in maps]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        from .model.multimodal_encoder import vit_ops
+        g = _vec8_rows(g)
+        grads, off = [], 0
+        for k, (B, Hs, Ws, Cs) in enumerate(ctx.shapes):
+            dx = None
+            if ctx.needs_input_grad[1 + k]:
+                dx = torch.empty((B, Hs * Ws, Cs), dtype=g.dtype, device=g.device)
+                vit_ops.k_resample_bwd(g, ctx.side, ctx.side, dx, Hs, Ws, col_offset=off)
+                dx = dx.view(B, Hs, Ws, Cs)
+            grads.append(dx)
+            off += Cs
+        return (None, *grads)
+
+
+def resample_concat(maps: Sequence[torch.Tensor], out_side: int) -> torch.Tensor:
+    """The ConvNeXt multi-stage output (clip_convnext_encoder.py:99-119,143): every map [B, Hs, Ws, Cs] bilinearly resized to
+    out_side x out_side and channel-concatenated, [B, out_side^2, sum Cs], as ONE differentiable operator — no per-map
+    output, no ``torch.cat``, and a backward that reads the concatenated gradient where it lies."""
+    maps = list(maps)
+    if not maps or any(m.dim() != 4 or m.shape[0] != maps[0].shape[0] or m.dtype != maps[0].dtype for m in maps):
+        raise L.CambrianAmdError("resample_concat: maps are [B, Hs, Ws, Cs] tensors of one batch size and dtype")
+    if not (resample_enabled() and all(resample_supported(m.dtype, m.shape[3]) for m in maps)):
+        B = maps[0].shape[0]
+        return torch.cat([_resample_aten(m.reshape(B, m.shape[1] * m.shape[2], m.shape[3]), m.shape[1], m.shape[2], out_side,
+                                         out_side) for m in maps], -1)
+    return ResampleConcatFn.apply(out_side, *maps)
+
+
 class AddRmsNormFn(torch.autograd.Function):
     """(s, y) = (x + delta, rmsnorm(x + delta) * w) in one pass — the decoder layer's "h = h + attn; mlp_in = norm(h)".
     Backward: d(x) = d(delta) = g_s + rmsnorm_backward(g_y), also one pass when the weight is frozen."""

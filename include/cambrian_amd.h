@@ -64,11 +64,12 @@ const char* cmb_version(void);
 /* ABI revision: bumped whenever an entry point's signature or a descriptor's layout changes (round 2's key_valid
  * arguments = 2, round 3's fold_kv workspace = 3, the batch fields of cmb_gemm_desc = 4,
  * the kernel-selection knobs of round 4 = 5, cmb_layernorm_fwd_multi = 9, cmb_ln_multi_desc.dx_out = 10, the workspaces of
- * the deterministic column sums = 11, cmb_decode_attn and its plan / workspace queries = 12).  Bindings must compare it
+ * the deterministic column sums = 11, cmb_decode_attn and its plan / workspace queries = 12,
+ * cmb_resample_bilinear_bwd = 13).  Bindings must compare it
  * with the revision they
  * were written against (CMB_ABI_VERSION; cambrian_amd/lib.py::load raises on a mismatch): every symbol of a stale
  * library still resolves, and a shifted argument list corrupts memory instead of failing. */
-#define CMB_ABI_VERSION 12
+#define CMB_ABI_VERSION 13
 int cmb_abi_version(void);
 
 /* Run-time kernel-selection knobs: which of several kernels that compute the SAME function an entry point launches
@@ -528,6 +529,15 @@ int cmb_dwconv7x7_wgrad(int dtype, const void* x, const void* dy, int64_t B, int
 int cmb_resample_bilinear(int dtype, const void* in, int64_t B, int32_t Hi, int32_t Wi, int64_t C,
                           int64_t ld_in, int64_t batch_stride_in, void* out, int32_t Ho, int32_t Wo,
                           int64_t ld_out, int64_t batch_stride_out, void* stream);
+/* Exact adjoint of cmb_resample_bilinear (towers that train, the S5 query-group resize): dout [B, Ho*Wo, ...] read at the
+ * pointer given with row stride ld_dout (a column slice of the concatenated gradient is read in place) -> din [B, Hi*Wi, C],
+ * written in full: a cell no output refers to gets an exact 0, nothing is accumulated into and no memset is needed.  Gather
+ * form, one thread per (input cell, 8 channels), fp32 sum in a fixed order (oy, then ox, ascending), rounded once: no
+ * atomics, bit-reproducible, and the weights are the forward's own (csrc/resample_core.h).  Replaces ATen's
+ * upsample_bilinear2d_backward and the fp32 NCHW copies around it. */
+int cmb_resample_bilinear_bwd(int dtype, const void* dout, int64_t B, int32_t Ho, int32_t Wo, int64_t C,
+                              int64_t ld_dout, int64_t batch_stride_dout, void* din, int32_t Hi, int32_t Wi,
+                              int64_t ld_din, int64_t batch_stride_din, void* stream);
 /* Elementwise y = act(a) * b (SwiGLU: act = SiLU) / y = act(a); a,b,y [rows, D] with strides. */
 int cmb_act_mul(int dtype, int32_t act, const void* a, int64_t lda, const void* b, int64_t ldb,
                 int64_t rows, int64_t D, void* y, int64_t ldy, void* stream);
