@@ -7,6 +7,10 @@
 // with scale = n_in / n_out in float.  The adjoint gathers: input i sums over the outputs that name it.  src is monotone in
 // o, so those outputs form one contiguous run; cmb_resample_window gives a conservative candidate range from the inverse map
 // and cmb_resample_weight decides membership and weight by calling lerp_index itself, so that the two kernels cannot disagree.
+//
+// cmb_resample_accum (resample_accum.hip) sums up to CMB_RESAMPLE_ACCUM_MAX_SRC resized maps onto a base: its thread -> cell
+// decomposition and the whole per-cell sum are cmb_resample_accum_decode / cmb_resample_accum_cell below, run on the CPU by
+// tests/csrc/resample_accum_sim.cpp.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -55,3 +59,54 @@ CMB_PHD void cmb_resample_window(int i, int n_in, int n_out, int& lo, int& hi) {
 // the trip count the adjoint kernel's per-axis loops are sized for: the 2 / scale outputs of the interval above (2.5 / scale
 // for input 1, whose window reaches down to output 0), its two end points and the two widening outputs.
 CMB_PHD int cmb_resample_window_bound(int n_in, int n_out) { return (5 * ((n_out + n_in - 1) / n_in) + 1) / 2 + 4; }
+
+// ---- cmb_resample_accum: pre = base + bias + sum_s lerp_s(src_s), one (output cell, 8 channels) at a time ----------------
+#ifndef CMB_RESAMPLE_ACCUM_MAX_SRC
+#define CMB_RESAMPLE_ACCUM_MAX_SRC 4
+#endif
+
+// work item i of B * Ho * Wo * nv (nv = C / 8 channel vectors, fastest) -> (batch, oy, ox, channel vector): consecutive
+// lanes walk the channels of one cell, then the cells of a row — every access of a wave is one contiguous run per row
+CMB_PHD void cmb_resample_accum_decode(int64_t i, int nv, int Ho, int Wo, int64_t& b, int& oy, int& ox, int& cv) {
+  const int64_t cell = i / nv;
+  cv = (int)(i - cell * nv);
+  const int cells = Ho * Wo;
+  b = cell / cells;
+  const int r = (int)(cell - b * cells);
+  oy = r / Wo;
+  ox = r - oy * Wo;
+}
+
+// one source's bilinear sample of cell (oy, ox): the forward kernel's own expression (resample_kernel), on the four
+// neighbours that lerp_index names.  load(row, v) reads the 8 channels of source row `row` = y * Wi + x as floats.
+template <typename Load>
+CMB_PHD void cmb_resample_lerp8(int oy, int ox, int Hi, int Wi, int Ho, int Wo, Load&& load, float (&o)[8]) {
+  const float sy = (float)Hi / (float)Ho, sx = (float)Wi / (float)Wo;
+  int y0, y1, x0, x1;
+  float ly, lx;
+  lerp_index(oy, sy, Hi, y0, y1, ly);
+  lerp_index(ox, sx, Wi, x0, x1, lx);
+  float v00[8], v01[8], v10[8], v11[8];
+  load((int64_t)y0 * Wi + x0, v00);
+  load((int64_t)y0 * Wi + x1, v01);
+  load((int64_t)y1 * Wi + x0, v10);
+  load((int64_t)y1 * Wi + x1, v11);
+  const float hy = 1.f - ly, hx = 1.f - lx;
+  for (int e = 0; e < 8; ++e) o[e] = hy * (hx * v00[e] + lx * v01[e]) + ly * (hx * v10[e] + lx * v11[e]);
+}
+
+// the cell's pre-activation: acc = base + bias on entry (zeros where absent), then the sources are added in list order, in
+// fp32; the caller rounds once.  load(s, row, v) reads source s.
+template <typename Load>
+CMB_PHD void cmb_resample_accum_cell(int oy, int ox, int Ho, int Wo, int n_src, const int32_t* Hi, const int32_t* Wi,
+                                     Load&& load, float (&acc)[8]) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int s = 0; s < CMB_RESAMPLE_ACCUM_MAX_SRC; ++s) {
+    if (s >= n_src) break;
+    float o[8];
+    cmb_resample_lerp8(oy, ox, Hi[s], Wi[s], Ho, Wo, [&](int64_t row, float (&v)[8]) { load(s, row, v); }, o);
+    for (int e = 0; e < 8; ++e) acc[e] += o[e];
+  }
+}

@@ -150,6 +150,24 @@ class PrepJob(C.Structure):
     ]
 
 
+RESAMPLE_ACCUM_MAX_SRC = 4
+
+
+class ResampleAccumDesc(C.Structure):
+    """cmb_resample_accum_desc (include/cambrian_amd.h): resized partial products summed onto a base, bias, activation."""
+    _fields_ = [
+        ("dtype", C.c_int32), ("src_dtype", C.c_int32), ("act", C.c_int32), ("n_src", C.c_int32),
+        ("B", C.c_int64), ("Ho", C.c_int32), ("Wo", C.c_int32), ("C", C.c_int64),
+        ("base", C.c_void_p), ("ld_base", C.c_int64), ("batch_stride_base", C.c_int64),
+        ("bias", C.c_void_p),
+        ("src", C.c_void_p * RESAMPLE_ACCUM_MAX_SRC),
+        ("Hi", C.c_int32 * RESAMPLE_ACCUM_MAX_SRC), ("Wi", C.c_int32 * RESAMPLE_ACCUM_MAX_SRC),
+        ("ld_src", C.c_int64 * RESAMPLE_ACCUM_MAX_SRC), ("batch_stride_src", C.c_int64 * RESAMPLE_ACCUM_MAX_SRC),
+        ("pre_out", C.c_void_p), ("ld_pre", C.c_int64), ("batch_stride_pre", C.c_int64),
+        ("out", C.c_void_p), ("ld_out", C.c_int64), ("batch_stride_out", C.c_int64),
+    ]
+
+
 # symbol -> (restype, argtypes); every symbol of include/cambrian_amd.h must be listed here
 # (tests/test_abi.py cross-checks this table against the header).
 _i32, _i64, _f, _p = C.c_int32, C.c_int64, C.c_float, C.c_void_p
@@ -208,6 +226,7 @@ SIGNATURES = {
     "cmb_dwconv7x7_wgrad": (C.c_int, [C.c_int, _p, _p, _i64, _i64, _i64, _i64, _p, _i32, _p]),
     "cmb_resample_bilinear": (C.c_int, [C.c_int, _p, _i64, _i32, _i32, _i64, _i64, _i64, _p, _i32, _i32, _i64, _i64, _p]),
     "cmb_resample_bilinear_bwd": (C.c_int, [C.c_int, _p, _i64, _i32, _i32, _i64, _i64, _i64, _p, _i32, _i32, _i64, _i64, _p]),
+    "cmb_resample_accum": (C.c_int, [C.POINTER(ResampleAccumDesc), _p]),
     "cmb_act_mul": (C.c_int, [C.c_int, _i32, _p, _i64, _p, _i64, _i64, _i64, _p, _i64, _p]),
     "cmb_act_bwd": (C.c_int, [C.c_int, _i32, _p, _p, _i64, _p, _p]),
     "cmb_bcast_rows": (C.c_int, [C.c_int, _p, _i64, _i64, _i64, _p, _p]),

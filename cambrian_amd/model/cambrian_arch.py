@@ -344,6 +344,9 @@ class CambrianMetaForCausalLM(ABC):
                     if gain > best:
                         best, pair = gain, (i, j)
         outs = [None] * len(towers) if outs is None else outs
+        cfg = self.get_model().config
+        # stage maps instead of their resized concatenation, for the aux projector to commute the resize (ops.linear_stage_maps)
+        want_maps = getattr(cfg, "mm_projector_type", None) == "sva" and ops.commuted_proj_enabled(cfg)
         for k, (image_aux, tower) in enumerate(zip(image_aux_list, towers)):
             if only is not None and k not in only:
                 continue
@@ -357,8 +360,21 @@ class CambrianMetaForCausalLM(ABC):
                 outs[i] = ta._forward(image_aux_list[i], trunk_out=sa)
                 outs[j] = tb._forward(image_aux_list[j], trunk_out=sb)
             else:
-                outs[k] = tower(image_aux)
+                maps = tower.forward_stage_maps(image_aux) if want_maps and hasattr(tower, "forward_stage_maps") else None
+                outs[k] = maps if maps is not None else tower(image_aux)
         return outs
+
+    def _project_aux(self, aux_i: int, f, dtype):
+        """mm_projector_aux_i on tower i's output (both paths: :372-379 static, :366-371 dynamic).  ``f`` is the tower's
+        [B, T, C] tensor, or — commuted aux projection switched on, multi-stage tower — its ``ops.StageMaps``, which a
+        HipSequential projector consumes as it is."""
+        proj = getattr(self.get_model(), f"mm_projector_aux_{aux_i}")
+        if isinstance(f, ops.StageMaps):
+            if f.dtype != dtype or not isinstance(proj, HipSequential):
+                f = f.concat()
+            else:
+                return proj(f).to(dtype)
+        return proj(f.to(dtype)).to(dtype)
 
     # ------------------------------------------------------------------------------------------
     def prepare_inputs_labels_for_multimodal(self, input_ids, position_ids, attention_mask, past_key_values, labels,
@@ -393,8 +409,7 @@ class CambrianMetaForCausalLM(ABC):
             samplers = [getattr(model, f"vision_sampler_{g}") for g in range(len(cfg.query_num_list))]
             samplers += list(getattr(model, "vision_sampler_layers", []) or [])
             for aux_i in range(len(towers)):                                         # :372-379
-                f = feats_raw[aux_i]
-                f = getattr(model, f"mm_projector_aux_{aux_i}")(f.to(dtype)).to(dtype)
+                f = self._project_aux(aux_i, feats_raw[aux_i], dtype)
                 holders.append(ops.GradAccumulator())
                 f2 = f.reshape(-1, vh)
                 tables = [t for sm in samplers for t in sm.pos_tables(aux_i)]
@@ -457,7 +472,7 @@ class CambrianMetaForCausalLM(ABC):
         feats_raw = self.encode_images(images)
         kv_final = mask_final = ctx_final = None
         if cfg.mm_projector_type == "sva":
-            feats = [getattr(model, f"mm_projector_aux_{i}")(feats_raw[i].to(dtype)).to(dtype) for i in range(len(towers))]
+            feats = [self._project_aux(i, feats_raw[i], dtype) for i in range(len(towers))]
             ctx_b = ops.token_mean(feats[0])                                           # [B, C] (:377)
             ctx = ctx_b.view(bs, 1, 1, -1)
             group_out = []

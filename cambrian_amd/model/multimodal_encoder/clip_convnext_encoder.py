@@ -94,6 +94,24 @@ class CLIPConvNextTower(BaseVisionTower):
             return feats.to(images.dtype) if images.dtype in (torch.float32, torch.bfloat16) else feats
 
     @property
+    def offers_stage_maps(self) -> bool:
+        """Only the multi-stage towers with an interp size resize and concatenate stage maps."""
+        return bool(self.is_multi_stage and self._interp_size is not None)
+
+    def forward_stage_maps(self, images):
+        """``forward`` without the resize + concat: an ``ops.StageMaps`` holder (the four stage maps and the output side)
+        whose ``concat()`` is ``forward(images)``, for a projector that commutes the resize behind its first linear; None
+        when this tower has no such stage (single-stage or no interp size) or ``images`` is a per-sample list."""
+        if not self.offers_stage_maps or type(images) is list:
+            return None
+        from ... import ops
+        with self._grad_mode():
+            maps = self.vision_tower.forward_maps(images.to(device=self.device))
+            if images.dtype in (torch.float32, torch.bfloat16):
+                maps = [m.to(images.dtype) for m in maps]
+            return ops.StageMaps(maps, self.num_patches_per_side)
+
+    @property
     def image_size(self):
         return self._image_size
 

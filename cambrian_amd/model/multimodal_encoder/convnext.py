@@ -164,6 +164,12 @@ class ConvNeXtTrunk(nn.Module):
         return outs
 
     @torch.no_grad()
+    def forward_maps(self, images: torch.Tensor) -> List[torch.Tensor]:
+        """The stage maps ``forward(..., multi_stage=True)`` would resize and concatenate, as they are: for a projector
+        that commutes the resize behind its first linear (``ops.linear_stage_maps``)."""
+        return self.forward_stages(images)
+
+    @torch.no_grad()
     def forward(self, images: torch.Tensor, out_side: Optional[int], multi_stage: bool = True) -> torch.Tensor:
         """-> [B, out_side^2, sum(dims)] (multi-stage) or [B, out_side^2, dims[-1]]; out_side None keeps the
         last stage's own grid (clip_convnext_encoder.py:99-119: no resize when _interp_size is None)."""

@@ -139,6 +139,11 @@ class TrainableConvNeXt(nn.Module):
             outs.append(x.view(B, H, H, c))
         return outs
 
+    def forward_maps(self, images: torch.Tensor) -> List[torch.Tensor]:
+        """The stage maps ``forward(..., multi_stage=True)`` would resize and concatenate, as they are (with their graph):
+        for a projector that commutes the resize behind its first linear (``ops.linear_stage_maps``)."""
+        return self.forward_stages(images)
+
     def forward(self, images: torch.Tensor, out_side: Optional[int], multi_stage: bool = True) -> torch.Tensor:
         """clip_convnext_encoder.py:99-144: every kept stage map bilinearly resized (fp32, align_corners=False) to
         out_side x out_side, flattened, channel-concatenated."""

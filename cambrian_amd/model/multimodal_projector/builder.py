@@ -19,11 +19,25 @@ class HipSequential(nn.Sequential):
     the aux projectors, whose rows are all tower tokens) lets ``ops.fp8_projections`` move its GEMMs to the fp8 MFMA."""
     fp8_heavy = False
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        shape = x.shape
-        y = x.reshape(-1, shape[-1])
+    def forward(self, x) -> torch.Tensor:
         mods = list(self)
         i = 0
+        if isinstance(x, ops.StageMaps):
+            # a multi-stage tower's maps instead of their resized concatenation: the leading Linear (+ GELU) commutes the
+            # resize behind its projection (ops.linear_stage_maps); anything else gets the tower's ordinary output
+            if mods and isinstance(mods[0], nn.Linear):
+                fuse = len(mods) > 1 and isinstance(mods[1], nn.GELU)
+                if fuse and getattr(mods[1], "approximate", "none") != "none":
+                    raise L.CambrianAmdError("only the exact-erf nn.GELU() of the reference is fused")
+                shape = x.shape
+                y = ops.linear_stage_maps(x.maps, x.side, mods[0].weight, mods[0].bias,
+                                          act=L.ACT_GELU_ERF if fuse else L.ACT_NONE, heavy=self.fp8_heavy, enabled=True)
+                i = 2 if fuse else 1
+            else:
+                x = x.concat()
+        if i == 0:
+            shape = x.shape
+            y = x.reshape(-1, shape[-1])
         while i < len(mods):
             m = mods[i]
             if isinstance(m, nn.Linear):

@@ -2352,3 +2352,289 @@ class AddRmsNormFn(torch.autograd.Function):
 
 def add_rmsnorm(x, delta, weight, eps: float = 1e-6):
     return AddRmsNormFn.apply(x, delta, weight, eps)
+
+
+# ================================================================================================
+# linear over channel-concatenated resized stage maps with the resize commuted behind the projection: bilinear resizing acts
+# on positions, the linear on channels, so R_s(X_s) W_s^T = R_s(X_s W_s^T).  A stage with fewer positions than the output
+# grid is projected at its own resolution and only the N-wide product is resized and summed (cmb_resample_accum); at the
+# ConvNeXt-XXL aux projector (stages 64^2 and 32^2 hold 4608 of 5760 channels, output 96^2) the forward and weight-gradient
+# GEMM work falls from 2.61 to 0.98 TFLOP per step and the resized stage-3/4 channels are never written.  Opt-in.
+# ================================================================================================
+def commuted_proj_enabled(config=None) -> bool:
+    """``CAMBRIAN_AMD_COMMUTED_PROJ=1`` in the environment (read at call time) or ``config.mm_commuted_aux_projection``.
+    Off by default: every path is then exactly what it was."""
+    return os.environ.get("CAMBRIAN_AMD_COMMUTED_PROJ", "0") == "1" or bool(getattr(config, "mm_commuted_aux_projection", False))
+
+
+# partial products (the dense stages' ``base`` and every commuted stage's Y_s) in fp32: the pre-activation is then rounded
+# once, as in the one unfused GEMM (CPU emulation: error 0.74-0.94 x the unfused path's; with bf16 partials 0.75-1.36 x).  The
+# price is the wider base / Y_s traffic of cmb_resample_accum.  CAMBRIAN_AMD_COMMUTED_PROJ_F32=0 keeps them in the compute
+# dtype (A/B runs, tools/bench_commuted_proj.py).
+def _commuted_f32_partials() -> bool:
+    return os.environ.get("CAMBRIAN_AMD_COMMUTED_PROJ_F32", "1") != "0"
+
+
+def stage_maps_plan(grids, out_side: int) -> List[bool]:
+    """Which stages of ``linear_stage_maps`` are commuted (True: projected at their own resolution, product resized) and
+    which are dense (False: resized first): a stage is commuted iff it has fewer positions than the output grid.  ``grids``
+    holds a side or an (H, W) pair per stage.  Pure: no tensors, no device."""
+    out = []
+    for g in grids:
+        h, w = (g, g) if isinstance(g, int) else g
+        out.append(h * w < out_side * out_side)
+    return out
+
+
+def k_resample_accum(out: torch.Tensor, ho: int, wo: int, *, base: Optional[torch.Tensor] = None,
+                     bias: Optional[torch.Tensor] = None, srcs: Sequence[Tuple[torch.Tensor, int, int]] = (),
+                     pre_out: Optional[torch.Tensor] = None, act: int = L.ACT_NONE) -> torch.Tensor:
+    """out = act(base + bias + sum_s bilinear(src_s -> ho x wo)) on cmb_resample_accum.  ``out`` / ``pre_out`` / ``base`` are
+    [B, ho*wo, C] (column slices of wider buffers are walked in place), ``srcs`` a list of (x [B, hi*wi, C], hi, wi), ``bias``
+    fp32 [C].  base and the sources share one dtype: ``out``'s, or fp32 under a bf16 ``out``."""
+    tens = [t for t in (base, pre_out) if t is not None] + [s[0] for s in srcs]
+    L.require_gpu(out, bias, *tens)
+    if out.dim() != 3 or out.shape[1] != ho * wo or any(t.dim() != 3 or t.stride(2) != 1 for t in [out] + tens):
+        raise L.CambrianAmdError("resample_accum: operands are [B, positions, C] with a unit channel stride")
+    B, _, Cc = out.shape
+    for t in (base, pre_out):
+        if t is not None and tuple(t.shape) != (B, ho * wo, Cc):
+            raise L.CambrianAmdError("resample_accum: base / pre_out must have the shape of out")
+    if pre_out is not None and pre_out.dtype != out.dtype:
+        raise L.CambrianAmdError("resample_accum: pre_out has the dtype of out")
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous() or bias.numel() != Cc):
+        raise L.CambrianAmdError("resample_accum: bias must be contiguous fp32 [C]")
+    if len(srcs) > L.RESAMPLE_ACCUM_MAX_SRC:
+        raise L.CambrianAmdError(f"resample_accum: at most {L.RESAMPLE_ACCUM_MAX_SRC} sources")
+    src_t = [base] if base is not None else []
+    src_t += [s[0] for s in srcs]
+    sdt = src_t[0].dtype if src_t else out.dtype
+    if any(t.dtype != sdt for t in src_t):
+        raise L.CambrianAmdError("resample_accum: base and the sources share one dtype")
+    d = L.ResampleAccumDesc()
+    d.dtype, d.src_dtype, d.act, d.n_src = L.dtype_code(out.dtype), L.dtype_code(sdt), act, len(srcs)
+    d.B, d.Ho, d.Wo, d.C = B, ho, wo, Cc
+    d.base = L.ptr(base)
+    d.ld_base, d.batch_stride_base = (base.stride(1), base.stride(0)) if base is not None else (0, 0)
+    d.bias = L.ptr(bias)
+    for k, (x, hi, wi) in enumerate(srcs):
+        if tuple(x.shape) != (B, hi * wi, Cc):
+            raise L.CambrianAmdError(f"resample_accum: source {k} is {tuple(x.shape)}, not [{B}, {hi}*{wi}, {Cc}]")
+        d.src[k], d.Hi[k], d.Wi[k], d.ld_src[k], d.batch_stride_src[k] = x.data_ptr(), hi, wi, x.stride(1), x.stride(0)
+    d.pre_out = L.ptr(pre_out)
+    d.ld_pre, d.batch_stride_pre = (pre_out.stride(1), pre_out.stride(0)) if pre_out is not None else (0, 0)
+    d.out, d.ld_out, d.batch_stride_out = out.data_ptr(), out.stride(1), out.stride(0)
+    L.check(L.load().cmb_resample_accum(C.byref(d), L.stream_ptr(out.device)), "cmb_resample_accum")
+    return out
+
+
+def _rows2d(m: torch.Tensor) -> torch.Tensor:
+    """NHWC map [B, H, W, C] as GEMM rows [B*H*W, C] (in place when the 16-byte row accesses can walk it)."""
+    x = m.reshape(-1, m.shape[-1])
+    if x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
+        x = x.contiguous()
+    return x
+
+
+def concat_stage_maps(maps: Sequence[torch.Tensor], out_side: int) -> torch.Tensor:
+    """maps [B, Hs, Ws, Cs] -> [B, out_side^2, sum Cs]: the towers' own multi-stage output.  Maps that carry no gradient
+    (frozen towers) go through ``cmb_resample_bilinear`` directly, as ConvNeXtTrunk.forward does; the rest through the
+    differentiable ``resample_concat``."""
+    maps = list(maps)
+    if torch.is_grad_enabled() and any(m.requires_grad for m in maps):
+        return resample_concat(maps, out_side)
+    from .model.multimodal_encoder import vit_ops
+    B = maps[0].shape[0]
+    out = torch.empty((B, out_side * out_side, sum(m.shape[3] for m in maps)), dtype=maps[0].dtype, device=maps[0].device)
+    off = 0
+    for m in maps:
+        _, Hs, Ws, Cs = m.shape
+        vit_ops.k_resample(_vec8_rows(m.reshape(B, Hs * Ws, Cs)), Hs, Ws, out, out_side, out_side, col_offset=off)
+        off += Cs
+    return out
+
+
+class StageMaps:
+    """What a multi-stage tower hands the projector when the resize is to be commuted behind the projection: the stage maps
+    [B, Hs, Ws, Cs] and the side of the common output grid, instead of their resized concatenation.  ``shape`` / ``dtype`` /
+    ``device`` are those of the tensor ``concat()`` returns — the tower's ordinary [B, side^2, sum Cs] output."""
+
+    def __init__(self, maps: Sequence[torch.Tensor], side: int):
+        self.maps, self.side = list(maps), int(side)
+
+    @property
+    def shape(self) -> torch.Size:
+        return torch.Size((self.maps[0].shape[0], self.side * self.side, sum(m.shape[3] for m in self.maps)))
+
+    @property
+    def dtype(self) -> torch.dtype:
+        return self.maps[0].dtype
+
+    @property
+    def device(self) -> torch.device:
+        return self.maps[0].device
+
+    @property
+    def requires_grad(self) -> bool:
+        return any(m.requires_grad for m in self.maps)
+
+    def concat(self) -> torch.Tensor:
+        return concat_stage_maps(self.maps, self.side)
+
+
+def _wgrad_into(g: torch.Tensor, x: torch.Tensor, out: torch.Tensor) -> None:
+    """out[N, K] (a column slice of the one fp32 weight gradient, row stride out.stride(0)) = g[R, N]^T x[R, K]: the two
+    routes of LinearFn.backward, writing in place."""
+    R, N = g.shape
+    K = x.shape[1]
+    dt = g.dtype
+    if (dt == torch.bfloat16 and R > 0 and N % 8 == 0 and K % 8 == 0 and x.stride(1) == 1 and x.stride(0) % 8 == 0
+            and x.data_ptr() % 16 == 0 and g.data_ptr() % 16 == 0 and g.stride(1) == 1 and g.stride(0) % 8 == 0
+            and TN_WGRAD and _tn_wgrad_wins(R, N, K)):
+        k_gemm_tn(g, x, out=out, split_k=_tn_splits(N, K, R), M=N, N=K, ldc=out.stride(0))
+    else:
+        ks = _kstep(dt)
+        m_pad = pad_to(R, ks)
+        k_gemm(k_transpose(g, m_pad), k_transpose(x, m_pad), out=out, split_k=_wgrad_splits(N, K, m_pad, ks))
+
+
+class LinearStageMapsFn(torch.autograd.Function):
+    """act(concat_s R_s(X_s) @ W^T + b) with the commuted stages projected at their own resolution (see the section head)."""
+
+    @staticmethod
+    def forward(ctx, side: int, weight, bias, act: int, f32_partials: bool, *maps):
+        from .model.multimodal_encoder import vit_ops
+        dt, dev = maps[0].dtype, maps[0].device
+        B, N, P = maps[0].shape[0], weight.shape[0], side * side
+        shapes = [tuple(m.shape) for m in maps]
+        plan = stage_maps_plan([(s[1], s[2]) for s in shapes], side)
+        offs = [0]
+        for s in shapes:
+            offs.append(offs[-1] + s[3])
+        prep = prepared_weight(weight, dt)
+        w_c, w_t = prep if prep is not None else (k_cast(weight, dt), None)
+        b_c = None if bias is None else k_cast(bias, torch.float32)
+        pdt = torch.float32 if f32_partials else dt
+        dense = [k for k, c in enumerate(plan) if not c]
+        xd = base = None
+        if dense:   # resized first, as today, into one buffer; one GEMM over their (contiguous) weight columns
+            d0, d1 = offs[dense[0]], offs[dense[-1] + 1]
+            xd = torch.empty((B, P, d1 - d0), dtype=dt, device=dev)
+            for k in dense:
+                _, Hs, Ws, Cs = shapes[k]
+                vit_ops.k_resample(_vec8_rows(maps[k].reshape(B, Hs * Ws, Cs)), Hs, Ws, xd, side, side, col_offset=offs[k] - d0)
+            base = k_gemm(xd.view(B * P, d1 - d0), w_c[:, d0:d1], out_dtype=pdt).view(B, P, N)
+        srcs, xs = [], []
+        for k, c in enumerate(plan):
+            if not c:
+                continue
+            _, Hs, Ws, Cs = shapes[k]
+            x = _rows2d(maps[k])
+            xs.append(x)
+            srcs.append((k_gemm(x, w_c[:, offs[k]:offs[k + 1]], out_dtype=pdt).view(B, Hs * Ws, N), Hs, Ws))
+        need_pre = act != L.ACT_NONE and any(ctx.needs_input_grad)
+        out = torch.empty((B * P, N), dtype=dt, device=dev)
+        pre = torch.empty((B * P, N), dtype=dt, device=dev) if need_pre else None
+        k_resample_accum(out.view(B, P, N), side, side, base=base, bias=b_c, srcs=srcs,
+                         pre_out=None if pre is None else pre.view(B, P, N), act=act)
+        ctx.side, ctx.act, ctx.shapes, ctx.plan, ctx.offs, ctx.dense = side, act, shapes, plan, offs, dense
+        ctx.has_bias, ctx.w_dtype, ctx.b_dtype = bias is not None, weight.dtype, None if bias is None else bias.dtype
+        ctx.has_wt = w_t is not None
+        ctx.save_for_backward(w_c, w_t, pre, xd, *xs)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        from .model.multimodal_encoder import vit_ops
+        w_c, w_t, pre, xd, *xs = ctx.saved_tensors
+        side, shapes, plan, offs, dense = ctx.side, ctx.shapes, ctx.plan, ctx.offs, ctx.dense
+        dt = w_c.dtype
+        B, P, N = shapes[0][0], side * side, w_c.shape[0]
+        need_w, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ctx.has_bias
+        need_m = list(ctx.needs_input_grad[5:])
+        g = _as_dtype_contig(dy, dt)
+        if ctx.act != L.ACT_NONE:
+            gp = torch.empty_like(pre)
+            L.check(L.load().cmb_act_bwd(L.dtype_code(dt), ctx.act, g.data_ptr(), pre.data_ptr(), pre.numel(), gp.data_ptr(),
+                                         L.stream_ptr(g.device)), "cmb_act_bwd")
+            g = gp
+        g3 = g.view(B, P, N)
+        dw = torch.empty((N, offs[-1]), dtype=torch.float32, device=g.device) if need_w else None
+        if any(need_m) and w_t is None:
+            w_t = k_transpose(w_c, N)                                   # [sum C, N]
+        grads = [None] * len(shapes)
+        if dense:
+            d0, d1 = offs[dense[0]], offs[dense[-1] + 1]
+            if need_w:
+                _wgrad_into(g, xd.view(B * P, d1 - d0), dw[:, d0:d1])
+            if any(need_m[k] for k in dense):                           # g W_dense, pushed through the adjoint resample
+                dxd = k_gemm(g, w_t[d0:d1, :N]).view(B, P, d1 - d0)
+                for k in dense:
+                    if need_m[k]:
+                        _, Hs, Ws, Cs = shapes[k]
+                        dx = torch.empty((B, Hs * Ws, Cs), dtype=dt, device=g.device)
+                        vit_ops.k_resample_bwd(dxd, side, side, dx, Hs, Ws, col_offset=offs[k] - d0)
+                        grads[k] = dx.view(B, Hs, Ws, Cs)
+        xi = 0
+        for k, c in enumerate(plan):
+            if not c:
+                continue
+            x = xs[xi]
+            xi += 1
+            if not (need_w or need_m[k]):
+                continue
+            _, Hs, Ws, Cs = shapes[k]
+            gs = torch.empty((B, Hs * Ws, N), dtype=dt, device=g.device)  # g_s = R_s^T g: the adjoint kernel on the shared d(pre)
+            vit_ops.k_resample_bwd(g3, side, side, gs, Hs, Ws)
+            gs = gs.view(B * Hs * Ws, N)
+            if need_w:
+                _wgrad_into(gs, x, dw[:, offs[k]:offs[k + 1]])
+            if need_m[k]:
+                grads[k] = k_gemm(gs, w_t[offs[k]:offs[k + 1], :N]).view(B, Hs, Ws, Cs)
+        if dw is not None and ctx.w_dtype != torch.float32:
+            dw = dw.to(ctx.w_dtype)
+        db = None
+        if need_b:
+            db = k_colsum(g)
+            if ctx.b_dtype != torch.float32:
+                db = db.to(ctx.b_dtype)
+        return (None, dw, db, None, None, *grads)
+
+
+def stage_maps_fusable(maps: Sequence[torch.Tensor], out_side: int, weight: torch.Tensor, bias: Optional[torch.Tensor],
+                       act: int) -> bool:
+    """What the commuted path takes: bf16 / fp32 NHWC maps of one batch on the GPU, at least one commuted stage and at most
+    ``RESAMPLE_ACCUM_MAX_SRC`` of them, dense stages that own one contiguous run of weight columns, every channel count and
+    N a multiple of the GEMM's K step (weight column slices are read in place through ``ldb``), no activation but erf-GELU."""
+    maps = list(maps)
+    if not maps or any(m.dim() != 4 or not m.is_cuda or m.shape[0] != maps[0].shape[0] or m.dtype != maps[0].dtype for m in maps):
+        return False
+    dt = maps[0].dtype
+    if dt not in (torch.bfloat16, torch.float32) or act not in (L.ACT_NONE, L.ACT_GELU_ERF):
+        return False
+    ks = _kstep(dt)
+    if (weight.dim() != 2 or not weight.is_cuda or weight.stride(1) != 1 or weight.shape[1] != sum(m.shape[3] for m in maps)
+            or weight.dtype not in (torch.float32, dt) or weight.shape[0] % ks or any(m.shape[3] % ks for m in maps)):
+        return False
+    if bias is not None and (not bias.is_cuda or bias.numel() != weight.shape[0]):
+        return False
+    plan = stage_maps_plan([(m.shape[1], m.shape[2]) for m in maps], out_side)
+    dense = [k for k, c in enumerate(plan) if not c]
+    if not any(plan) or sum(plan) > L.RESAMPLE_ACCUM_MAX_SRC or (dense and dense != list(range(dense[0], dense[-1] + 1))):
+        return False
+    return True
+
+
+def linear_stage_maps(maps: Sequence[torch.Tensor], out_side: int, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                      act: int = L.ACT_NONE, heavy: bool = False, enabled: Optional[bool] = None) -> torch.Tensor:
+    """``linear(resample_concat(maps, out_side).reshape(-1, sum Cs), weight, bias, act)`` -> [B * out_side^2, N], with the
+    resize of every stage that has fewer positions than the output grid commuted behind its slice of the projection
+    (``stage_maps_plan``).  ``weight`` is the one [N, sum Cs] parameter; its gradient comes back whole.  The unfused
+    composition runs when the switch is off (``enabled``; None = ``commuted_proj_enabled()``), no stage would be commuted,
+    an input is something the kernels do not take, or ``fp8_projections`` is active for this (``heavy``) projector."""
+    maps = list(maps)
+    on = commuted_proj_enabled() if enabled is None else enabled
+    if not (on and not (heavy and _FP8_LINEAR) and stage_maps_fusable(maps, out_side, weight, bias, act)):
+        x = concat_stage_maps(maps, out_side)
+        return linear(x.reshape(-1, x.shape[-1]), weight, bias, act=act, heavy=heavy)
+    return LinearStageMapsFn.apply(out_side, weight, bias, act, _commuted_f32_partials(), *maps)

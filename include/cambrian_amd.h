@@ -65,7 +65,9 @@ const char* cmb_version(void);
  * arguments = 2, round 3's fold_kv workspace = 3, the batch fields of cmb_gemm_desc = 4,
  * the kernel-selection knobs of round 4 = 5, cmb_layernorm_fwd_multi = 9, cmb_ln_multi_desc.dx_out = 10, the workspaces of
  * the deterministic column sums = 11, cmb_decode_attn and its plan / workspace queries = 12,
- * cmb_resample_bilinear_bwd = 13).  Bindings must compare it
+ * cmb_resample_bilinear_bwd = 13).  cmb_resample_accum and its descriptor were ADDED under revision 13: no existing
+ * signature or layout changed, which is the rule for a bump, so a binding written against 13 still calls everything it
+ * knows correctly.  Bindings must compare it
  * with the revision they
  * were written against (CMB_ABI_VERSION; cambrian_amd/lib.py::load raises on a mismatch): every symbol of a stale
  * library still resolves, and a shifted argument list corrupts memory instead of failing. */
@@ -538,6 +540,37 @@ int cmb_resample_bilinear(int dtype, const void* in, int64_t B, int32_t Hi, int3
 int cmb_resample_bilinear_bwd(int dtype, const void* dout, int64_t B, int32_t Ho, int32_t Wo, int64_t C,
                               int64_t ld_dout, int64_t batch_stride_dout, void* din, int32_t Hi, int32_t Wi,
                               int64_t ld_din, int64_t batch_stride_din, void* stream);
+/* Sum of bilinearly resized maps onto a base, bias and activation in one pass (resample_accum.hip):
+ *     pre[b, o, c] = base[b, o, c] (0 if base == NULL) + bias[c] (0 if NULL) + sum_s lerp_s(src_s)[b, o, c],  s in list order
+ *     out[b, o, c] = act(pre),  act = CMB_ACT_NONE | CMB_ACT_GELU_ERF (the GEMM epilogues' own GELU)
+ * over the Ho x Wo output grid, channels-last.  Source s is [B, Hi[s]*Wi[s], C] with row stride ld_src[s] and batch stride
+ * batch_stride_src[s] (elements) and is resized with the arithmetic of cmb_resample_bilinear (align_corners=False, fp32
+ * lerp).  base, pre_out (optional) and out are [B, Ho*Wo, C] with their own row / batch strides, so column slices of wider
+ * buffers work in place.  `dtype` is the element type of out and pre_out, `src_dtype` that of base and the sources: equal,
+ * or CMB_F32 under a CMB_BF16 `dtype` (partial products kept unrounded).  fp32 sum in the stated order, rounded once; no
+ * atomics, bit-reproducible.  n_src <= CMB_RESAMPLE_ACCUM_MAX_SRC (n_src == 0 needs a base); C and every stride % 8 == 0
+ * (CMB_ERR_BAD_ARG), every pointer 16-byte aligned (CMB_ERR_ALIGNMENT); all checks run before any launch.
+ * Use: a linear over channel-concatenated resized maps, with the maps that have fewer positions than the output projected
+ * at their own resolution (src_s = X_s W_s^T); d(src_s) = cmb_resample_bilinear_bwd of d(pre). */
+#define CMB_RESAMPLE_ACCUM_MAX_SRC 4
+typedef struct cmb_resample_accum_desc {
+  int32_t dtype, src_dtype;
+  int32_t act, n_src;
+  int64_t B;
+  int32_t Ho, Wo;
+  int64_t C;
+  const void* base;
+  int64_t ld_base, batch_stride_base;
+  const float* bias;
+  const void* src[CMB_RESAMPLE_ACCUM_MAX_SRC];
+  int32_t Hi[CMB_RESAMPLE_ACCUM_MAX_SRC], Wi[CMB_RESAMPLE_ACCUM_MAX_SRC];
+  int64_t ld_src[CMB_RESAMPLE_ACCUM_MAX_SRC], batch_stride_src[CMB_RESAMPLE_ACCUM_MAX_SRC];
+  void* pre_out;
+  int64_t ld_pre, batch_stride_pre;
+  void* out;
+  int64_t ld_out, batch_stride_out;
+} cmb_resample_accum_desc;
+int cmb_resample_accum(const cmb_resample_accum_desc* d, void* stream);
 /* Elementwise y = act(a) * b (SwiGLU: act = SiLU) / y = act(a); a,b,y [rows, D] with strides. */
 int cmb_act_mul(int dtype, int32_t act, const void* a, int64_t lda, const void* b, int64_t ldb,
                 int64_t rows, int64_t D, void* y, int64_t ldy, void* stream);
