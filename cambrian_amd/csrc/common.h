@@ -86,22 +86,7 @@ extern int g_cmb_knobs[CMB_KNOB_COUNT];
 static inline int cmb_knob(int k) { return g_cmb_knobs[k]; }
 
 // ---- rowmap -------------------------------------------------------------------------------
-struct RowMap {
-  uint32_t n1, n2;
-  int64_t s0, s1, s2;
-};
-static inline RowMap make_rowmap(const cmb_rowmap& m) {
-  RowMap r;
-  r.n1 = (uint32_t)m.n1; r.n2 = (uint32_t)(m.n2 ? m.n2 : 1);
-  r.s0 = m.s0; r.s1 = m.s1; r.s2 = m.s2;
-  return r;
-}
-__host__ __device__ static inline int64_t row_off(const RowMap& m, uint32_t r) {
-  if (m.n1 == 0) return (int64_t)r * m.s2;
-  uint32_t a = r / m.n1, rem = r - a * m.n1;
-  uint32_t b = rem / m.n2, c = rem - b * m.n2;
-  return (int64_t)a * m.s0 + (int64_t)b * m.s1 + (int64_t)c * m.s2;
-}
+#include "rowmap.h"
 
 // ---- 8-element vector load/store with fp32 math ------------------------------------------------
 // A "vec8" is 8 consecutive elements: 16 bytes of bf16 or 32 bytes of fp32.

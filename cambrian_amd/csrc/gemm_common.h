@@ -4,33 +4,9 @@
 #include <type_traits>
 #include "common.h"
 #include "gemm_layout.h"
+#include "gemm_plan.h"   // GemmParams (gemm_params.h) and every host-side dispatch decision
 
 namespace cmb_gemm_detail {
-
-struct GemmParams {
-  int M, N, K;
-  const char* A; RowMap a_map;
-  const char* B; int64_t ldb;
-  char* C; RowMap c_map;
-  const float* bias;
-  const float* colscale;
-  const char* R; RowMap r_map;
-  char* P; RowMap p_map;
-  int act;
-  float alpha, beta;
-  int out_f32;
-  int tiles_m, tiles_n;
-  int k_per_split;
-  float* slabs;
-  const float* a_scale;  // fp8 operands: per-row dequantisation factors (nullptr otherwise)
-  const float* b_scale;
-  int batch;                 // > 1: blockIdx.z walks independent problems of the same shape (128 x 128 kernel only)
-  int64_t a_bs, b_bs, c_bs;  // element strides of A / B / C between consecutive problems of a batch
-  int slab_rows;             // rows of one split-K slab (= M; batch * M for cmb_gemm_tn's batched split-K)
-  const float* row_mean;     // LayerNorm folded into this linear (cmb_gemm_desc.row_mean): v = rstd[m] (acc - mean[m] colsum[n]) + bias[n]
-  const float* row_rstd;
-  const float* col_sum;
-};
 
 // storage tag of an OCP e4m3fn operand byte (gfx950 native fp8)
 struct fp8e4m3_t { uint8_t v; };
@@ -185,17 +161,20 @@ int launch_gemm256_bf16(GemmParams& p, int splits, int sched, hipStream_t s);
 
 // gemm_p5.hip: persistent 256x256 bf16 tile, 4 waves x (128 x 128), 64-deep tiles, the tile's fragments in registers,
 // two LDS buffers (gemm_nt_p5_kernel)
-// q != nullptr: a pair launch — q (same activation, whole K, no slabs) runs beside p on its own share of the workgroups
-int launch_gemm_p5_bf16(GemmParams& p, int splits, hipStream_t s, GemmParams* q = nullptr);
-double gemm_p5_pair_gain(const GemmParams& a, const GemmParams& b, int n_cu);
-bool gemm_p5_pair_act_ok(int act);   // activation templates that have a pair instantiation
+// q != nullptr: a pair launch — q (same activation, whole K, no slabs) runs beside p, which gets the workgroups [0, pair_g0)
+// (gemm_plan.h: gemm_pair_plan)
+int launch_gemm_p5_bf16(GemmParams& p, int splits, hipStream_t s, GemmParams* q = nullptr, int pair_g0 = 0);
+
+// CUs of the current device in whole XCDs (rounded down to a multiple of 8; 256 if the query fails): the one count behind the
+// persistent kernel's grid, the tail split and the pair arithmetic
+int gemm_device_cus();
 
 // gemm_k64.hip: batched problems with a 64-deep contraction and a wide N (the per-head expand products): HBM-write-bound kernel
-bool gemm_k64_eligible(const GemmParams& p);
+// (gemm_plan.h: gemm_k64_eligible)
 int launch_gemm_k64_batched(const GemmParams& p, hipStream_t s);
 
 // gemm_smallm.hip: M <= 32 rows (the SVA layers' per-image context vectors): 32 output columns per workgroup, K split over its waves
-bool gemm_small_m_eligible(const GemmParams& p, int splits);
+// (gemm_plan.h: gemm_small_m_eligible)
 int launch_gemm_small_m(const GemmParams& p, hipStream_t s);
 
 // gemm_tn.hip: C[M,N] = At[K,M]^T Bt[K,N] (both operands row-major over the contraction rows; p.a_map.s2 = lda, p.K = rows),

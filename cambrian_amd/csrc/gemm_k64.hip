@@ -9,7 +9,6 @@
 //   * 128 output columns at a time are staged through 8 KiB of LDS per wave (XOR-swizzled 16-byte slots: conflict-free writes)
 //     and leave as whole 256-byte row segments — 4 rows x 256 B per store instruction, non-temporal.
 // MFMA operand order (B, A) as everywhere in this library: a lane owns an output row.
-#include <cstdlib>
 #include "gemm_common.h"
 
 namespace cmb_gemm_detail {
@@ -65,17 +64,6 @@ __global__ void __launch_bounds__(256) gemm_k64_batched_kernel(const GemmParams 
 }
 
 }  // namespace
-
-// Eligibility (gemm.hip): bf16 in and out, K == 64, N % 128 == 0, batch > 1, plain row maps, plain epilogue.
-bool gemm_k64_eligible(const GemmParams& p) {
-  static int on = -1;   // CMB_GEMM_K64=0: the 128 x 128 tile kernel as before (A/B runs)
-  if (on < 0) {
-    const char* e = getenv("CMB_GEMM_K64");
-    on = (e && atoi(e) == 0) ? 0 : 1;
-  }
-  return on && p.batch > 1 && p.K == 64 && (p.N % 128) == 0 && !p.out_f32 && !p.bias && !p.colscale && !p.R && !p.P && !p.slabs &&
-         p.act == CMB_ACT_NONE && p.a_map.n1 == 0 && p.c_map.n1 == 0 && (p.c_map.s2 % 8) == 0 && (p.c_bs % 8) == 0 && !p.row_mean;
-}
 
 int launch_gemm_k64_batched(const GemmParams& p, hipStream_t s) {
   const dim3 grid((unsigned)((p.M + 127) / 128), (unsigned)p.batch);

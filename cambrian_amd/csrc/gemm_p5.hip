@@ -1,5 +1,5 @@
 // gemm_p5.hip — persistent large-tile configuration of C[M,N] = epilogue(alpha * A[M,K] · B[N,K]^T), bf16, gfx950:
-// gemm_nt_p5_kernel, the default 256 x 256 kernel (gemm.hip::p5_default says where).
+// gemm_nt_p5_kernel, the default 256 x 256 kernel (gemm_plan.h::p5_default says where).
 //
 // Why a second 256 x 256 kernel beside the 8-wave / 8-phase kernel of gemm256.hip: that kernel keeps the matrix pipe 60 %
 // busy — a wave owns 128 x 64 of the tile, so every K-step moves 24 KB of fragments per wave through the LDS, each phase
@@ -19,7 +19,6 @@
 //
 // LDS tile layout (gemm_layout.h): rows of 128 B = 8 chunks of 16 B; chunk c of row r lives at r*128 + ((c ^ gl_swz(r)) << 4);
 // ds_read_b128 fragment reads are conflict-free and the swizzle is applied to the DMA's per-lane SOURCE address.
-#include <cstdlib>
 #include <type_traits>
 #include "gemm_common.h"
 
@@ -207,7 +206,7 @@ struct P5Src {
 // Pair launch (round 6): TWO independent problems with the same activation template in one grid — workgroups [0, g0) run
 // problem 0, the rest problem 1, each side persistent over its own items exactly as a single launch of that many workgroups.
 // DINOv2's and SigLIP's linears at 24 images are 414 / 345 tiles: 1.62 / 1.35 rounds of 256 workgroups, i.e. two rounds each
-// for 2.97 rounds of work; side by side on 138 + 118 workgroups they are 3.0 + 2.9 rounds (gemm.hip: cmb_gemm_pair picks g0).
+// for 2.97 rounds of work; side by side on 138 + 118 workgroups they are 3.0 + 2.9 rounds (gemm_plan.h: gemm_pair_plan picks g0).
 // A workgroup picks its problem ONCE: everything below reads `p` through one reference as before.
 }  // namespace
 struct P5Args {
@@ -413,40 +412,12 @@ __global__ void __launch_bounds__(256) gemm_nt_p5_kernel(const P5Args args) {
 }
 
 #ifndef CMB_P5_PAIR_TU
-// Workgroups of problem 0 in a pair launch: the split g0 in [1, n_cu) that minimises max over the two sides of
-// rounds x (K tiles per item + epilogue), rounds = ceil(items / workgroups) (whole XCD multiples are not needed: a side's items
-// are numbered from its own first workgroup).
-int p5_pair_split(int items0, int k0, int items1, int k1, int n_cu) {
-  const double c0 = k0 / 64.0 + 6.0, c1 = k1 / 64.0 + 6.0;
-  int best = n_cu / 2;
-  double best_t = 1e30;
-  static int step = 0;   // CMB_P5_PAIR_ALIGN (lab): candidate splits in multiples of this (8 keeps item % 8 == block % 8 on both sides)
-  if (!step) {
-    const char* e = getenv("CMB_P5_PAIR_ALIGN");
-    step = e && atoi(e) > 0 ? atoi(e) : 1;
-  }
-  for (int g = 8; g <= n_cu - 8; g += step) {
-    const double t0 = (double)((items0 + g - 1) / g) * c0, t1 = (double)((items1 + (n_cu - g) - 1) / (n_cu - g)) * c1;
-    const double t = t0 > t1 ? t0 : t1;
-    if (t < best_t - 1e-9) best_t = t, best = g;
-  }
-  return best;
-}
-double p5_pair_cost(int items0, int k0, int items1, int k1, int n_cu, bool paired) {
-  const double c0 = k0 / 64.0 + 6.0, c1 = k1 / 64.0 + 6.0;
-  if (!paired) return (double)((items0 + n_cu - 1) / n_cu) * c0 + (double)((items1 + n_cu - 1) / n_cu) * c1;
-  const int g = p5_pair_split(items0, k0, items1, k1, n_cu);
-  const double t0 = (double)((items0 + g - 1) / g) * c0, t1 = (double)((items1 + (n_cu - g) - 1) / (n_cu - g)) * c1;
-  return t0 > t1 ? t0 : t1;
-}
-
 template <int ACT>
-int launch_p5_act(GemmParams& p, int splits, hipStream_t s, GemmParams* q = nullptr) {
+int launch_p5_act(GemmParams& p, int splits, hipStream_t s, GemmParams* q, int pair_g0) {
   constexpr int smem = 2 * kP5Buf + 4 * 8192;  // two operand buffers + the epilogue's staging area = all 160 KiB
   static CmbAttrOnce attr_once;
-  static int n_cu = 0;
   // pair launches exist for the plain and the erf-GELU epilogue templates only (the residual linears of the ViT blocks are
-  // plain; every further instantiation is 35 s of compile time): gemm_p5_pair_act_ok() tells cmb_gemm_pair
+  // plain; every further instantiation is 35 s of compile time): gemm_plan.h's gemm_p5_pair_act_ok() tells cmb_gemm_pair
   constexpr bool kPairAct = ACT == CMB_ACT_NONE || ACT == CMB_ACT_GELU_ERF;
   auto kern = gemm_nt_p5_kernel<ACT, false>;
   if (q && !kPairAct) return CMB_ERR_BAD_ARG;
@@ -455,14 +426,9 @@ int launch_p5_act(GemmParams& p, int splits, hipStream_t s, GemmParams* q = null
             hipSuccess ||
         p5_pair_set_attr(smem) != CMB_OK)
       return CMB_ERR_LAUNCH;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
-      return CMB_ERR_LAUNCH;
-    n_cu -= n_cu % 8;  // whole XCD rounds: item % 8 == block % 8 in every round
-    if (n_cu <= 0) return CMB_ERR_LAUNCH;
     attr_once.done(attr_bit);
   }
+  const int n_cu = gemm_device_cus();
   p.tiles_m = (p.M + 255) / 256;
   p.tiles_n = (p.N + 255) / 256;
   const int n_items = p.tiles_m * p.tiles_n * splits;
@@ -471,16 +437,13 @@ int launch_p5_act(GemmParams& p, int splits, hipStream_t s, GemmParams* q = null
   P5Args args;
   args.prob[0] = p;
   args.n_items[0] = n_items;
-  if (q) {   // pair launch: q on the workgroups [g0, n_cu)
+  if (q) {   // pair launch: p on the workgroups [0, pair_g0), q on [pair_g0, n_cu)
     q->tiles_m = (q->M + 255) / 256;
     q->tiles_n = (q->N + 255) / 256;
     args.prob[1] = *q;
     args.n_items[1] = q->tiles_m * q->tiles_n;
-    g0 = p5_pair_split(n_items, p.K, args.n_items[1], q->K, n_cu);
-    if (const char* e = getenv("CMB_P5_PAIR_G0")) {   // lab: sweep the split
-      const int v = atoi(e);
-      if (v >= 8 && v <= n_cu - 8) g0 = v;
-    }
+    if (pair_g0 < 1 || pair_g0 >= n_cu) return CMB_ERR_BAD_ARG;
+    g0 = pair_g0;
     grid = n_cu;
   } else {
     args.prob[1] = p;
@@ -495,24 +458,15 @@ int launch_p5_act(GemmParams& p, int splits, hipStream_t s, GemmParams* q = null
 
 }  // namespace
 
-int launch_gemm_p5_bf16(GemmParams& p, int splits, hipStream_t s, GemmParams* q) {
+int launch_gemm_p5_bf16(GemmParams& p, int splits, hipStream_t s, GemmParams* q, int pair_g0) {
   switch (p.slabs ? CMB_ACT_NONE : p.act) {
-    case CMB_ACT_GELU_ERF: return launch_p5_act<CMB_ACT_GELU_ERF>(p, splits, s, q);
-    case CMB_ACT_GELU_TANH: return launch_p5_act<CMB_ACT_GELU_TANH>(p, splits, s, q);
-    case CMB_ACT_QUICK_GELU: return launch_p5_act<CMB_ACT_QUICK_GELU>(p, splits, s, q);
-    case CMB_ACT_SILU: return launch_p5_act<CMB_ACT_SILU>(p, splits, s, q);
-    case CMB_ACT_SWIGLU_PAIRS: return launch_p5_act<CMB_ACT_SWIGLU_PAIRS>(p, splits, s, q);
-    default: return launch_p5_act<CMB_ACT_NONE>(p, splits, s, q);
+    case CMB_ACT_GELU_ERF: return launch_p5_act<CMB_ACT_GELU_ERF>(p, splits, s, q, pair_g0);
+    case CMB_ACT_GELU_TANH: return launch_p5_act<CMB_ACT_GELU_TANH>(p, splits, s, q, pair_g0);
+    case CMB_ACT_QUICK_GELU: return launch_p5_act<CMB_ACT_QUICK_GELU>(p, splits, s, q, pair_g0);
+    case CMB_ACT_SILU: return launch_p5_act<CMB_ACT_SILU>(p, splits, s, q, pair_g0);
+    case CMB_ACT_SWIGLU_PAIRS: return launch_p5_act<CMB_ACT_SWIGLU_PAIRS>(p, splits, s, q, pair_g0);
+    default: return launch_p5_act<CMB_ACT_NONE>(p, splits, s, q, pair_g0);
   }
-}
-
-bool gemm_p5_pair_act_ok(int act) { return act == CMB_ACT_NONE || act == CMB_ACT_GELU_ERF; }
-
-// cost model of a pair launch against the two single launches (K tiles + epilogue per item, whole rounds): > 0 = the pair wins
-double gemm_p5_pair_gain(const GemmParams& a, const GemmParams& b, int n_cu) {
-  const int ia = ((a.M + 255) / 256) * ((a.N + 255) / 256), ib = ((b.M + 255) / 256) * ((b.N + 255) / 256);
-  const double single = p5_pair_cost(ia, a.K, ib, b.K, n_cu, false), pair = p5_pair_cost(ia, a.K, ib, b.K, n_cu, true);
-  return (single - pair) / single;
 }
 
 #else   // CMB_P5_PAIR_TU: only the pair instantiations and their two entry points

@@ -66,13 +66,6 @@ __global__ void __launch_bounds__(256) gemm_small_m_kernel(const GemmParams p) {
 
 }  // namespace
 
-// Eligibility (gemm.hip): bf16 operands, M <= 32, one problem, whole K, N % 32 == 0, plain epilogue, no beta.
-bool gemm_small_m_eligible(const GemmParams& p, int splits) {
-  return p.M <= 32 && p.batch == 1 && splits == 1 && !p.slabs && (p.N % 32) == 0 && (p.K % 16) == 0 && !p.bias && !p.colscale && !p.R &&
-         !p.P && p.act == CMB_ACT_NONE && !p.a_scale && !p.b_scale && !p.row_mean && p.beta == 0.0f && p.c_map.n1 == 0 &&
-         (p.c_map.s2 % 4) == 0;
-}
-
 int launch_gemm_small_m(const GemmParams& p, hipStream_t s) {
   hipLaunchKernelGGL(gemm_small_m_kernel, dim3((unsigned)(p.N / 32)), dim3(256), 0, s, p);
   CMB_CHECK_LAUNCH();

@@ -49,6 +49,49 @@ def k_cast(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     return out
 
 
+def _gemm_desc(dt: int, M: int, N: int, K: int, a: torch.Tensor, a_map: RowMap, w: torch.Tensor, ldb: int, out: torch.Tensor,
+               c_map: RowMap, *, bias=None, colscale=None, residual=None, r_map: Optional[RowMap] = None, pre_out=None,
+               act: int = L.ACT_NONE, alpha: float = 1.0, beta: float = 0.0, split_k: int = 1, tile: int = 0, slab_rows: int = 0,
+               batch: Optional[Tuple[int, int, int, int]] = None, scales=None, ln=None):
+    """The ``cmb_gemm_desc`` of every GEMM launcher (the launchers validate, this fills): operands and row maps, the optional
+    bias / colscale / residual (through ``r_map``) / contiguous pre_out, the split-K workspace (``split_k`` slabs of
+    ``slab_rows`` x N fp32), ``batch`` = (count, a / b / c element strides), ``scales`` = fp8 (a_inv, w_inv), ``ln`` = folded
+    LayerNorm (mean, rstd, col_sum).  Returns (descriptor, workspace): the workspace lives as long as the caller holds it."""
+    d = GemmDesc()
+    d.dtype, d.out_dtype = dt, L.dtype_code(out.dtype)
+    d.M, d.N, d.K = M, N, K
+    d.A, d.a_map = a.data_ptr(), a_map
+    d.B, d.ldb = w.data_ptr(), ldb
+    d.C, d.c_map = out.data_ptr(), c_map
+    d.bias, d.colscale = L.ptr(bias), L.ptr(colscale)
+    d.residual, d.r_map = L.ptr(residual), (r_map if residual is not None else L.identity_map(0))
+    d.pre_out, d.p_map = L.ptr(pre_out), L.identity_map(N if pre_out is not None else 0)
+    d.act, d.alpha, d.beta, d.split_k, d.tile_hint = act, alpha, beta, split_k, tile
+    ws = None
+    if split_k > 1:
+        ws = torch.empty((split_k * slab_rows * N,), dtype=torch.float32, device=a.device)
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    else:
+        d.workspace, d.workspace_bytes = None, 0
+    if batch is not None:
+        d.batch, d.a_batch_stride, d.b_batch_stride, d.c_batch_stride = batch
+    if scales is not None:
+        d.a_scale, d.b_scale = scales[0].data_ptr(), scales[1].data_ptr()
+    if ln is not None:
+        d.row_mean, d.row_rstd, d.col_sum = (t.data_ptr() for t in ln)
+    return d, ws
+
+
+def _gemm_launch(fn: str, descs, device, what: str, prof=None, row=None) -> None:
+    """``cmb_<fn>`` on the descriptors; while ``prof`` is a list (GEMM_PROFILE) the launch is bracketed by HIP events on the
+    launch stream (bench.py roofline leg) and one row is appended: (start, end) + ``row(lib)``, read after the launch."""
+    lib = L.load()
+    e0 = _event() if prof is not None else None
+    L.check(getattr(lib, fn)(*[C.byref(d) for d in descs], L.stream_ptr(device)), what)
+    if prof is not None:
+        prof.append((e0, _event()) + row(lib))
+
+
 def k_gemm(a: torch.Tensor, w: torch.Tensor, *, M: Optional[int] = None, a_map: Optional[RowMap] = None,
            bias: Optional[torch.Tensor] = None, act: int = L.ACT_NONE, colscale: Optional[torch.Tensor] = None,
            residual: Optional[torch.Tensor] = None, r_map: Optional[RowMap] = None,
@@ -82,18 +125,9 @@ def k_gemm(a: torch.Tensor, w: torch.Tensor, *, M: Optional[int] = None, a_map: 
         if out.dim() != 2 or out.stride(1) != 1:
             raise L.CambrianAmdError("gemm out must be 2-D row-major unless c_map is given")
         c_map = L.identity_map(out.stride(0))
-    d = GemmDesc()
-    d.dtype = L.dtype_code(dt)
-    d.out_dtype = L.dtype_code(out.dtype)
-    d.M, d.N, d.K = M, N, K
-    d.A, d.a_map = a.data_ptr(), a_map
-    d.B, d.ldb = w.data_ptr(), w.stride(0)
-    d.C, d.c_map = out.data_ptr(), c_map
     for t in (bias, colscale):
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != N):
             raise L.CambrianAmdError("bias / colscale must be contiguous fp32 [N]")
-    d.bias = L.ptr(bias)
-    d.colscale = L.ptr(colscale)
     if residual is not None:
         if residual.dtype != dt:
             raise L.CambrianAmdError("residual dtype must equal the operand dtype")
@@ -101,31 +135,19 @@ def k_gemm(a: torch.Tensor, w: torch.Tensor, *, M: Optional[int] = None, a_map: 
             if residual.dim() != 2 or residual.stride(1) != 1:
                 raise L.CambrianAmdError("residual must be 2-D row-major unless r_map is given")
             r_map = L.identity_map(residual.stride(0))
-        d.residual, d.r_map = residual.data_ptr(), r_map
-    else:
-        d.residual, d.r_map = None, L.identity_map(0)
-    if pre_out is not None:
-        if pre_out.dtype != dt or not pre_out.is_contiguous():
-            raise L.CambrianAmdError("pre_out must be contiguous and of the operand dtype")
-        d.pre_out, d.p_map = pre_out.data_ptr(), L.identity_map(N)
-    else:
-        d.pre_out, d.p_map = None, L.identity_map(0)
-    d.act, d.alpha, d.beta = act, alpha, beta
-    d.split_k = split_k
-    d.tile_hint = tile
+    if pre_out is not None and (pre_out.dtype != dt or not pre_out.is_contiguous()):
+        raise L.CambrianAmdError("pre_out must be contiguous and of the operand dtype")
+    ln = None
     if row_stats is not None:
         mean, rstd = row_stats
         L.require_gpu(mean, rstd, col_sum)
         if (col_sum is None or bias is None or any(t.dtype != torch.float32 or not t.is_contiguous() for t in (mean, rstd, col_sum))
                 or mean.numel() != M or rstd.numel() != M or col_sum.numel() != N):
             raise L.CambrianAmdError("folded LayerNorm: mean / rstd fp32 [M], col_sum fp32 [N] and a bias are required")
-        d.row_mean, d.row_rstd, d.col_sum = mean.data_ptr(), rstd.data_ptr(), col_sum.data_ptr()
-    ws = None
-    if split_k > 1:
-        ws = torch.empty((split_k * M * N,), dtype=torch.float32, device=a.device)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-    else:
-        d.workspace, d.workspace_bytes = None, 0
+        ln = (mean, rstd, col_sum)
+    d, ws = _gemm_desc(L.dtype_code(dt), M, N, K, a, a_map, w, w.stride(0), out, c_map, bias=bias, colscale=colscale,
+                       residual=residual, r_map=r_map, pre_out=pre_out, act=act, alpha=alpha, beta=beta, split_k=split_k, tile=tile,
+                       slab_rows=M, ln=ln)
     if GEMM_CENSUS is not None and dt == torch.bfloat16 and split_k <= 1 and tile == 0:
         key = (M, N, K, act, pre_out is not None)
         GEMM_CENSUS[key] = GEMM_CENSUS.get(key, 0) + 1
@@ -134,20 +156,13 @@ def k_gemm(a: torch.Tensor, w: torch.Tensor, *, M: Optional[int] = None, a_map: 
         return out
     prof = GEMM_PROFILE
     tile_used = 0
-    if prof is not None:  # HIP events on the launch stream around this launch (bench.py roofline leg)
+    if prof is not None:
         tile_used = L.load().cmb_gemm_tile(d.dtype, M, N, split_k, tile)
         if GEMM_PROFILE_TILE and tile_used != GEMM_PROFILE_TILE:
             prof = None  # only the dominant kernel is timed: every event pair costs the stream a barrier packet
-    if prof is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = L.load().cmb_gemm(C.byref(d), L.stream_ptr(a.device))
-    L.check(rc, f"cmb_gemm(M={M},N={N},K={K},{dt})")
-    if prof is not None:
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        prof.append((e0, e1, 2.0 * M * N * K, dt, split_k, tile_used, (M, N, K, act, out.dtype == torch.float32),
-                     L.load().cmb_gemm_last_kernel()))
+    _gemm_launch("cmb_gemm", (d,), a.device, f"cmb_gemm(M={M},N={N},K={K},{dt})", prof,
+                 lambda lib: (2.0 * M * N * K, dt, split_k, tile_used, (M, N, K, act, out.dtype == torch.float32),
+                              lib.cmb_gemm_last_kernel()))
     return out
 
 
@@ -159,23 +174,12 @@ def k_gemm_pair(kw0: dict, kw1: dict) -> Tuple[torch.Tensor, torch.Tensor]:
     k_gemm(_collect=col, **kw0)
     k_gemm(_collect=col, **kw1)
     (d0, o0, _k0, m0), (d1, o1, _k1, m1) = col
-    prof = GEMM_PROFILE
-    if prof is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-    lib = L.load()
-    rc = lib.cmb_gemm_pair(C.byref(d0), C.byref(d1), L.stream_ptr(o0.device))
-    L.check(rc, f"cmb_gemm_pair({m0[:3]}, {m1[:3]})")
-    if prof is not None:
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        paired = bool(lib.cmb_gemm_pair_last())
-        # one row for the call: the FLOPs of both problems over the span of the launch (or of the two launches)
-        prof.append((e0, e1, 2.0 * (m0[0] * m0[1] * m0[2] + m1[0] * m1[1] * m1[2]), m0[4], 1, 256,
-                     (m0[0], m0[1], m0[2], m0[3], False), lib.cmb_gemm_last_kernel(),
-                     ("pair:" if paired else "seq:") + f"{m1[0]}x{m1[1]}x{m1[2]}"))
+    # one profile row for the call: the FLOPs of both problems over the span of the launch (or of the two launches)
+    _gemm_launch("cmb_gemm_pair", (d0, d1), o0.device, f"cmb_gemm_pair({m0[:3]}, {m1[:3]})", GEMM_PROFILE,
+                 lambda lib: (2.0 * (m0[0] * m0[1] * m0[2] + m1[0] * m1[1] * m1[2]), m0[4], 1, 256,
+                              (m0[0], m0[1], m0[2], m0[3], False), lib.cmb_gemm_last_kernel(),
+                              ("pair:" if lib.cmb_gemm_pair_last() else "seq:") + f"{m1[0]}x{m1[1]}x{m1[2]}"))
     return o0, o1
-
 
 
 def k_quantize_fp8_rows(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -205,30 +209,15 @@ def k_gemm_fp8(a_q: torch.Tensor, a_inv: torch.Tensor, w_q: torch.Tensor, w_inv:
     if a_q.dtype != torch.uint8 or w_q.dtype != torch.uint8 or w_q.shape[1] != K or not (a_q.is_contiguous() and w_q.is_contiguous()):
         raise L.CambrianAmdError("fp8 gemm operands must be contiguous uint8 [M,K] / [N,K]")
     out = torch.empty((M, N), dtype=out_dtype, device=a_q.device)
-    d = GemmDesc()
-    d.dtype, d.out_dtype = L.FP8_E4M3, L.dtype_code(out_dtype)
-    d.M, d.N, d.K = M, N, K
-    d.A, d.a_map = a_q.data_ptr(), L.identity_map(K)
-    d.B, d.ldb = w_q.data_ptr(), K
-    d.C, d.c_map = out.data_ptr(), L.identity_map(N)
-    d.bias, d.colscale = L.ptr(bias), L.ptr(colscale)
     if residual is not None:
         if residual.dtype != torch.bfloat16:
             raise L.CambrianAmdError("fp8 gemm residual must be bf16")
-        d.residual, d.r_map = residual.data_ptr(), (r_map or L.identity_map(residual.stride(0)))
-    else:
-        d.residual, d.r_map = None, L.identity_map(0)
-    if pre_out is not None:
-        if pre_out.dtype != torch.bfloat16 or not pre_out.is_contiguous():
-            raise L.CambrianAmdError("fp8 gemm pre_out must be contiguous bf16")
-        d.pre_out, d.p_map = pre_out.data_ptr(), L.identity_map(N)
-    else:
-        d.pre_out, d.p_map = None, L.identity_map(0)
-    d.act, d.alpha, d.beta, d.split_k, d.tile_hint = act, 1.0, 0.0, 1, 0
-    d.workspace, d.workspace_bytes = None, 0
-    d.a_scale, d.b_scale = a_inv.data_ptr(), w_inv.data_ptr()
-    rc = L.load().cmb_gemm(C.byref(d), L.stream_ptr(a_q.device))
-    L.check(rc, f"cmb_gemm(fp8, M={M},N={N},K={K})")
+        r_map = r_map or L.identity_map(residual.stride(0))
+    if pre_out is not None and (pre_out.dtype != torch.bfloat16 or not pre_out.is_contiguous()):
+        raise L.CambrianAmdError("fp8 gemm pre_out must be contiguous bf16")
+    d, _ = _gemm_desc(L.FP8_E4M3, M, N, K, a_q, L.identity_map(K), w_q, K, out, L.identity_map(N), bias=bias, colscale=colscale,
+                      residual=residual, r_map=r_map, pre_out=pre_out, act=act, scales=(a_inv, w_inv))
+    _gemm_launch("cmb_gemm", (d,), a_q.device, f"cmb_gemm(fp8, M={M},N={N},K={K})")   # (no GEMM_PROFILE row: bf16 / fp32 rooflines only)
     return out
 
 
@@ -314,7 +303,7 @@ class gemm_census:
             if pre or N % 128 or K < 128 or K % 64 or tiles < min_tiles:
                 continue
             if L.load().cmb_gemm_tail_rows(M, N):
-                continue   # launched as 256-tile head + 128-tile tail (gemm.hip "Tail split"): the policy does not apply
+                continue   # launched as 256-tile head + 128-tile tail (gemm_plan.h "tail split"): the policy does not apply
             rows.append((2.0 * M * N * K * cnt, (M, N, K, act)))
         rows.sort(reverse=True)
         return [r[1] for r in rows[:n]]
@@ -454,30 +443,14 @@ def k_gemm_tn(at: torch.Tensor, bt: torch.Tensor, *, out: Optional[torch.Tensor]
         if batch > 1:
             raise L.CambrianAmdError("gemm_tn: a batched launch needs the caller's output tensor")
         out = torch.empty((M, N), dtype=out_dtype, device=at.device)
-    d = GemmDesc()
-    d.dtype, d.out_dtype = L.dtype_code(at.dtype), L.dtype_code(out.dtype)
-    d.M, d.N, d.K = M, N, K
-    d.A, d.a_map = at.data_ptr(), L.identity_map(at.stride(0))
-    d.B, d.ldb = bt.data_ptr(), bt.stride(0)
-    d.C, d.c_map = out.data_ptr(), L.identity_map(ldc if ldc is not None else out.stride(0))
-    d.bias = d.colscale = d.residual = d.pre_out = None
-    d.r_map = d.p_map = L.identity_map(0)
-    d.act, d.alpha, d.beta, d.split_k, d.tile_hint = L.ACT_NONE, alpha, beta, split_k, 0
-    ws = None
-    if split_k > 1:
-        ws = torch.empty((split_k * max(batch, 1) * M * N,), dtype=torch.float32, device=at.device)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-    else:
-        d.workspace, d.workspace_bytes = None, 0
-    d.batch, d.a_batch_stride, d.b_batch_stride, d.c_batch_stride = batch, a_bs, b_bs, c_bs
-    prof = GEMM_PROFILE if not GEMM_PROFILE_TILE else None   # (the timed region times the dominant kernel only)
-    if prof is not None:
-        e0 = _event()
-    rc = L.load().cmb_gemm_tn(C.byref(d), L.stream_ptr(at.device))
-    L.check(rc, f"cmb_gemm_tn(M={M}, N={N}, K={K}, batch={batch})")
-    if prof is not None:   # the span covers the split-K reduce the library launches behind the kernel
-        prof.append((e0, _event(), 2.0 * max(batch, 1) * M * N * K, at.dtype, split_k, 128,
-                     (M, N, K, L.ACT_NONE, out.dtype == torch.float32), KERNEL_ID_TN, max(batch, 1)))
+    d, ws = _gemm_desc(L.dtype_code(at.dtype), M, N, K, at, L.identity_map(at.stride(0)), bt, bt.stride(0), out,
+                       L.identity_map(ldc if ldc is not None else out.stride(0)), alpha=alpha, beta=beta, split_k=split_k,
+                       slab_rows=max(batch, 1) * M, batch=(batch, a_bs, b_bs, c_bs))
+    # (the timed region times the dominant kernel only; the span covers the split-K reduce the library launches behind the kernel)
+    _gemm_launch("cmb_gemm_tn", (d,), at.device, f"cmb_gemm_tn(M={M}, N={N}, K={K}, batch={batch})",
+                 GEMM_PROFILE if not GEMM_PROFILE_TILE else None,
+                 lambda lib: (2.0 * max(batch, 1) * M * N * K, at.dtype, split_k, 128, (M, N, K, L.ACT_NONE, out.dtype == torch.float32),
+                              KERNEL_ID_TN, max(batch, 1)))
     return out
 
 
@@ -1282,31 +1255,17 @@ def k_gemm_batched(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, batch
     L.require_gpu(a, w, out)
     if a.dtype != w.dtype:
         raise L.CambrianAmdError("batched gemm operand dtypes differ")
-    d = GemmDesc()
-    d.dtype, d.out_dtype = L.dtype_code(a.dtype), L.dtype_code(out.dtype)
-    d.M, d.N, d.K = M, N, K
-    d.A, d.a_map = a.data_ptr(), L.identity_map(lda)
-    d.B, d.ldb = w.data_ptr(), ldb
-    d.C, d.c_map = out.data_ptr(), L.identity_map(ldc)
-    d.bias = d.colscale = d.residual = d.pre_out = None
-    d.r_map = d.p_map = L.identity_map(0)
     if residual is not None:   # laid out as ``out`` (row stride ldc, batch stride c_bs), the operands' dtype
         L.require_gpu(residual)
         if residual.dtype != a.dtype or out.dtype != a.dtype or residual.stride(-1) != 1 or residual.stride(0) != ldc \
                 or residual.data_ptr() % 16:
             raise L.CambrianAmdError("batched gemm residual must have the operands' dtype and the output's layout")
-        d.residual, d.r_map = residual.data_ptr(), L.identity_map(ldc)
-    d.act, d.alpha, d.beta, d.split_k, d.tile_hint = L.ACT_NONE, 1.0, 0.0, 1, 0
-    d.workspace, d.workspace_bytes = None, 0
-    d.batch, d.a_batch_stride, d.b_batch_stride, d.c_batch_stride = batch, a_bs, b_bs, c_bs
-    prof = GEMM_PROFILE if not GEMM_PROFILE_TILE else None
-    if prof is not None:
-        e0 = _event()
-    rc = L.load().cmb_gemm(C.byref(d), L.stream_ptr(a.device))
-    L.check(rc, f"cmb_gemm(batch={batch}, M={M}, N={N}, K={K})")
-    if prof is not None:
-        prof.append((e0, _event(), 2.0 * batch * M * N * K, a.dtype, 1, 128, (M, N, K, L.ACT_NONE, out.dtype == torch.float32),
-                     L.load().cmb_gemm_last_kernel(), batch))
+    d, _ = _gemm_desc(L.dtype_code(a.dtype), M, N, K, a, L.identity_map(lda), w, ldb, out, L.identity_map(ldc), residual=residual,
+                      r_map=L.identity_map(ldc), batch=(batch, a_bs, b_bs, c_bs))
+    _gemm_launch("cmb_gemm", (d,), a.device, f"cmb_gemm(batch={batch}, M={M}, N={N}, K={K})",
+                 GEMM_PROFILE if not GEMM_PROFILE_TILE else None,
+                 lambda lib: (2.0 * batch * M * N * K, a.dtype, 1, 128, (M, N, K, L.ACT_NONE, out.dtype == torch.float32),
+                              lib.cmb_gemm_last_kernel(), batch))
     return out
 
 

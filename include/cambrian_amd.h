@@ -121,7 +121,8 @@ int cmb_knob_get(int32_t knob);                  /* -1 for an unknown knob */
  * dtype CMB_FP8_E4M3: v_mfma_f32_32x32x64_f8f6f4 (K = 64 per instruction, twice the bf16 MFMA rate), 128x128 tile,
  *   no split-K; see a_scale / b_scale.
  * two tile configurations: 128x128 / 4 waves, and for bf16 256x256 / 8 waves with the
- *   8-phase LDS-DMA schedule; `tile_hint` = 0 lets the library pick by grid fill.
+ *   8-phase LDS-DMA schedule or the persistent 4-wave kernel; `tile_hint` = 0 lets the library pick (grid-fill cost model,
+ *   per-shape policy, tail split: cambrian_amd/csrc/gemm_plan.h holds every rule).
  * split_k > 1: fp32 partial slabs go to `workspace` (split_k*M*N*4 bytes) and are reduced by a
  *   second kernel; only alpha/beta and out_dtype apply (used for weight gradients).
  * ---------------------------------------------------------------------------------------- */
@@ -142,8 +143,10 @@ typedef struct cmb_gemm_desc {
   void* workspace; int64_t workspace_bytes;
   int32_t tile_hint;       /* 0 = choose by grid-fill cost model; 128 / 256 = force that block tile (bf16 only);
                               2560 / 2561 = 256 tile with schedule 0 (8-phase ping-pong, default) / 1 (in-wave pipeline);
-                              2590 = 4-wave register-buffered 256x256 kernel (what 0 / 256 pick when N % 256 == 0 and there is
-                              more than one round of tiles).  0 also consults the per-shape policy (cmb_gemm_policy_set) */
+                              2590 = 4-wave register-buffered 256x256 kernel (what 0 / 256 pick when N % 128 == 0, there is no
+                              pre_out, the launch has at least 64 tiles and every K slice holds two 64-deep tiles; K slices
+                              shorter than that run on the 8-wave kernel even under 2590).  0 also consults the per-shape policy
+                              (cmb_gemm_policy_set), and only 0 allows the M <= 32 kernel and the tail split */
   const float* a_scale;    /* CMB_FP8_E4M3 only: [M] fp32 dequantisation factor of each A row (or NULL = 1) */
   const float* b_scale;    /* CMB_FP8_E4M3 only: [N] fp32 dequantisation factor of each B row (or NULL = 1);
                               the accumulator is multiplied by a_scale[m] * b_scale[n] before alpha / bias */
@@ -201,11 +204,13 @@ int cmb_gemm_tile(int dtype, int64_t M, int64_t N, int32_t split_k, int32_t tile
 int cmb_gemm_last_kernel(void);
 /* Per-shape dispatch policy: bf16 launches of exactly (M, N, K, act) without a tile_hint and without split-K take
  * `kernel` (128 | 2560 = 8-wave 256x256 | 2590 = 4-wave 256x256; 0 removes the entry) instead of the built-in cost
- * model.  Meant for a start-up calibration on the device at hand (the candidates give bit-identical results; which is
+ * model (a 256-tile entry still yields to the checks of the kernel it names: row strides beyond the 32-bit tile span run on
+ * the 128 tile, K < 128 on the 8-wave kernel; problems that take the M <= 32 kernel or the tail split never reach the policy).  Meant for a
+ * start-up calibration on the device at hand (the candidates give bit-identical results; which is
  * faster for a shape varies from box to box — VERDICT r2 #4).  At most 64 entries (CMB_ERR_WORKSPACE beyond); not
  * thread-safe against concurrent cmb_gemm calls: set it between steps. */
 int cmb_gemm_policy_set(int64_t M, int64_t N, int64_t K, int32_t act, int32_t kernel);
-/* Tail split of bf16 launches without tile_hint / split-K (gemm.hip "Tail split"): when an M x N problem's 256 x 256 tile
+/* Tail split of bf16 launches without tile_hint / split-K (gemm_plan.h "tail split"): when an M x N problem's 256 x 256 tile
  * count is a little more than a whole number of rounds of the device's CUs, rows [0, m1) run on the 256-tile kernel and
  * rows [m1, M) on the 128 x 128 kernel, two launches inside one cmb_gemm call.  Returns m1 (0 = launched whole).
  * CMB_GEMM_NO_TAIL_SPLIT=1 in the environment disables it (A/B runs). */
