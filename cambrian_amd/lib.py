@@ -150,6 +150,14 @@ class PrepJob(C.Structure):
     ]
 
 
+class OptimJob(C.Structure):
+    """cmb_optim_job (include/cambrian_amd.h): one tensor of a cmb_grad_sqnorm / cmb_adamw_step launch."""
+    _fields_ = [
+        ("grad", C.c_void_p), ("param", C.c_void_p), ("low", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+        ("n", C.c_int64), ("chunk0", C.c_int64), ("grad_dtype", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 RESAMPLE_ACCUM_MAX_SRC = 4
 
 
@@ -227,6 +235,10 @@ SIGNATURES = {
     "cmb_resample_bilinear": (C.c_int, [C.c_int, _p, _i64, _i32, _i32, _i64, _i64, _i64, _p, _i32, _i32, _i64, _i64, _p]),
     "cmb_resample_bilinear_bwd": (C.c_int, [C.c_int, _p, _i64, _i32, _i32, _i64, _i64, _i64, _p, _i32, _i32, _i64, _i64, _p]),
     "cmb_resample_accum": (C.c_int, [C.POINTER(ResampleAccumDesc), _p]),
+    "cmb_optim_chunks": (_i64, [_i64]),
+    "cmb_grad_sqnorm_workspace": (_i64, [_i64]),
+    "cmb_grad_sqnorm": (C.c_int, [_p, _i64, _i64, _p, _i64, _p, _p]),
+    "cmb_adamw_step": (C.c_int, [_p, _i64, _i64, _f, _f, _f, _f, _f, _f, _f, _f, _p, _f, _p]),
     "cmb_act_mul": (C.c_int, [C.c_int, _i32, _p, _i64, _p, _i64, _i64, _i64, _p, _i64, _p]),
     "cmb_act_bwd": (C.c_int, [C.c_int, _i32, _p, _p, _i64, _p, _p]),
     "cmb_bcast_rows": (C.c_int, [C.c_int, _p, _i64, _i64, _i64, _p, _p]),

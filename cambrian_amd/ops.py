@@ -2141,6 +2141,109 @@ def decode_attention_enabled() -> bool:
 
 
 # ================================================================================================
+# optimizer: global gradient norm and the one-pass AdamW step (optim.hip) over lists of tensors
+# ================================================================================================
+# Both kernels read a job table in device memory, one job per tensor.  The table is cached on a signature of every pointer
+# in it and uploaded again only when one moves (gradients freed by zero_grad() usually come back at the same addresses from
+# the caching allocator); the upload goes through a pinned host copy and does not block, so a step never waits for the
+# device.  The partials of the norm live in one workspace per device, grown on demand and reused.
+OPTIM_CHUNK = 65536        # CMB_OPTIM_CHUNK of csrc/optim_core.h (tests/test_optim_host.py checks it against cmb_optim_chunks)
+_OPTIM_TABLES: dict = {}   # signature -> (device table, its pinned host copy, n_jobs, total_chunks)
+_OPTIM_WS: dict = {}       # device -> fp32 workspace of the chunk partials
+
+
+def _optim_check(name: str, t: torch.Tensor, numel: int, dev: torch.device, dtypes) -> None:
+    if t.device != dev or t.numel() != numel or t.dtype not in dtypes or not t.is_contiguous():
+        raise L.CambrianAmdError(f"optimizer kernels: {name} must be a contiguous {' / '.join(str(d) for d in dtypes)} tensor "
+                                 f"of {numel} elements on {dev}; got {tuple(t.shape)} {t.dtype} on {t.device}"
+                                 f"{'' if t.is_contiguous() else ', not contiguous'}")
+
+
+def _optim_table(grads, params=None, lows=None, exp_avgs=None, exp_avg_sqs=None):
+    """(device job table, n_jobs, total_chunks) of a list of tensors; every tensor is validated here, since the library cannot
+    look into a table that lives in device memory."""
+    n = len(grads)
+    dev = grads[0].device
+    rows = []
+    for i, g in enumerate(grads):
+        _optim_check("a gradient", g, g.numel(), dev, (torch.float32, torch.bfloat16))
+        p = m = v = low = None
+        if params is not None:
+            p, m, v = params[i], exp_avgs[i], exp_avg_sqs[i]
+            low = lows[i] if lows is not None else None
+            _optim_check("a parameter / master", p, g.numel(), dev, (torch.float32,))
+            _optim_check("exp_avg", m, g.numel(), dev, (torch.float32,))
+            _optim_check("exp_avg_sq", v, g.numel(), dev, (torch.float32,))
+            if low is not None:
+                _optim_check("the low-precision copy", low, g.numel(), dev, (torch.bfloat16,))
+        rows.append((g.data_ptr(), L.ptr(p) or 0, L.ptr(low) or 0, L.ptr(m) or 0, L.ptr(v) or 0, g.numel(), L.dtype_code(g.dtype)))
+    sig = (dev, tuple(rows))
+    hit = _OPTIM_TABLES.get(sig)
+    if hit is None:
+        lib = L.load()
+        jobs = (L.OptimJob * n)()
+        chunk0 = 0
+        for i, (gp, pp, lp, mp, vp, numel, code) in enumerate(rows):
+            j = jobs[i]
+            j.grad, j.param, j.low, j.exp_avg, j.exp_avg_sq = gp, pp or None, lp or None, mp or None, vp or None
+            j.n, j.chunk0, j.grad_dtype, j.reserved = numel, chunk0, code, 0
+            chunk0 += lib.cmb_optim_chunks(numel)
+        host = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).pin_memory()
+        if len(_OPTIM_TABLES) >= 64:   # pointers that keep moving: do not collect stale tables without bound
+            _OPTIM_TABLES.clear()
+        hit = _OPTIM_TABLES[sig] = (host.to(dev, non_blocking=True), host, n, chunk0)
+    return hit[0], hit[2], hit[3]
+
+
+def grad_sqnorm(grads: Sequence[torch.Tensor]) -> torch.Tensor:
+    """Sum of squares of every element of ``grads`` (fp32 / bf16 tensors on one device, any sizes, views at any element
+    offset) as an fp32 device scalar: the square of the global L2 norm ``torch.nn.utils.clip_grad_norm_`` clips by.  The
+    same bits on every run and for every placement of the same values; the host does not wait for it."""
+    grads = list(grads)
+    if not grads:
+        raise L.CambrianAmdError("grad_sqnorm: an empty list has no device to put the result on")
+    L.require_gpu(*grads)
+    grads = [g if g.is_contiguous() else g.contiguous() for g in grads]
+    table, n, chunks = _optim_table(grads)
+    dev = grads[0].device
+    lib = L.load()
+    need = int(lib.cmb_grad_sqnorm_workspace(chunks))
+    ws = _OPTIM_WS.get(dev)
+    if ws is None or ws.numel() < max(need, 1):
+        ws = _OPTIM_WS[dev] = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    L.check(lib.cmb_grad_sqnorm(table.data_ptr(), n, chunks, ws.data_ptr(), ws.numel(), out.data_ptr(), L.stream_ptr(dev)),
+            "cmb_grad_sqnorm")
+    return out
+
+
+def adamw_step(grads: Sequence[torch.Tensor], params: Sequence[torch.Tensor], exp_avgs: Sequence[torch.Tensor],
+               exp_avg_sqs: Sequence[torch.Tensor], lows: Optional[Sequence[Optional[torch.Tensor]]] = None, *, lr: float,
+               beta1: float, beta2: float, eps: float, weight_decay: float, step: int, grad_scale: float = 1.0,
+               sumsq: Optional[torch.Tensor] = None, max_norm: float = 0.0) -> None:
+    """One launch of torch.optim.AdamW's update, in place, over a list of tensors that share their hyper-parameters and
+    their step count ``step`` (>= 1, the count INCLUDING this step).  ``params`` / moments fp32, ``grads`` fp32 or bf16,
+    ``lows[i]``: the bf16 compute copy of ``params[i]`` to refresh in the same pass, or None.  The gradient enters as
+    ``g * grad_scale * coef`` with ``coef = min(1, max_norm / (grad_scale * sqrt(sumsq) + 1e-6))`` when ``sumsq`` (the fp32
+    device scalar of ``grad_sqnorm``) is given and ``max_norm`` > 0, else 1; ``sumsq`` is read on the device."""
+    grads, params, exp_avgs, exp_avg_sqs = list(grads), list(params), list(exp_avgs), list(exp_avg_sqs)
+    if not (len(grads) == len(params) == len(exp_avgs) == len(exp_avg_sqs)) or (lows is not None and len(lows) != len(grads)):
+        raise L.CambrianAmdError("adamw_step: the lists differ in length")
+    if step < 1:
+        raise L.CambrianAmdError("adamw_step: step counts from 1")
+    if not grads:
+        return
+    L.require_gpu(*grads, *params, *exp_avgs, *exp_avg_sqs, *(lows or ()), sumsq)
+    if sumsq is not None and (sumsq.dtype != torch.float32 or sumsq.numel() != 1 or sumsq.device != grads[0].device):
+        raise L.CambrianAmdError("adamw_step: sumsq is the fp32 device scalar of grad_sqnorm")
+    table, n, chunks = _optim_table(grads, params, lows, exp_avgs, exp_avg_sqs)
+    dev = grads[0].device
+    rc = L.load().cmb_adamw_step(table.data_ptr(), n, chunks, lr, beta1, beta2, eps, weight_decay, 1.0 - beta1 ** step,
+                                 1.0 - beta2 ** step, grad_scale, L.ptr(sumsq), max_norm, L.stream_ptr(dev))
+    L.check(rc, "cmb_adamw_step")
+
+
+# ================================================================================================
 # bilinear token-grid resample that back-propagates on our own kernels (elementwise.hip: resample_kernel and its adjoint
 # resample_bwd_kernel) — the trainable towers' 27^2 -> 24^2 / multi-stage -> 96^2 resize and the S5 query-group resize
 # ================================================================================================

@@ -8,7 +8,8 @@ every bucket.  Per step
     accumulate, as ``--gradient_accumulation_steps`` of the reference launch scripts needs); on the LAST micro-batch of
     a step — every backward outside ``no_sync()`` — the arrival of a bucket's last gradient launches an async
     ``reduce_scatter`` (RCCL's own stream) that delivers the SUM of the owned shard and overlaps the rest of backward;
-  * ``step()``: waits, turns sums into means, runs AdamW (torch's fused multi-tensor kernel) on the owned shards only —
+  * ``step()``: waits, turns sums into means (clipped to ``max_grad_norm`` in the same multiplication, if set), runs
+    AdamW (torch's fused multi-tensor kernel) on the owned shards only —
     exp_avg / exp_avg_sq exist for 1/world of the parameters — and ``all_gather``s the updated shards straight into the
     flat parameter buckets, of which the module's parameters are views (no copy back).
 With world == 1 it degenerates to AdamW over flat buckets.  CPU coverage: tests/test_zero.py (gloo, world_size 2) checks
@@ -58,11 +59,21 @@ class Zero2AdamW:
 
     def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, bucket_mb: float = 64.0, process_group: Optional[dist.ProcessGroup] = None,
-                 master_dtype: Optional[torch.dtype] = torch.float32):
+                 master_dtype: Optional[torch.dtype] = torch.float32, max_grad_norm: Optional[float] = None):
         """``master_dtype``: parameters of a narrower floating type (a bf16 decoder in the finetune stage) get an fp32 master
         copy of the owned shard, fp32 AdamW moments and a cast back per step — 16 B per parameter / world, the accounting of
         BASELINE configs[3] / [4]; ``None`` steps in the parameter's own dtype (the round-4 behaviour: at lr 4e-5 most
-        updates of a bf16 parameter vanish below its ulp, tests/test_master_weights.py)."""
+        updates of a bf16 parameter vanish below its ulp, tests/test_master_weights.py).
+
+        ``max_grad_norm``: global L2 clip of the rank-averaged gradient before the step, the reference's inherited
+        ``transformers`` default of 1.0 (train_fsdp.py:122); ``None`` (the default) clips nothing and leaves the step as it
+        was.  Every rank holds 1 / world of the gradient, so the sum of squares of the owned shards is all-reduced (one
+        scalar) and the coefficient rides in the multiplication that turns sums into means; ``last_grad_norm`` is the norm
+        before clipping, a scalar tensor on the shards' device."""
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"Zero2AdamW: max_grad_norm must be positive or None, got {max_grad_norm}")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.last_grad_norm: Optional[torch.Tensor] = None
         self.group = process_group
         on = dist.is_initialized()
         self.world = dist.get_world_size(process_group) if on else 1
@@ -149,8 +160,14 @@ class Zero2AdamW:
             if b.work is not None:
                 b.work.wait()
                 b.work = None
-            g = b.grad_shard if self.world == 1 else b.grad_shard.div_(self.world)
-            s.grad = g if b.master_shard is None else g.to(b.master_shard.dtype)
+            if self.max_grad_norm is None:
+                g = b.grad_shard if self.world == 1 else b.grad_shard.div_(self.world)
+                s.grad = g if b.master_shard is None else g.to(b.master_shard.dtype)
+        if self.max_grad_norm is not None:
+            scale = self._clip_scale()   # coef / world: the sums become clipped means in one multiplication
+            for b, s in zip(self.buckets, self._shards):
+                g = b.grad_shard.mul_(scale)
+                s.grad = g if b.master_shard is None else g.to(b.master_shard.dtype)
         self.inner.step()
         for b, s in zip(self.buckets, self._shards):
             if b.master_shard is not None:
@@ -163,6 +180,27 @@ class Zero2AdamW:
             b.pending = len(b.params)
         for w in gathers:
             w.wait()
+
+    def _clip_scale(self) -> torch.Tensor:
+        """coef / world as a scalar tensor, coef = min(1, max_grad_norm / (norm + 1e-6)) as torch.nn.utils.clip_grad_norm_ forms
+        it, norm = the L2 norm of the rank-averaged gradient; called once every reduce-scatter of the step has been waited for.
+        The shards hold SUMS over ranks and the padding of a bucket is zero, so norm = sqrt(sum over ranks and buckets of
+        |grad_shard|^2) / world.  GPU shards: one cmb_grad_sqnorm launch over all of them (fp32, no host read); the CPU /
+        gloo test path sums in fp64 with torch."""
+        shards = [b.grad_shard for b in self.buckets]
+        if shards and shards[0].is_cuda:
+            from .. import ops
+            sq = ops.grad_sqnorm(shards)
+        else:
+            sq = torch.zeros((), dtype=torch.float64)
+            for g in shards:
+                sq += g.double().pow(2).sum()
+        if self.world > 1:
+            dist.all_reduce(sq, op=dist.ReduceOp.SUM, group=self.group)
+        norm = sq.sqrt() / self.world
+        self.last_grad_norm = norm
+        coef = torch.clamp(self.max_grad_norm / (norm + 1e-6), max=1.0)
+        return (coef / self.world).to(torch.float32)
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         """Drops this step's gradients INCLUDING what the hooks already accumulated / launched: after a skipped step

@@ -65,7 +65,8 @@ const char* cmb_version(void);
  * arguments = 2, round 3's fold_kv workspace = 3, the batch fields of cmb_gemm_desc = 4,
  * the kernel-selection knobs of round 4 = 5, cmb_layernorm_fwd_multi = 9, cmb_ln_multi_desc.dx_out = 10, the workspaces of
  * the deterministic column sums = 11, cmb_decode_attn and its plan / workspace queries = 12,
- * cmb_resample_bilinear_bwd = 13).  cmb_resample_accum and its descriptor were ADDED under revision 13: no existing
+ * cmb_resample_bilinear_bwd = 13).  cmb_resample_accum and its descriptor, and later the optimizer entry points
+ * (cmb_optim_chunks, cmb_grad_sqnorm, cmb_grad_sqnorm_workspace, cmb_adamw_step) were ADDED under revision 13: no existing
  * signature or layout changed, which is the rule for a bump, so a binding written against 13 still calls everything it
  * knows correctly.  Bindings must compare it
  * with the revision they
@@ -576,6 +577,55 @@ typedef struct cmb_resample_accum_desc {
   int64_t ld_out, batch_stride_out;
 } cmb_resample_accum_desc;
 int cmb_resample_accum(const cmb_resample_accum_desc* d, void* stream);
+/* ------------------------------------------------------------------------------------------
+ * Optimizer: global gradient norm and a one-pass AdamW step (csrc/optim.hip, arithmetic in csrc/optim_core.h).
+ * Replaces transformers.Trainer's clip_grad_norm_ + optimizer.step() that the reference inherits (train_fsdp.py:122
+ * derives TrainingArguments from transformers', no script under scripts/cambrian passes --max_grad_norm, so every recipe clips
+ * at the default 1.0) and the up-cast / torch AdamW / cast-back passes of train/master.py.
+ *
+ * Both entry points take a table of jobs in DEVICE memory, one job per tensor.  Every pointer is element-aligned only
+ * (gradients are views into flat buckets): a job whose pointers are all 16-byte aligned is moved with 16-byte accesses,
+ * any other job element by element; any n >= 0 is legal.  A tensor is cut into chunks of a fixed element count (a
+ * compile-time constant of the library); cmb_optim_chunks(n) is the chunk count of n elements (0 for n <= 0), chunk0 the
+ * sum of the chunk counts of the jobs before this one, total_chunks the sum over all jobs.  The table is not validated on
+ * the host (it is device memory); the scalar arguments are, before anything is launched (CMB_ERR_BAD_ARG: NULL table with
+ * n_jobs > 0, a negative count, total_chunks > 0 with n_jobs == 0, NULL outputs, bias corrections <= 0, NaN lr).
+ *
+ * cmb_grad_sqnorm: *sumsq_out = sum over all jobs of sum g^2 (bf16 widened exactly; param / low / moments are not read).
+ * Deterministic and independent of the launch geometry and of the alignment path: each chunk's sum is formed in a fixed
+ * fp32 tree order into partial[chunk] (at least cmb_grad_sqnorm_workspace(total_chunks) floats, else CMB_ERR_WORKSPACE),
+ * a second launch adds the partials in index order in fp64 and rounds once.  total_chunks == 0 gives 0.  No atomics.
+ *
+ * cmb_adamw_step: one pass, for every element, all in fp32 with IEEE division and square root,
+ *     g  = grad * (grad_scale * coef)
+ *     p *= 1 - lr * weight_decay
+ *     m  = beta1 m + (1 - beta1) g
+ *     v  = beta2 v + (1 - beta2) g^2
+ *     p -= (lr / bias_correction1) * (m / (sqrt(v) / sqrt(bias_correction2) + eps))
+ *     low = bf16(p), round to nearest even, where low != NULL
+ * with coef = 1 when sumsq == NULL or max_norm <= 0, else min(1, max_norm / (grad_scale * sqrt(*sumsq) + 1e-6)), the
+ * expression of torch.nn.utils.clip_grad_norm_; *sumsq is read on the device, the host never waits for it.  A NaN *sumsq
+ * gives coef = 1, an infinite one coef = 0.  grad_scale: 1 / world for gradients that are sums over ranks, else 1.  One
+ * launch serves one parameter group at one step count (bias_correction = 1 - beta^step, formed by the caller). */
+typedef struct cmb_optim_job {
+  const void* grad;      /* CMB_F32 | CMB_BF16, n elements */
+  float* param;          /* fp32: the master, or the parameter itself */
+  void* low;             /* bf16 compute copy of param to refresh, or NULL */
+  float* exp_avg;        /* fp32 */
+  float* exp_avg_sq;     /* fp32 */
+  int64_t n;
+  int64_t chunk0;
+  int32_t grad_dtype;
+  int32_t reserved;
+} cmb_optim_job;
+int64_t cmb_optim_chunks(int64_t n);
+int64_t cmb_grad_sqnorm_workspace(int64_t total_chunks);
+int cmb_grad_sqnorm(const cmb_optim_job* jobs_device, int64_t n_jobs, int64_t total_chunks, float* partial,
+                    int64_t partial_floats, float* sumsq_out, void* stream);
+int cmb_adamw_step(const cmb_optim_job* jobs_device, int64_t n_jobs, int64_t total_chunks, float lr, float beta1,
+                   float beta2, float eps, float weight_decay, float bias_correction1, float bias_correction2,
+                   float grad_scale, const float* sumsq, float max_norm, void* stream);
+
 /* Elementwise y = act(a) * b (SwiGLU: act = SiLU) / y = act(a); a,b,y [rows, D] with strides. */
 int cmb_act_mul(int dtype, int32_t act, const void* a, int64_t lda, const void* b, int64_t ldb,
                 int64_t rows, int64_t D, void* y, int64_t ldy, void* stream);
