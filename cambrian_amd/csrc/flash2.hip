@@ -8,7 +8,7 @@
 //     the tile in flight.  V is consumed straight from the row-major image with transposing reads (ds_read_b64_tr_b16);
 //   * two K and two V buffers, ONE barrier per tile (the round-4 kernel: two): top of iteration t = "my pieces of K(t), V(t)
 //     have landed" (s_waitcnt vmcnt(0)) + barrier, then the DMA of tile t + 1 goes out and flies for the whole tile;
-//   * the LDS fragment reads of both products run a ring of four fragments ahead of the MFMAs in a fixed order (FL_FENCE);
+//   * the LDS fragment reads of both products run a ring of four fragments ahead of the MFMAs in a fixed order (CMB_SCHED_FENCE);
 //   * the exponentials sit INSIDE the P V phase: key block kb's eight probabilities are computed and converted while the four
 //     MFMAs of key block kb - 1 run (five vector instructions per MFMA), packed fp32 for the exponent argument and the row sum
 //     (two partial sums per lane); only the row maximum and the first key block's exponentials run with the matrix pipe idle.
@@ -18,40 +18,17 @@
 // kernel's 715: hipcc moved the score sets between the register halves ~100 times per tile; 64-query waves: 512 registers + spills.
 // Results agree with flash_fwd_kernel to fp32 rounding (the row sum is accumulated in two partial sums here), not bit for
 // bit; tests/test_flash_bwd_gpu.py holds both against fp32 autograd of the plain formula.
-#include <type_traits>
 #include "flash_common.h"
 #include "flash_layout.h"
+#include "tile_ops.h"
 
 namespace cmb_flash {
 namespace {
 
-#define FL_FENCE() __builtin_amdgcn_sched_barrier(0)
-
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef short s16x8_t __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4_t* lds_tr_ptr;
-typedef __bf16 bf16x2_v __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4_v __attribute__((ext_vector_type(4)));
 
 constexpr int kTile = FL_TILE_BYTES;            // 16 KiB
 constexpr int kSmemFwd = 4 * kTile;             // K ring (2) + V ring (2)
-
-__device__ __forceinline__ uint32_t cvt2(float a, float b) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){a, b}, bf16x2_v));
-}
-__device__ __forceinline__ const char* uniform_ptr(const char* q) {
-  const uint64_t v = (uint64_t)q;
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-  return (const char*)(((uint64_t)hi << 32) | lo);
-}
-// one LDS-DMA piece: 64 lanes x 16 bytes from base + voff (per lane) to LDS byte address lds (wave-uniform), lane-linear
-__device__ __forceinline__ void dma_piece(const char* base, uint32_t voff, uint32_t lds) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-               :
-               : "v"(voff), "s"(base), "s"(lds)
-               : "memory", "m0");
-}
 
 template <bool CAUSAL, bool MASKED>
 __global__ void __launch_bounds__(256, 2) flash_fwd2_kernel(const FlashParams p, bf16_t* __restrict__ out,
@@ -99,8 +76,8 @@ __global__ void __launch_bounds__(256, 2) flash_fwd2_kernel(const FlashParams p,
     // middle of a tile waits for the next tile's fills, issued a moment earlier: the prefetch ran serialised with the S products.
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]));
-    const char* kbase = uniform_ptr(reinterpret_cast<const char*>(p.k + (int64_t)b * p.kv_sb + (int64_t)hk * p.kv_sh));
-    const char* vbase = uniform_ptr(reinterpret_cast<const char*>(p.v + (int64_t)b * p.kv_sb + (int64_t)hk * p.kv_sh));
+    const char* kbase = wave_uniform_ptr(reinterpret_cast<const char*>(p.k + (int64_t)b * p.kv_sb + (int64_t)hk * p.kv_sh));
+    const char* vbase = wave_uniform_ptr(reinterpret_cast<const char*>(p.v + (int64_t)b * p.kv_sb + (int64_t)hk * p.kv_sh));
     const int64_t tile_bytes = (int64_t)64 * p.kv_ss * 2;   // global bytes from one tile's first row to the next's
     f32x16_t acc[DT];
 #pragma unroll
@@ -116,19 +93,19 @@ __global__ void __launch_bounds__(256, 2) flash_fwd2_kernel(const FlashParams p,
       const char* src = kbase + (int64_t)t * tile_bytes;
       const uint32_t dst = lds0 + (uint32_t)((t & 1) * kTile) + (uint32_t)wave * 4096u;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) dma_piece(src, voff[i], dst + (uint32_t)i * 1024u);
+      for (int i = 0; i < 4; ++i) lds_dma_piece(src, voff[i], dst + (uint32_t)i * 1024u);
     };
     auto issue_v = [&](int t) {   // V tile t -> V buffer t & 1
       const char* src = vbase + (int64_t)t * tile_bytes;
       const uint32_t dst = lds0 + (uint32_t)(2 * kTile + (t & 1) * kTile) + (uint32_t)wave * 4096u;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) dma_piece(src, voff[i], dst + (uint32_t)i * 1024u);
+      for (int i = 0; i < 4; ++i) lds_dma_piece(src, voff[i], dst + (uint32_t)i * 1024u);
     };
     auto kfrag = [&](const char* kbuf, int i) __attribute__((always_inline)) -> bf16x8_t {   // product i = 2 ks + kt
       return *reinterpret_cast<const bf16x8_t*>(kbuf + kro[i >> 1] + (i & 1) * 32 * FL_ROW_BYTES);
     };
     auto vfrag_half = [&](const char* vbuf, int i, int r) __attribute__((always_inline)) -> s16x4_t {   // product i = 4 kb + d
-      return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(vbuf + tro[i & 3][r] + (i >> 2) * 16 * FL_ROW_BYTES));
+      return lds_read_tr16(vbuf + tro[i & 3][r] + (i >> 2) * 16 * FL_ROW_BYTES);
     };
     // does tile t need a mask for some query of this wave (diagonal / ragged end / padded keys)?
     auto edge_tile = [&](int t, uint64_t vw) -> bool {
@@ -170,13 +147,13 @@ __global__ void __launch_bounds__(256, 2) flash_fwd2_kernel(const FlashParams p,
       bf16x8_t kr[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) kr[i] = kfrag(kbuf, i);
-      FL_FENCE();
+      CMB_SCHED_FENCE();
 #pragma unroll
       for (int i = 0; i < 2 * KS; ++i) {
         if (i < 2) (i ? s1 : s0) = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kr[i & 3], qf[0], (f32x16_t){0}, 0, 0, 0);
         else (i & 1 ? s1 : s0) = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kr[i & 3], qf[i >> 1], (i & 1 ? s1 : s0), 0, 0, 0);
         if (i + 4 < 2 * KS) kr[i & 3] = kfrag(kbuf, i + 4);
-        FL_FENCE();
+        CMB_SCHED_FENCE();
       }
     };
     // probabilities of elements (e, e + 1) (in place) and their share of the row sum: packed exponent argument, two partial sums
@@ -206,9 +183,9 @@ __global__ void __launch_bounds__(256, 2) flash_fwd2_kernel(const FlashParams p,
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         exp_pair(c0, c1, 2 * c, nm2, c22);
-        pf[0][c] = cvt2(pel(2 * c), pel(2 * c + 1));
+        pf[0][c] = cvt2_bf16(pel(2 * c), pel(2 * c + 1));
       }
-      FL_FENCE();
+      CMB_SCHED_FENCE();
 #pragma unroll
       for (int i = 0; i < 4 * DT; ++i) {
         const s16x8_t vv = {vlo[i & 3][0], vlo[i & 3][1], vlo[i & 3][2], vlo[i & 3][3],
@@ -222,9 +199,9 @@ __global__ void __launch_bounds__(256, 2) flash_fwd2_kernel(const FlashParams p,
         if (i < 12) {   // component c = i & 3 of the NEXT key block's operand: elements 8 (kb + 1) + 2 c, + 1
           const int e = 8 * ((i >> 2) + 1) + 2 * (i & 3);
           exp_pair(c0, c1, e, nm2, c22);
-          pf[((i >> 2) + 1) & 1][i & 3] = cvt2(pel(e), pel(e + 1));
+          pf[((i >> 2) + 1) & 1][i & 3] = cvt2_bf16(pel(e), pel(e + 1));
         }
-        FL_FENCE();
+        CMB_SCHED_FENCE();
       }
     };
 
@@ -343,8 +320,8 @@ __global__ void __launch_bounds__(256, 2) flash_dq2_kernel(const FlashParams p) 
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]), "+v"(dof[ks]));
     asm volatile("" : "+v"(lse2), "+v"(dq_d));
-    const char* kbase = uniform_ptr(reinterpret_cast<const char*>(p.k + (int64_t)b * p.kv_sb + (int64_t)hk * p.kv_sh));
-    const char* vbase = uniform_ptr(reinterpret_cast<const char*>(p.v + (int64_t)b * p.kv_sb + (int64_t)hk * p.kv_sh));
+    const char* kbase = wave_uniform_ptr(reinterpret_cast<const char*>(p.k + (int64_t)b * p.kv_sb + (int64_t)hk * p.kv_sh));
+    const char* vbase = wave_uniform_ptr(reinterpret_cast<const char*>(p.v + (int64_t)b * p.kv_sb + (int64_t)hk * p.kv_sh));
     const int64_t tile_bytes = (int64_t)64 * p.kv_ss * 2;
     f32x16_t acc[DT];
 #pragma unroll
@@ -359,9 +336,9 @@ __global__ void __launch_bounds__(256, 2) flash_dq2_kernel(const FlashParams p) 
       const char* vs_ = vbase + (int64_t)t * tile_bytes;
       const uint32_t kd = lds0 + (uint32_t)((t & 1) * kTile) + (uint32_t)wave * 4096u;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) dma_piece(ks_, voff[i], kd + (uint32_t)i * 1024u);
+      for (int i = 0; i < 4; ++i) lds_dma_piece(ks_, voff[i], kd + (uint32_t)i * 1024u);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) dma_piece(vs_, voff[i], kd + (uint32_t)(2 * kTile) + (uint32_t)i * 1024u);
+      for (int i = 0; i < 4; ++i) lds_dma_piece(vs_, voff[i], kd + (uint32_t)(2 * kTile) + (uint32_t)i * 1024u);
     };
     uint8_t vb = MASKED ? kv_byte(p, b, 0, lane) : (uint8_t)1;
     __syncthreads();
@@ -388,7 +365,7 @@ __global__ void __launch_bounds__(256, 2) flash_dq2_kernel(const FlashParams p) 
         bf16x8_t rf[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) rf[i] = rfrag(i);
-        FL_FENCE();
+        CMB_SCHED_FENCE();
 #pragma unroll
         for (int i = 0; i < 2 * KS; ++i) {
           if (i == 0) sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rf[0], qf[0], (f32x16_t){0}, 0, 0, 0);
@@ -396,7 +373,7 @@ __global__ void __launch_bounds__(256, 2) flash_dq2_kernel(const FlashParams p) 
           else if (i & 1) dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rf[i & 3], dof[i >> 1], dp, 0, 0, 0);
           else sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rf[i & 3], qf[i >> 1], sc, 0, 0, 0);
           if (i + 4 < 2 * KS) rf[i & 3] = rfrag(i + 4);
-          FL_FENCE();
+          CMB_SCHED_FENCE();
         }
         // mask only where the half tile can hold a masked key for some query of the wave
         if (CAUSAL ? (t * 64 + kt * 32 + 31 > q0) : (t * 64 + kt * 32 + 32 > p.kv_len)) {
@@ -417,13 +394,12 @@ __global__ void __launch_bounds__(256, 2) flash_dq2_kernel(const FlashParams p) 
         auto ds_pair = [&](int e) __attribute__((always_inline)) -> uint32_t {
           const float p0 = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[e], c2, -lse2));
           const float p1 = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[e + 1], c2, -lse2));
-          return cvt2(p0 * (dp[e] - dq_d), p1 * (dp[e + 1] - dq_d));
+          return cvt2_bf16(p0 * (dp[e] - dq_d), p1 * (dp[e + 1] - dq_d));
         };
         u32x4_v pf[2];
         s16x4_t tlo[4], thi[4];
         auto tfrag = [&](int i, int r) __attribute__((always_inline)) -> s16x4_t {
-          return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (lds_tr_ptr)(kc + tro[i & 3][r] + (kt * 32 + 16 * (i >> 2)) * FL_ROW_BYTES));
+          return lds_read_tr16(kc + tro[i & 3][r] + (kt * 32 + 16 * (i >> 2)) * FL_ROW_BYTES);
         };
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -432,7 +408,7 @@ __global__ void __launch_bounds__(256, 2) flash_dq2_kernel(const FlashParams p) 
         }
 #pragma unroll
         for (int c = 0; c < 4; ++c) pf[0][c] = ds_pair(2 * c);
-        FL_FENCE();
+        CMB_SCHED_FENCE();
 #pragma unroll
         for (int i = 0; i < 2 * DT; ++i) {
           const s16x8_t tv = {tlo[i & 3][0], tlo[i & 3][1], tlo[i & 3][2], tlo[i & 3][3],
@@ -444,7 +420,7 @@ __global__ void __launch_bounds__(256, 2) flash_dq2_kernel(const FlashParams p) 
             thi[i & 3] = tfrag(i + 4, 1);
           }
           if (i < 4) pf[1][i] = ds_pair(8 + 2 * i);
-          FL_FENCE();
+          CMB_SCHED_FENCE();
         }
       }
     }
@@ -468,48 +444,41 @@ __global__ void __launch_bounds__(256, 2) flash_dq2_kernel(const FlashParams p) 
 
 }  // namespace
 
+// dynamic LDS above the 48 KiB a kernel gets without asking: once per device, for the three instantiations of `kern`
+template <typename K>
+static bool flash2_attr(CmbAttrOnce& once, K kern) {
+  if (const uint32_t attr_bit = once.need()) {
+    bool ok = true;
+    flash_dispatch_all([&](auto c_, auto m_) {
+      ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(kern(c_, m_)), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     kSmemFwd) == hipSuccess;
+    });
+    if (!ok) return false;
+    once.done(attr_bit);
+  }
+  return true;
+}
+
 int launch_flash_fwd2(const FlashParams& p, bf16_t* out, float* lse, bool causal, hipStream_t stream) {
   static CmbAttrOnce attr_once;
-  if (const uint32_t attr_bit = attr_once.need()) {
-    bool ok = true;
-#define FWD2_ATTR(C_, M_)                                                                              \
-  ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(flash_fwd2_kernel<C_, M_>),             \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, kSmemFwd) == hipSuccess
-    FWD2_ATTR(true, true); FWD2_ATTR(true, false); FWD2_ATTR(false, false);
-#undef FWD2_ATTR
-    if (!ok) return CMB_ERR_LAUNCH;
-    attr_once.done(attr_bit);
-  }
-  const int64_t nqb = p.S / 128;
-  const dim3 grid((unsigned)((int64_t)flash_items((int)nqb, causal) * p.H * p.B));   // 1-D: flash_map.h
-  if (causal && p.key_valid) hipLaunchKernelGGL((flash_fwd2_kernel<true, true>), grid, dim3(256), kSmemFwd, stream, p, out, lse);
-  else if (causal) hipLaunchKernelGGL((flash_fwd2_kernel<true, false>), grid, dim3(256), kSmemFwd, stream, p, out, lse);
-  else hipLaunchKernelGGL((flash_fwd2_kernel<false, false>), grid, dim3(256), kSmemFwd, stream, p, out, lse);
+  auto kern = [](auto c_, auto m_) { return flash_fwd2_kernel<decltype(c_)::value, decltype(m_)::value>; };
+  if (!flash2_attr(attr_once, kern)) return CMB_ERR_LAUNCH;
+  const dim3 grid((unsigned)((int64_t)flash_items(p.S / 128, causal) * p.H * p.B));   // 1-D: flash_map.h
+  flash_dispatch(causal, p.key_valid != nullptr,
+                 [&](auto c_, auto m_) { hipLaunchKernelGGL(kern(c_, m_), grid, dim3(256), kSmemFwd, stream, p, out, lse); });
   CMB_CHECK_LAUNCH();
   return CMB_OK;
 }
-
 
 int launch_flash_dq2(const FlashParams& p, bool causal, hipStream_t stream) {
   static CmbAttrOnce attr_once;
-  if (const uint32_t attr_bit = attr_once.need()) {
-    bool ok = true;
-#define DQ2_ATTR(C_, M_)                                                                              \
-  ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(flash_dq2_kernel<C_, M_>),              \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, kSmemFwd) == hipSuccess
-    DQ2_ATTR(true, true); DQ2_ATTR(true, false); DQ2_ATTR(false, false);
-#undef DQ2_ATTR
-    if (!ok) return CMB_ERR_LAUNCH;
-    attr_once.done(attr_bit);
-  }
-  const int64_t nqb = p.S / 128;
-  const dim3 grid((unsigned)((int64_t)flash_items((int)nqb, causal) * p.H * p.B));
-  if (causal && p.key_valid) hipLaunchKernelGGL((flash_dq2_kernel<true, true>), grid, dim3(256), kSmemFwd, stream, p);
-  else if (causal) hipLaunchKernelGGL((flash_dq2_kernel<true, false>), grid, dim3(256), kSmemFwd, stream, p);
-  else hipLaunchKernelGGL((flash_dq2_kernel<false, false>), grid, dim3(256), kSmemFwd, stream, p);
+  auto kern = [](auto c_, auto m_) { return flash_dq2_kernel<decltype(c_)::value, decltype(m_)::value>; };
+  if (!flash2_attr(attr_once, kern)) return CMB_ERR_LAUNCH;
+  const dim3 grid((unsigned)((int64_t)flash_items(p.S / 128, causal) * p.H * p.B));
+  flash_dispatch(causal, p.key_valid != nullptr,
+                 [&](auto c_, auto m_) { hipLaunchKernelGGL(kern(c_, m_), grid, dim3(256), kSmemFwd, stream, p); });
   CMB_CHECK_LAUNCH();
   return CMB_OK;
 }
-
 
 }  // namespace cmb_flash

@@ -13,18 +13,21 @@
 // P is recomputed from the forward's log-sum-exp (natural log of the sum of exp(scale·q·k)); D = rowsum(dO∘O) is computed
 // in the dQ kernel's prologue (each lane owns a query row) and handed to the dK/dV kernel through dvec.  7 tile products instead of the 5 of a single-pass backward, nothing is atomically
 // accumulated, results are bit-reproducible.
+// These are the round-4 kernels.  The round-5 forward and dQ (LDS-DMA operand tiles, fragment reads in a fixed ring ahead of the
+// MFMAs) are separate kernels in flash2.hip, selected by CMB_KNOB_FLASH bits 0 / 1 in the entry points at the end of this file;
+// flash_fwd_kernel and flash_dq_kernel here have no pipelined variant.  Only flash_dkdv_kernel carries round-5 code, as its
+// template parameters PIPE (knob bit 4) and TR (bit 16).
 // Layout: all of q, k, v, o, do, dq, dk, dv are addressed as [B, S, H, 128] through (batch, token, head) element strides
 // (token-major storage, what ops.qkv_rope produces and the attention returns); lse / D are fp32 [B, H, S].
 #include "flash_common.h"
 #include "flash_layout.h"
+#include "tile_ops.h"
 
 using namespace cmb_flash;
 
 namespace {
 
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
 #define cvt8 cvt8_bf16
 
@@ -84,17 +87,9 @@ __device__ __forceinline__ void tile_put(const TileRegs& r, bf16_t* sR, bf16_t* 
 // ------------------------------------------------------------------------------------------------------------------
 // MASKED: a key-padding mask is given (causal only).  A separate instantiation: the unmasked kernels carry none of the mask's
 // registers or code (with a run-time pointer test instead they ran 3-8 % slower although every tile took the all-valid path).
-// PIPE (round 5, knob CMB_KNOB_FLASH = 1): the LDS fragment reads of the two products run a ring of four fragments AHEAD of
-// the MFMAs that consume them, in a fixed order (FLASH_FENCE = scheduling barrier).  Left to itself hipcc reuses eight fragment
-// registers: ds_read x 2, s_waitcnt, MFMA, s_waitcnt, MFMA, then the next two reads — every pair of MFMAs waits out a full
-// LDS round trip, and all eight products of a 32-key half chain on one accumulator (the assembly of the round-4 kernel,
-// profiles/r05_lab.md).  Here read i + 4 is issued right behind MFMA i and consecutive MFMAs alternate between the two
-// halves' accumulators.  Same products, same accumulation order per accumulator: bit-identical results.
-// (A cross-tile variant — S of tile t + 1 in the same basic block as the exponentials of tile t, two K buffers — was built
-// first and measured SLOWER, 460 vs 397 us at 8 x 2048 tokens: 256 registers with spills, and the compiler's interleave still
-// waited for every read.)
-#define FLASH_FENCE() __builtin_amdgcn_sched_barrier(0)
-template <bool CAUSAL, bool MASKED, bool PIPE>
+// This is the round-4 kernel as it stands (knob CMB_KNOB_FLASH bit 0 clear): hipcc orders its LDS fragment reads and MFMAs.
+// The round-5 forward with the fragment reads in a fixed ring ahead of the MFMAs is flash_fwd2_kernel (flash2.hip).
+template <bool CAUSAL, bool MASKED>
 __global__ void __launch_bounds__(256, 2) flash_fwd_kernel(const FlashParams p, bf16_t* __restrict__ out,
                                                            float* __restrict__ lse_out) {
   __shared__ __attribute__((aligned(16))) bf16_t sK[64 * LDR];
@@ -143,25 +138,6 @@ __global__ void __launch_bounds__(256, 2) flash_fwd_kernel(const FlashParams p, 
     if (CAUSAL && t * 64 > q0 + 31) continue;
     if (MASKED && vw == 0 && t * 64 + 63 < q0) continue;  // a tile of padding below the wave's diagonal: nothing to add
     f32x16_t s[2];
-    if (PIPE) {
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[kt][r] = 0.f;
-      // product i = 2 ks + kt: K rows of half kt, k-step ks
-      const bf16_t* kb0 = sK + j * LDR + g * 8;
-      bf16x8_t kr[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) kr[i] = *reinterpret_cast<const bf16x8_t*>(kb0 + (i & 1) * 32 * LDR + (i >> 1) * 16);
-      FLASH_FENCE();
-#pragma unroll
-      for (int i = 0; i < 2 * KS; ++i) {
-        s[i & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kr[i & 3], qf[i >> 1], s[i & 1], 0, 0, 0);
-        if (i + 4 < 2 * KS)
-          kr[i & 3] = *reinterpret_cast<const bf16x8_t*>(kb0 + ((i + 4) & 1) * 32 * LDR + ((i + 4) >> 1) * 16);
-        FLASH_FENCE();
-      }
-    } else {
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
 #pragma unroll
@@ -171,7 +147,6 @@ __global__ void __launch_bounds__(256, 2) flash_fwd_kernel(const FlashParams p, 
         const bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(sK + (kt * 32 + j) * LDR + ks * 16 + g * 8);
         s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], s[kt], 0, 0, 0);
       }
-    }
     }
     // VALU budget: this block runs once per 32 MFMAs of the wave, so every instruction per score element counts.
     // The mask is applied only on tiles that can hold a masked key for some query of the wave (the diagonal tiles /
@@ -219,36 +194,6 @@ __global__ void __launch_bounds__(256, 2) flash_fwd_kernel(const FlashParams p, 
         l += pv;
         s[kt][r] = pv;
       }
-    if (PIPE) {
-      bf16x8_t pf[4];
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) {
-        const int kt = kb >> 1, hh = kb & 1;
-        pf[kb] = cvt8(s[kt][8 * hh + 0], s[kt][8 * hh + 1], s[kt][8 * hh + 2], s[kt][8 * hh + 3], s[kt][8 * hh + 4],
-                      s[kt][8 * hh + 5], s[kt][8 * hh + 6], s[kt][8 * hh + 7]);
-      }
-      // product i = 4 kb + d: V^T rows of d tile d, keys 16 kb .. 16 kb + 15 of the tile (two 8-byte reads per fragment)
-      const bf16_t* vb0 = sVT + j * LDT + 4 * g;
-      bf16x4_t vlo[4], vhi[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        vlo[i] = *reinterpret_cast<const bf16x4_t*>(vb0 + (i & 3) * 32 * LDT + (i >> 2) * 16);
-        vhi[i] = *reinterpret_cast<const bf16x4_t*>(vb0 + (i & 3) * 32 * LDT + (i >> 2) * 16 + 8);
-      }
-      FLASH_FENCE();
-#pragma unroll
-      for (int i = 0; i < 4 * DT; ++i) {
-        bf16x8_t vf;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { vf[e] = vlo[i & 3][e]; vf[4 + e] = vhi[i & 3][e]; }
-        acc[i & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[i >> 2], acc[i & 3], 0, 0, 0);  // O^T[d][query]
-        if (i + 4 < 4 * DT) {
-          vlo[i & 3] = *reinterpret_cast<const bf16x4_t*>(vb0 + ((i + 4) & 3) * 32 * LDT + ((i + 4) >> 2) * 16);
-          vhi[i & 3] = *reinterpret_cast<const bf16x4_t*>(vb0 + ((i + 4) & 3) * 32 * LDT + ((i + 4) >> 2) * 16 + 8);
-        }
-        FLASH_FENCE();
-      }
-    } else {
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) {
       const int kt = kb >> 1, hh = kb & 1;
@@ -264,7 +209,6 @@ __global__ void __launch_bounds__(256, 2) flash_fwd_kernel(const FlashParams p, 
         for (int e = 0; e < 4; ++e) { vf[e] = lo[e]; vf[4 + e] = hi[e]; }
         acc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, acc[d], 0, 0, 0);  // O^T[d][query]
       }
-    }
     }
   }
   const float l_tot = l + __shfl_xor(l, 32, 64);
@@ -288,8 +232,9 @@ __global__ void __launch_bounds__(256, 2) flash_fwd_kernel(const FlashParams p, 
 // ------------------------------------------------------------------------------------------------------------------
 // MASKED: a key-padding mask is given (causal only).  A separate instantiation: the unmasked kernels carry none of the mask's
 // registers or code (with a run-time pointer test instead they ran 3-8 % slower although every tile took the all-valid path).
-template <bool CAUSAL, bool MASKED, bool PIPE>
-__global__ void __launch_bounds__(256, (CAUSAL && !PIPE) ? 2 : 1) flash_dq_kernel(const FlashParams p) {
+// The round-4 kernel (knob bit 1 clear); the round-5 dQ on LDS-DMA tiles is flash_dq2_kernel (flash2.hip).
+template <bool CAUSAL, bool MASKED>
+__global__ void __launch_bounds__(256, CAUSAL ? 2 : 1) flash_dq_kernel(const FlashParams p) {
   __shared__ __attribute__((aligned(16))) bf16_t sK[64 * LDR];
   __shared__ __attribute__((aligned(16))) bf16_t sV[64 * LDR];
   __shared__ __attribute__((aligned(16))) bf16_t sKT[HD * LDT];
@@ -406,100 +351,12 @@ __global__ void __launch_bounds__(256, (CAUSAL && !PIPE) ? 2 : 1) flash_dq_kerne
         }
       }
     };
-    const bool edge = (CAUSAL ? (t * 64 + 63 > q0) : (t * 64 + 64 > p.kv_len)) || (MASKED && vw != ~0ull);
-    if (PIPE && !edge) {
-      // Round 5 (knob CMB_KNOB_FLASH = 1), interior tiles: the dK/dV kernel's arrangement (see there) — four phases in a fixed
-      // order, every MFMA followed by the LDS read of the fragment four products ahead and by a slice of the other half's
-      // exponentials:  A  S0, dP0   B  S1, dP1 + dS0   C  dQ0 + dS1 (two elements per product)   D  dQ1.
-      // This variant is compiled for one workgroup per CU (the second set of score registers does not fit 256).
-      f32x16_t s0, dp0, s1, dp1;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) { s0[r] = 0.f; dp0[r] = 0.f; s1[r] = 0.f; dp1[r] = 0.f; }
-      // product i = 2 ks + w of a score phase: w = 0 S^T (K rows x Q fragment), w = 1 dP^T (V rows x dO fragment)
-      auto row_frag = [&](int kt, int i) __attribute__((always_inline)) -> bf16x8_t {
-        return *reinterpret_cast<const bf16x8_t*>(((i & 1) ? sV : sK) + (kt * 32 + j) * LDR + (i >> 1) * 16 + g * 8);
-      };
-      // product i = 4 kb + d of a dQ phase: K^T rows of d tile d, keys 16 kb .. of the half
-      auto tr_ptr = [&](int kt, int i) __attribute__((always_inline)) -> const bf16_t* {
-        return sKT + ((i & 3) * 32 + j) * LDT + kt * 32 + 16 * (i >> 2) + 4 * g;
-      };
-      auto elem = [&](int r, f32x16_t& s_, const f32x16_t& dp_) __attribute__((always_inline)) {
-        const float pr = __builtin_amdgcn_exp2f(__builtin_fmaf(s_[r], c2, -lse2));
-        s_[r] = pr * (dp_[r] - dq_d);
-      };
-      bf16x8_t rf[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) rf[i] = row_frag(0, i);
-      FLASH_FENCE();
-#pragma unroll
-      for (int i = 0; i < 2 * KS; ++i) {   // A
-        if (i & 1) dp0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rf[i & 3], dof[i >> 1], dp0, 0, 0, 0);
-        else s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rf[i & 3], qf[i >> 1], s0, 0, 0, 0);
-        rf[i & 3] = row_frag(i + 4 < 2 * KS ? 0 : 1, (i + 4) & (2 * KS - 1));
-        FLASH_FENCE();
-      }
-#pragma unroll
-      for (int i = 0; i < 2 * KS; ++i) {   // B
-        if (i & 1) dp1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rf[i & 3], dof[i >> 1], dp1, 0, 0, 0);
-        else s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rf[i & 3], qf[i >> 1], s1, 0, 0, 0);
-        if (i + 4 < 2 * KS) rf[i & 3] = row_frag(1, i + 4);
-        elem(i, s0, dp0);
-        FLASH_FENCE();
-      }
-      bf16x8_t pf[2];
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-        pf[kb] = cvt8(s0[8 * kb + 0], s0[8 * kb + 1], s0[8 * kb + 2], s0[8 * kb + 3], s0[8 * kb + 4], s0[8 * kb + 5],
-                      s0[8 * kb + 6], s0[8 * kb + 7]);
-      bf16x4_t tlo[4], thi[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const bf16_t* q_ = tr_ptr(0, i);
-        tlo[i] = *reinterpret_cast<const bf16x4_t*>(q_);
-        thi[i] = *reinterpret_cast<const bf16x4_t*>(q_ + 8);
-      }
-      FLASH_FENCE();
-#pragma unroll
-      for (int i = 0; i < 2 * DT; ++i) {   // C
-        bf16x8_t tf;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { tf[e] = tlo[i & 3][e]; tf[4 + e] = thi[i & 3][e]; }
-        acc[i & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tf, pf[i >> 2], acc[i & 3], 0, 0, 0);
-        {
-          const bf16_t* q_ = tr_ptr(i + 4 < 2 * DT ? 0 : 1, (i + 4) & (2 * DT - 1));
-          tlo[i & 3] = *reinterpret_cast<const bf16x4_t*>(q_);
-          thi[i & 3] = *reinterpret_cast<const bf16x4_t*>(q_ + 8);
-        }
-        elem(2 * i, s1, dp1);
-        elem(2 * i + 1, s1, dp1);
-        FLASH_FENCE();
-      }
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-        pf[kb] = cvt8(s1[8 * kb + 0], s1[8 * kb + 1], s1[8 * kb + 2], s1[8 * kb + 3], s1[8 * kb + 4], s1[8 * kb + 5],
-                      s1[8 * kb + 6], s1[8 * kb + 7]);
-      FLASH_FENCE();
-#pragma unroll
-      for (int i = 0; i < 2 * DT; ++i) {   // D
-        bf16x8_t tf;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { tf[e] = tlo[i & 3][e]; tf[4 + e] = thi[i & 3][e]; }
-        acc[i & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tf, pf[i >> 2], acc[i & 3], 0, 0, 0);
-        if (i + 4 < 2 * DT) {
-          const bf16_t* q_ = tr_ptr(1, i + 4);
-          tlo[i & 3] = *reinterpret_cast<const bf16x4_t*>(q_);
-          thi[i & 3] = *reinterpret_cast<const bf16x4_t*>(q_ + 8);
-        }
-        FLASH_FENCE();
-      }
-    } else {
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt) {
-        f32x16_t s, dp;
-        sdp(kt, s, dp);
-        mask_s(kt, s);
-        ds_dq(kt, s, dp);
-      }
+    for (int kt = 0; kt < 2; ++kt) {
+      f32x16_t s, dp;
+      sdp(kt, s, dp);
+      mask_s(kt, s);
+      ds_dq(kt, s, dp);
     }
   }
   bf16_t* out = p.dq + (int64_t)b * p.q_sb + (int64_t)qi * p.q_ss + (int64_t)h * p.q_sh;
@@ -523,6 +380,8 @@ __global__ void __launch_bounds__(256, (CAUSAL && !PIPE) ? 2 : 1) flash_dq_kerne
 // ------------------------------------------------------------------------------------------------------------------
 // MASKED: a key-padding mask is given (causal only).  A separate instantiation: the unmasked kernels carry none of the mask's
 // registers or code (with a run-time pointer test instead they ran 3-8 % slower although every tile took the all-valid path).
+// PIPE (round 5, knob bit 4) and TR belong to this kernel only: the forward and dQ kernels above have no such variants (their
+// round-5 forms are separate kernels in flash2.hip).  PIPE: the four-phase interior tile body, see it below.
 // TR (round 5, knob bit 16): the transposed fragments (dO^T for dV, Q^T for dK) are read out of the ROW-major Q / dO images with
 // ds_read_b64_tr_b16 instead of out of transposed copies: the 64 ds_write_b32 and the ~100 16-bit shuffles per tile and thread
 // that built those copies are gone.  The row-major images are then un-padded and XOR-swizzled (flash_layout.h: 256-byte rows, slot ^
@@ -644,10 +503,8 @@ __global__ void __launch_bounds__(256) flash_dkdv_kernel(const FlashParams p) {
       // 8-byte half r (0 / 1: rows + 8) of transposed fragment i = 8 qb16 + 2 d + w of half qs: w = 0 dO^T (dV), w = 1 Q^T (dK)
       auto tr_half = [&](int qs, int i, int r) __attribute__((always_inline)) -> bf16x4_t {
         if (TR) {
-          typedef short s16x4_v __attribute__((ext_vector_type(4)));
-          typedef __attribute__((address_space(3))) s16x4_v* lds_s16x4_p;
           const char* a_ = reinterpret_cast<const char*>((i & 1) ? sQ : sDO) + tro_[(i >> 1) & 3][r] + (qs * 32 + 16 * (i >> 3)) * FL_ROW_BYTES;
-          return __builtin_bit_cast(bf16x4_t, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)a_));
+          return __builtin_bit_cast(bf16x4_t, lds_read_tr16(a_));
         }
         const bf16_t* q_ = ((i & 1) ? sQT : sDOT) + (((i >> 1) & 3) * 32 + j) * LDT + qs * 32 + 16 * (i >> 3) + 4 * g;
         return *reinterpret_cast<const bf16x4_t*>(q_ + 8 * r);
@@ -718,8 +575,8 @@ __global__ void __launch_bounds__(256) flash_dkdv_kernel(const FlashParams p) {
       const bool edge0 = (CAUSAL ? (k0 + 31 > qt * 64) : (k0 + 32 > p.kv_len)) || wave_padded;
       const bool edge1 = (CAUSAL ? (k0 + 31 > qt * 64 + 32) : (k0 + 32 > p.kv_len)) || wave_padded;
       if (PIPE && !edge0 && !edge1) {
-        // Round 5 (knob CMB_KNOB_FLASH = 1), interior tiles.  One wave per SIMD has no other wave to fill its stalls, so the
-        // tile is issued as four phases of 16 MFMAs in a FIXED order (FLASH_FENCE): every MFMA is followed by the LDS read of
+        // Round 5 (knob CMB_KNOB_FLASH bit 4), interior tiles.  One wave per SIMD has no other wave to fill its stalls, so the
+        // tile is issued as four phases of 16 MFMAs in a FIXED order (CMB_SCHED_FENCE): every MFMA is followed by the LDS read of
         // the fragment four products ahead (ring of four) and by one element of the OTHER half's softmax arithmetic —
         //   A  S0, dP0                        B  S1, dP1   + P0, dS0 (element i per product)
         //   C  dV0, dK0  + P1, dS1            D  dV1, dK1
@@ -753,16 +610,16 @@ __global__ void __launch_bounds__(256) flash_dkdv_kernel(const FlashParams p) {
         // ---- A: S0, dP0
 #pragma unroll
         for (int i = 0; i < 4; ++i) rf[i] = row_frag(0, i);
-        FLASH_FENCE();
+        CMB_SCHED_FENCE();
 #pragma unroll
         for (int i = 0; i < 2 * KS; ++i) {
           if (i & 1) dp0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rf[i & 3], vf[i >> 1], dp0, 0, 0, 0);
           else s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rf[i & 3], kf[i >> 1], s0, 0, 0, 0);
           rf[i & 3] = row_frag(i + 4 < 2 * KS ? 0 : 1, (i + 4) & (2 * KS - 1));   // runs on into phase B's first four
-          FLASH_FENCE();
+          CMB_SCHED_FENCE();
         }
         load_ld(0);
-        FLASH_FENCE();
+        CMB_SCHED_FENCE();
         // ---- B: S1, dP1  +  the first half's probabilities
 #pragma unroll
         for (int i = 0; i < 2 * KS; ++i) {
@@ -770,7 +627,7 @@ __global__ void __launch_bounds__(256) flash_dkdv_kernel(const FlashParams p) {
           else s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rf[i & 3], kf[i >> 1], s1, 0, 0, 0);
           if (i + 4 < 2 * KS) rf[i & 3] = row_frag(1, i + 4);
           elem(i, s0, dp0, pr0);
-          FLASH_FENCE();
+          CMB_SCHED_FENCE();
         }
         bf16x8_t pf[2], dsf[2];
 #pragma unroll
@@ -786,7 +643,7 @@ __global__ void __launch_bounds__(256) flash_dkdv_kernel(const FlashParams p) {
           tlo[i] = tr_half(0, i, 0);
           thi[i] = tr_half(0, i, 1);
         }
-        FLASH_FENCE();
+        CMB_SCHED_FENCE();
         // ---- C: dV0, dK0  +  the second half's probabilities
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -801,7 +658,7 @@ __global__ void __launch_bounds__(256) flash_dkdv_kernel(const FlashParams p) {
             thi[i & 3] = tr_half(i + 4 < 16 ? 0 : 1, (i + 4) & 15, 1);
           }
           elem(i, s1, dp1, pr1);
-          FLASH_FENCE();
+          CMB_SCHED_FENCE();
         }
 #pragma unroll
         for (int h8 = 0; h8 < 2; ++h8) {
@@ -809,7 +666,7 @@ __global__ void __launch_bounds__(256) flash_dkdv_kernel(const FlashParams p) {
           pf[h8] = cvt8(pr1[o8], pr1[o8 + 1], pr1[o8 + 2], pr1[o8 + 3], pr1[o8 + 4], pr1[o8 + 5], pr1[o8 + 6], pr1[o8 + 7]);
           dsf[h8] = cvt8(s1[o8], s1[o8 + 1], s1[o8 + 2], s1[o8 + 3], s1[o8 + 4], s1[o8 + 5], s1[o8 + 6], s1[o8 + 7]);
         }
-        FLASH_FENCE();
+        CMB_SCHED_FENCE();
         // ---- D: dV1, dK1
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -823,7 +680,7 @@ __global__ void __launch_bounds__(256) flash_dkdv_kernel(const FlashParams p) {
             tlo[i & 3] = tr_half(1, i + 4, 0);
             thi[i & 3] = tr_half(1, i + 4, 1);
           }
-          FLASH_FENCE();
+          CMB_SCHED_FENCE();
         }
       } else {
 #pragma unroll
@@ -864,18 +721,12 @@ extern "C" int cmb_flash_attn_bwd(const void* q, const void* k, const void* v, c
                                   int64_t q_sb, int64_t q_ss, int64_t q_sh, int64_t kv_sb, int64_t kv_ss, int64_t kv_sh,
                                   float scale, int32_t causal, int64_t kv_len, const uint8_t* key_valid, float* dvec,
                                   void* dq, void* dk, void* dv, void* stream) {
-  if (!q || !k || !v || !o || !dout || !lse || !dvec || !dq || !dk || !dv) return CMB_ERR_BAD_ARG;
-  if (hd != HD || S <= 0 || (S % 128) != 0 || H <= 0 || HKV <= 0 || (H % HKV) != 0 || B < 0) return CMB_ERR_SHAPE;
-  if (!causal && (kv_len <= 0 || kv_len > S)) return CMB_ERR_SHAPE;
-  if (B == 0) return CMB_OK;
-  if ((q_ss % 8) || (q_sh % 8) || (q_sb % 8) || (kv_ss % 8) || (kv_sh % 8) || (kv_sb % 8)) return CMB_ERR_ALIGNMENT;
+  if (!o || !dout || !lse || !dvec || !dq || !dk || !dv) return CMB_ERR_BAD_ARG;
   FlashParams p;
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (const bf16_t*)o;
-  p.dout = (const bf16_t*)dout; p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv;
+  int rc = flash_fill_params(p, q, k, v, B, S, H, HKV, hd, q_sb, q_ss, q_sh, kv_sb, kv_ss, kv_sh, scale, causal, kv_len, key_valid);
+  if (rc != CMB_OK || p.B == 0) return rc;
+  p.o = (const bf16_t*)o; p.dout = (const bf16_t*)dout; p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv;
   p.lse = lse; p.dvec = dvec;
-  p.q_sb = q_sb; p.q_ss = q_ss; p.q_sh = q_sh; p.kv_sb = kv_sb; p.kv_ss = kv_ss; p.kv_sh = kv_sh;
-  p.B = (int)B; p.S = (int)S; p.H = H; p.HKV = HKV; p.scale = scale; p.kv_len = causal ? (int)S : (int)kv_len;
-  p.key_valid = causal ? key_valid : nullptr;
   hipStream_t s = (hipStream_t)stream;
   const int64_t nkb = S / 128;
   const int items = flash_items((int)nkb, causal != 0);
@@ -884,14 +735,14 @@ extern "C" int cmb_flash_attn_bwd(const void* q, const void* k, const void* v, c
   static CmbAttrOnce attr_once;
   if (const uint32_t attr_bit = attr_once.need()) {
     bool ok = true;
-#define DKDV_ATTR(C_, M_, P_)                                                                                   \
-  ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(flash_dkdv_kernel<C_, M_, P_, false>),           \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, smem) == hipSuccess &&              \
-       hipFuncSetAttribute(reinterpret_cast<const void*>(flash_dkdv_kernel<C_, M_, P_, true>),                  \
-                           hipFuncAttributeMaxDynamicSharedMemorySize, smem) == hipSuccess
-    DKDV_ATTR(true, true, false); DKDV_ATTR(true, false, false); DKDV_ATTR(false, false, false);
-    DKDV_ATTR(true, true, true); DKDV_ATTR(true, false, true); DKDV_ATTR(false, false, true);
-#undef DKDV_ATTR
+    auto attr = [&](auto kern) {
+      ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) == hipSuccess;
+    };
+    flash_dispatch_all([&](auto c_, auto m_) {
+      constexpr bool C = decltype(c_)::value, M = decltype(m_)::value;
+      attr(flash_dkdv_kernel<C, M, false, false>); attr(flash_dkdv_kernel<C, M, false, true>);
+      attr(flash_dkdv_kernel<C, M, true, false>); attr(flash_dkdv_kernel<C, M, true, true>);
+    });
     if (!ok) return CMB_ERR_LAUNCH;
     attr_once.done(attr_bit);
   }
@@ -899,21 +750,18 @@ extern "C" int cmb_flash_attn_bwd(const void* q, const void* k, const void* v, c
   // 16 = its transposed fragments by transposing reads; 0 = round 4  (bit 8, a dK/dV kernel on LDS-DMA tiles, is gone)
   const int knob = cmb_knob(CMB_KNOB_FLASH);
   const bool pipe_q = (knob & 2) != 0, pipe_k = (knob & 4) != 0, tr_k = (knob & 16) != 0;
-#define FLASH_BWD_LAUNCH(C_, M_)                                                                      \
-  do {                                                                                                \
-    if (pipe_q) {                                                                                     \
-      const int rc_ = launch_flash_dq2(p, C_, s);                                                     \
-      if (rc_ != CMB_OK) return rc_;                                                                  \
-    } else hipLaunchKernelGGL((flash_dq_kernel<C_, M_, false>), gq, dim3(256), 0, s, p);              \
-    if (pipe_k && tr_k) hipLaunchKernelGGL((flash_dkdv_kernel<C_, M_, true, true>), gk, dim3(256), smem, s, p); \
-    else if (pipe_k) hipLaunchKernelGGL((flash_dkdv_kernel<C_, M_, true, false>), gk, dim3(256), smem, s, p); \
-    else if (tr_k) hipLaunchKernelGGL((flash_dkdv_kernel<C_, M_, false, true>), gk, dim3(256), smem, s, p); \
-    else hipLaunchKernelGGL((flash_dkdv_kernel<C_, M_, false, false>), gk, dim3(256), smem, s, p);    \
-  } while (0)
-  if (causal && p.key_valid) FLASH_BWD_LAUNCH(true, true);
-  else if (causal) FLASH_BWD_LAUNCH(true, false);
-  else FLASH_BWD_LAUNCH(false, false);
-#undef FLASH_BWD_LAUNCH
+  flash_dispatch(causal != 0, p.key_valid != nullptr, [&](auto c_, auto m_) {
+    constexpr bool C = decltype(c_)::value, M = decltype(m_)::value;
+    if (pipe_q) {
+      rc = launch_flash_dq2(p, C, s);
+      if (rc != CMB_OK) return;
+    } else hipLaunchKernelGGL((flash_dq_kernel<C, M>), gq, dim3(256), 0, s, p);
+    if (pipe_k && tr_k) hipLaunchKernelGGL((flash_dkdv_kernel<C, M, true, true>), gk, dim3(256), smem, s, p);
+    else if (pipe_k) hipLaunchKernelGGL((flash_dkdv_kernel<C, M, true, false>), gk, dim3(256), smem, s, p);
+    else if (tr_k) hipLaunchKernelGGL((flash_dkdv_kernel<C, M, false, true>), gk, dim3(256), smem, s, p);
+    else hipLaunchKernelGGL((flash_dkdv_kernel<C, M, false, false>), gk, dim3(256), smem, s, p);
+  });
+  if (rc != CMB_OK) return rc;
   CMB_CHECK_LAUNCH();
   return CMB_OK;
 }
@@ -922,27 +770,17 @@ extern "C" int cmb_flash_attn_fwd(const void* q, const void* k, const void* v, i
                                   int32_t hd, int64_t q_sb, int64_t q_ss, int64_t q_sh, int64_t kv_sb, int64_t kv_ss,
                                   int64_t kv_sh, float scale, int32_t causal, int64_t kv_len, const uint8_t* key_valid,
                                   void* out, float* lse, void* stream) {
-  if (!q || !k || !v || !out || !lse) return CMB_ERR_BAD_ARG;
-  if (hd != HD || S <= 0 || (S % 128) != 0 || H <= 0 || HKV <= 0 || (H % HKV) != 0 || B < 0) return CMB_ERR_SHAPE;
-  if (!causal && (kv_len <= 0 || kv_len > S)) return CMB_ERR_SHAPE;
-  if (B == 0) return CMB_OK;
-  if ((q_ss % 8) || (q_sh % 8) || (q_sb % 8) || (kv_ss % 8) || (kv_sh % 8) || (kv_sb % 8)) return CMB_ERR_ALIGNMENT;
+  if (!out || !lse) return CMB_ERR_BAD_ARG;
   FlashParams p;
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = nullptr; p.dout = nullptr;
-  p.dq = p.dk = p.dv = nullptr; p.lse = nullptr; p.dvec = nullptr;
-  p.q_sb = q_sb; p.q_ss = q_ss; p.q_sh = q_sh; p.kv_sb = kv_sb; p.kv_ss = kv_ss; p.kv_sh = kv_sh;
-  p.B = (int)B; p.S = (int)S; p.H = H; p.HKV = HKV; p.scale = scale; p.kv_len = causal ? (int)S : (int)kv_len;
-  p.key_valid = causal ? key_valid : nullptr;
-  const int64_t nqb = S / 128;
+  const int rc = flash_fill_params(p, q, k, v, B, S, H, HKV, hd, q_sb, q_ss, q_sh, kv_sb, kv_ss, kv_sh, scale, causal, kv_len, key_valid);
+  if (rc != CMB_OK || p.B == 0) return rc;
   // knob bit 0: the round-5 forward on LDS-DMA tiles (flash2.hip); else the round-4 kernel
   if ((cmb_knob(CMB_KNOB_FLASH) & 1) != 0) return launch_flash_fwd2(p, (bf16_t*)out, lse, causal != 0, (hipStream_t)stream);
-  const dim3 grid((unsigned)((int64_t)flash_items((int)nqb, causal != 0) * H * B));   // 1-D: flash_map.h
-  if (causal && p.key_valid)
-    hipLaunchKernelGGL((flash_fwd_kernel<true, true, false>), grid, dim3(256), 0, (hipStream_t)stream, p, (bf16_t*)out, lse);
-  else if (causal)
-    hipLaunchKernelGGL((flash_fwd_kernel<true, false, false>), grid, dim3(256), 0, (hipStream_t)stream, p, (bf16_t*)out, lse);
-  else
-    hipLaunchKernelGGL((flash_fwd_kernel<false, false, false>), grid, dim3(256), 0, (hipStream_t)stream, p, (bf16_t*)out, lse);
+  const dim3 grid((unsigned)((int64_t)flash_items((int)(S / 128), causal != 0) * H * B));   // 1-D: flash_map.h
+  flash_dispatch(causal != 0, p.key_valid != nullptr, [&](auto c_, auto m_) {
+    hipLaunchKernelGGL((flash_fwd_kernel<decltype(c_)::value, decltype(m_)::value>), grid, dim3(256), 0, (hipStream_t)stream, p,
+                       (bf16_t*)out, lse);
+  });
   CMB_CHECK_LAUNCH();
   return CMB_OK;
 }

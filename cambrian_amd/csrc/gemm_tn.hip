@@ -18,16 +18,13 @@
 // gemm.hip's (gemm_common.h).  128 x 128 tile, 4 waves (2 x 2), each 64 x 64 as 2 x 2 v_mfma_f32_32x32x16_bf16 tiles.
 #include "gemm_common.h"
 #include "gemm_tn_layout.h"
+#include "tile_ops.h"
 
 using namespace cmb_gemm_detail;
 
 namespace {
 
 __device__ __attribute__((aligned(256))) char g_zero_row[256];   // zero-initialised: the source of rows >= K
-
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef short s16x8_t __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4_t* lds_tr_ptr;
 
 // Round 6: a ring of FOUR 32-row stages instead of two 64-row ones (the same 64 KiB).  With two stages every K-step ended in
 // s_waitcnt vmcnt(0) + barrier, so a stage's DMA had ONE step of MFMAs (16 per wave, ~0.25 us) to land in: the split-K weight
@@ -139,10 +136,10 @@ __global__ void __launch_bounds__(256) gemm_tn_kernel(const GemmParams p_in) {
         bf16x8_t a[2], b[2];
 #pragma unroll
         for (int f = 0; f < 2; ++f) {
-          const s16x4_t a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(base + a_off[f] + tn_frag_piece(s, 0) * 1024));
-          const s16x4_t a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(base + a_off[f] + tn_frag_piece(s, 1) * 1024));
-          const s16x4_t b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(base + b_off[f] + tn_frag_piece(s, 0) * 1024));
-          const s16x4_t b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(base + b_off[f] + tn_frag_piece(s, 1) * 1024));
+          const s16x4_t a0 = lds_read_tr16(base + a_off[f] + tn_frag_piece(s, 0) * 1024);
+          const s16x4_t a1 = lds_read_tr16(base + a_off[f] + tn_frag_piece(s, 1) * 1024);
+          const s16x4_t b0 = lds_read_tr16(base + b_off[f] + tn_frag_piece(s, 0) * 1024);
+          const s16x4_t b1 = lds_read_tr16(base + b_off[f] + tn_frag_piece(s, 1) * 1024);
           const s16x8_t av = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
           const s16x8_t bv = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
           a[f] = __builtin_bit_cast(bf16x8_t, av);

@@ -30,7 +30,7 @@
 // backward 373 us stand-alone = 5.1 / 4.8 TB/s over the 1069 / 1806 MB the kernels touch (PMC: every byte once;
 // profiles/r03_hbm_kernels_table.md).  (The v_dot2c / v_fma forms of these products were VALU-bound at one wave per SIMD:
 // 372 us forward and 646 us backward.)
-#include "common.h"
+#include "tile_ops.h"
 #include "sva_abs_layout.h"
 
 namespace {
@@ -43,12 +43,7 @@ constexpr int kSmemBwd = kWinBytes + kCoefBytes;
 constexpr int kMaxD = 4;      // directly projected towers (one key each) beside the absorbed one
 constexpr int kPStride = 20;  // P row of a (query, head): [0, 4) the direct towers' keys, [4, 20) the absorbed tokens
 
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef short s16x8_t __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) s16x4_t* lds_tr_ptr;
 
 struct AbsParams {
   int B, qside, ntowers, window_major;
@@ -88,13 +83,9 @@ __device__ __forceinline__ float qmax(float v) {
   return v;
 }
 
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
-  const f32x2_t v = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
 __device__ __forceinline__ s16x4_t pack4_bf16(float a, float b, float c, float d) {
   typedef uint32_t u32x2_v __attribute__((ext_vector_type(2)));
-  const u32x2_v w = {pack_bf16(a, b), pack_bf16(c, d)};
+  const u32x2_v w = {cvt2_bf16(a, b), cvt2_bf16(c, d)};
   return __builtin_bit_cast(s16x4_t, w);
 }
 
@@ -164,8 +155,8 @@ __device__ __forceinline__ void token_mix(const char* xs, s16x4_t coef, bf16_t* 
   bf16_t* op = orow + i * kC + qd * 8;
 #pragma unroll 4
   for (int cg = 0; cg < 32; ++cg) {
-    const s16x4_t a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(xs + abs_mix_off(i, qd, cg, 0)));
-    const s16x4_t a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(xs + abs_mix_off(i, qd, cg, 1)));
+    const s16x4_t a0 = lds_read_tr16(xs + abs_mix_off(i, qd, cg, 0));
+    const s16x4_t a1 = lds_read_tr16(xs + abs_mix_off(i, qd, cg, 1));
     const f32x4_t z = {0.f, 0.f, 0.f, 0.f};
     const f32x4_t d0 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a0, coef, z, 0, 0, 0);
     const f32x4_t d1 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a1, coef, z, 0, 0, 0);
@@ -451,8 +442,8 @@ __global__ void __launch_bounds__(64) sva_abs_bwd_kernel(const AbsParams p) {
           f32x4_t dd[2];
 #pragma unroll
           for (int T = 0; T < 2; ++T) {
-            const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(xs + abs_w_read_off(i, qd, 0, cg, T)));
-            const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr)(xs + abs_w_read_off(i, qd, 1, cg, T)));
+            const s16x4_t lo = lds_read_tr16(xs + abs_w_read_off(i, qd, 0, cg, T));
+            const s16x4_t hi = lds_read_tr16(xs + abs_w_read_off(i, qd, 1, cg, T));
             const s16x8_t a = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
             dd[T] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), cf, f32x4_t{0.f, 0.f, 0.f, 0.f}, 0,
                                                             0, 0);

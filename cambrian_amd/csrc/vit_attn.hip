@@ -14,7 +14,7 @@
 //                    no shuffle; V^T fragments are two 8-byte LDS reads in the same key order.
 // fp32 path (parity tests): one wave per query, VALU dot products, same online softmax.
 #include <type_traits>
-#include "common.h"
+#include "tile_ops.h"
 #include "flash_layout.h"
 #include "vit_layout.h"
 
@@ -251,26 +251,7 @@ template <> struct VitTile<96> {
   static __device__ __forceinline__ int tr_frag(int r16, int c32, int read, int lane) { return fl_tr_frag_off(r16, c32, read, lane); }
 };
 
-#define VA_FENCE() __builtin_amdgcn_sched_barrier(0)
-typedef short va_s16x4_t __attribute__((ext_vector_type(4)));
-typedef short va_s16x8_t __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) va_s16x4_t* va_lds_tr_ptr;
-typedef __bf16 va_bf16x2_v __attribute__((ext_vector_type(2)));
 typedef uint32_t va_u32x4_v __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t va_cvt2(float a, float b) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){a, b}, va_bf16x2_v));
-}
-__device__ __forceinline__ const char* va_uniform_ptr(const char* q) {
-  const uint64_t v = (uint64_t)q;
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-  return (const char*)(((uint64_t)hi << 32) | lo);
-}
-// one LDS-DMA piece: 64 lanes x 16 bytes from base + voff (per lane) to LDS byte address lds (wave-uniform), lane-linear
-__device__ __forceinline__ void va_dma_piece(const char* base, uint32_t voff, uint32_t lds) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(base), "s"(lds) : "memory", "m0");
-}
 
 template <int HD, int NW, int WPE>
 __global__ void __launch_bounds__(64 * NW, WPE) vit_attn_dma_kernel(const bf16_t* __restrict__ qkv, int N, int heads, int nqb,
@@ -323,8 +304,8 @@ __global__ void __launch_bounds__(64 * NW, WPE) vit_attn_dma_kernel(const bf16_t
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]));
 
-  const char* kbase = va_uniform_ptr(reinterpret_cast<const char*>(base + C));
-  const char* vbase = va_uniform_ptr(reinterpret_cast<const char*>(base + 2 * C));
+  const char* kbase = wave_uniform_ptr(reinterpret_cast<const char*>(base + C));
+  const char* vbase = wave_uniform_ptr(reinterpret_cast<const char*>(base + 2 * C));
   const int64_t tile_bytes = 64 * ld * 2;
   auto issue = [&](int t) {   // K tile t -> K buffer t & 1, V tile t -> V buffer t & 1
     const bool last = t == nt - 1;
@@ -333,15 +314,15 @@ __global__ void __launch_bounds__(64 * NW, WPE) vit_attn_dma_kernel(const bf16_t
     const char* ks = kbase + (int64_t)t * tile_bytes;
     const char* vs = vbase + (int64_t)t * tile_bytes;
 #pragma unroll
-    for (int i = 0; i < PW; ++i) va_dma_piece(ks, last ? voff_l[i] : voff[i], dk + (uint32_t)i * 1024u);
+    for (int i = 0; i < PW; ++i) lds_dma_piece(ks, last ? voff_l[i] : voff[i], dk + (uint32_t)i * 1024u);
 #pragma unroll
-    for (int i = 0; i < PW; ++i) va_dma_piece(vs, last ? voff_l[i] : voff[i], dv + (uint32_t)i * 1024u);
+    for (int i = 0; i < PW; ++i) lds_dma_piece(vs, last ? voff_l[i] : voff[i], dv + (uint32_t)i * 1024u);
   };
   auto kfrag = [&](const char* kbuf, int i) __attribute__((always_inline)) -> bf16x8_t {   // product i = 2 ks + kt
     return *reinterpret_cast<const bf16x8_t*>(kbuf + kro[i >> 1] + (i & 1) * 32 * T::ROWB);
   };
-  auto vfrag_half = [&](const char* vbuf, int i, int r) __attribute__((always_inline)) -> va_s16x4_t {   // product i = DT kb + d
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((va_lds_tr_ptr)(vbuf + tro[i % DT][r] + (i / DT) * 16 * T::ROWB));
+  auto vfrag_half = [&](const char* vbuf, int i, int r) __attribute__((always_inline)) -> s16x4_t {   // product i = DT kb + d
+    return lds_read_tr16(vbuf + tro[i % DT][r] + (i / DT) * 16 * T::ROWB);
   };
 
   f32x16_t acc[DT];
@@ -367,13 +348,13 @@ __global__ void __launch_bounds__(64 * NW, WPE) vit_attn_dma_kernel(const bf16_t
       bf16x8_t kr[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) kr[i] = kfrag(kc, i);
-      VA_FENCE();
+      CMB_SCHED_FENCE();
 #pragma unroll
       for (int i = 0; i < 2 * KS; ++i) {
         if (i < 2) (i ? s1 : s0) = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kr[i & 3], qf[0], (f32x16_t){0}, 0, 0, 0);
         else (i & 1 ? s1 : s0) = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kr[i & 3], qf[i >> 1], (i & 1 ? s1 : s0), 0, 0, 0);
         if (i + 4 < 2 * KS) kr[i & 3] = kfrag(kc, i + 4);
-        VA_FENCE();
+        CMB_SCHED_FENCE();
       }
     }
     if (LAST && last_rows < 64) {
@@ -423,7 +404,7 @@ __global__ void __launch_bounds__(64 * NW, WPE) vit_attn_dma_kernel(const bf16_t
         s[r + 1] = pv[1];
       };
       va_u32x4_v pf[2];
-      va_s16x4_t vlo[4], vhi[4];
+      s16x4_t vlo[4], vhi[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         vlo[i] = vfrag_half(vc, i, 0);
@@ -432,13 +413,13 @@ __global__ void __launch_bounds__(64 * NW, WPE) vit_attn_dma_kernel(const bf16_t
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         exp_pair(2 * c);
-        pf[0][c] = va_cvt2(pel(2 * c), pel(2 * c + 1));
+        pf[0][c] = cvt2_bf16(pel(2 * c), pel(2 * c + 1));
       }
-      VA_FENCE();
+      CMB_SCHED_FENCE();
 #pragma unroll
       for (int i = 0; i < NP; ++i) {
         const int kb = i / DT, d = i % DT;
-        const va_s16x8_t vv = {vlo[i & 3][0], vlo[i & 3][1], vlo[i & 3][2], vlo[i & 3][3],
+        const s16x8_t vv = {vlo[i & 3][0], vlo[i & 3][1], vlo[i & 3][2], vlo[i & 3][3],
                                vhi[i & 3][0], vhi[i & 3][1], vhi[i & 3][2], vhi[i & 3][3]};
         acc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, vv), __builtin_bit_cast(bf16x8_t, pf[kb & 1]),
                                                          acc[d], 0, 0, 0);
@@ -451,10 +432,10 @@ __global__ void __launch_bounds__(64 * NW, WPE) vit_attn_dma_kernel(const bf16_t
           for (int c = c_lo; c < c_hi; ++c) {
             const int e = 8 * (kb + 1) + 2 * c;
             exp_pair(e);
-            pf[(kb + 1) & 1][c] = va_cvt2(pel(e), pel(e + 1));
+            pf[(kb + 1) & 1][c] = cvt2_bf16(pel(e), pel(e + 1));
           }
         }
-        VA_FENCE();
+        CMB_SCHED_FENCE();
       }
     }
   };

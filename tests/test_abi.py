@@ -125,3 +125,37 @@ def test_knob_values_are_validated(built):
     finally:
         for k, v in enumerate(saved):
             assert lib.cmb_knob_set(k, v) == ok
+
+
+def test_flash_attn_arguments_are_checked_before_any_launch(built):
+    """cmb_flash_attn_fwd / _bwd share one host-side argument check (flash_common.h): the status per kind of mistake and the
+    order of the checks.  Every case returns before anything is launched; the pointers are never dereferenced."""
+    import ctypes as C
+    lib = built.load()
+    ok, bad_arg, alignment, shape = 0, -1, -2, -3
+    buf = (C.c_float * 16)()
+    p = C.addressof(buf)
+
+    def fwd(q=p, k=p, v=p, B=2, S=256, H=4, HKV=2, hd=128, q_ss=512, kv_sh=128, causal=1, kv_len=256, out=p, lse=p):
+        return lib.cmb_flash_attn_fwd(q, k, v, B, S, H, HKV, hd, S * H * 128, q_ss, 128, S * HKV * 128, HKV * 128, kv_sh, 0.088,
+                                      causal, kv_len, None, out, lse, None)
+
+    def bwd(q=p, k=p, v=p, o=p, dout=p, lse=p, B=2, S=256, H=4, HKV=2, hd=128, q_ss=512, kv_sh=128, causal=1, kv_len=256,
+            dvec=p, dq=p, dk=p, dv=p):
+        return lib.cmb_flash_attn_bwd(q, k, v, o, dout, lse, B, S, H, HKV, hd, S * H * 128, q_ss, 128, S * HKV * 128, HKV * 128,
+                                      kv_sh, 0.088, causal, kv_len, None, dvec, dq, dk, dv, None)
+
+    for f, ptrs in ((fwd, ("q", "k", "v", "out", "lse")), (bwd, ("q", "k", "v", "o", "dout", "lse", "dvec", "dq", "dk", "dv"))):
+        for name in ptrs:
+            assert f(**{name: None}) == bad_arg, f"{f.__name__}: NULL {name}"
+            assert f(**{name: None}, hd=64, B=0) == bad_arg             # the null test comes first
+        assert f(hd=64) == shape
+        assert f(S=100) == shape and f(S=0) == shape
+        assert f(H=3, HKV=2) == shape
+        assert f(H=0) == shape and f(HKV=0) == shape and f(B=-1) == shape
+        assert f(causal=0, kv_len=0) == shape and f(causal=0, kv_len=257) == shape
+        assert f(q_ss=4) == alignment and f(kv_sh=4) == alignment and f(q_ss=516) == alignment
+        assert f(B=0) == ok
+        assert f(B=0, causal=1, kv_len=0) == ok                          # kv_len matters only to the bidirectional kernels
+        assert f(B=0, q_ss=4) == ok                                      # an empty batch returns before the stride test ...
+        assert f(B=0, hd=64) == shape and f(B=0, causal=0, kv_len=0) == shape   # ... and after the shape tests
