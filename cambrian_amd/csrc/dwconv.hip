@@ -8,6 +8,7 @@
 // (XT+6)*7 / XT = 17.5 vector loads per output instead of 49.
 #include <type_traits>
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -32,8 +33,7 @@ __global__ void __launch_bounds__(256) dwconv7x7_kernel(const T* __restrict__ x,
       load8f(bias + cg * 8, bb);
 #pragma unroll
       for (int o = 0; o < XT; ++o)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[o][e] = bb[e];
+        FOR8(e) acc[o][e] = bb[e];
     }
     for (int dy = 0; dy < 7; ++dy) {
       const int iy = yy + dy - 3;
@@ -46,8 +46,7 @@ __global__ void __launch_bounds__(256) dwconv7x7_kernel(const T* __restrict__ x,
         if (ix >= 0 && ix < W) {
           Vec8<T>::load(row + (int64_t)ix * C, in[k]);
         } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) in[k][e] = 0.f;
+          FOR8(e) in[k][e] = 0.f;
         }
       }
 #pragma unroll
@@ -56,8 +55,7 @@ __global__ void __launch_bounds__(256) dwconv7x7_kernel(const T* __restrict__ x,
         load8f(w + (int64_t)(dy * 7 + dx) * C + cg * 8, ww);
 #pragma unroll
         for (int o = 0; o < XT; ++o)
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc[o][e] += ww[e] * in[o + dx][e];
+          FOR8(e) acc[o][e] += ww[e] * in[o + dx][e];
       }
     }
     T* orow = y + ((b * H + yy) * (int64_t)W) * C + cg * 8;
@@ -111,8 +109,7 @@ __global__ void __launch_bounds__(256) dwconv7x7_lds_kernel(const T* __restrict_
       const int64_t off = ok ? (((int64_t)iy * W + ix) * C + c0 + cv * 8) : (int64_t)(c0 + cv * 8);
       vec_t v = *reinterpret_cast<const vec_t*>(xb + off);  // (clamped address: always a valid element of x)
       if (!ok) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = (T)0.f;
+        FOR8(e) v[e] = (T)0.f;
       }
       r[k] = v;
     }
@@ -134,8 +131,7 @@ __global__ void __launch_bounds__(256) dwconv7x7_lds_kernel(const T* __restrict_
     load8f(bias + c0 + cl * 8, bb);
 #pragma unroll
     for (int o = 0; o < 4; ++o)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) acc[o][e] = bb[e];
+      FOR8(e) acc[o][e] = bb[e];
   }
 #pragma unroll 1
   for (int dy = 0; dy < 7; ++dy) {
@@ -149,8 +145,7 @@ __global__ void __launch_bounds__(256) dwconv7x7_lds_kernel(const T* __restrict_
       load8f(wt + (dy * 7 + dx) * CC + cl * 8, ww);
 #pragma unroll
       for (int o = 0; o < 4; ++o)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[o][e] += ww[e] * in[o + dx][e];
+        FOR8(e) acc[o][e] += ww[e] * in[o + dx][e];
     }
   }
   const int oy = ty0 + sy;
@@ -409,30 +404,18 @@ extern "C" int cmb_dwconv7x7_nhwc(int dtype, const void* x, int64_t B, int64_t H
   if (B == 0) return CMB_OK;
   constexpr int XT = 4;
   const int64_t total = B * H * ((W + XT - 1) / XT) * (C / 8);
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 65535) blocks = 65535;
   hipStream_t s = (hipStream_t)stream;
   const int variant = cmb_knob(CMB_KNOB_DWCONV);
   if (variant != 0 && (C & 63) == 0 && cmb_aligned16(x) && cmb_aligned16(y) && cmb_aligned16(w) && cmb_aligned16(bias)) {
     // column-walking kernel; rows per chunk: fewer rows = more waves, more halo rows re-read (profiles/r04_lab.md)
     const int chunk = variant == 1 ? (H >= 128 ? 64 : 32) : variant;
-    if (dtype == CMB_BF16) return launch_dwconv_col<bf16_t>(x, B, (int)H, (int)W, (int)C, w, bias, y, chunk, s);
-    if (dtype == CMB_F32) return launch_dwconv_col<float>(x, B, (int)H, (int)W, (int)C, w, bias, y, chunk, s);
-    return CMB_ERR_BAD_ARG;
+    DT_SWITCH(dtype, return launch_dwconv_col<T>(x, B, (int)H, (int)W, (int)C, w, bias, y, chunk, s));
   }
   if ((C & 63) == 0 && B <= 65535 && cmb_aligned16(x) && cmb_aligned16(y)) {
-    if (dtype == CMB_BF16) return launch_dwconv_lds<bf16_t>(x, B, (int)H, (int)W, (int)C, w, bias, y, s);
-    if (dtype == CMB_F32) return launch_dwconv_lds<float>(x, B, (int)H, (int)W, (int)C, w, bias, y, s);
-    return CMB_ERR_BAD_ARG;
+    DT_SWITCH(dtype, return launch_dwconv_lds<T>(x, B, (int)H, (int)W, (int)C, w, bias, y, s));
   }
-  if (dtype == CMB_BF16)
-    hipLaunchKernelGGL((dwconv7x7_kernel<bf16_t, XT>), dim3((unsigned)blocks), dim3(256), 0, s, (const bf16_t*)x, B,
-                       (int)H, (int)W, (int)C, w, bias, (bf16_t*)y);
-  else if (dtype == CMB_F32)
-    hipLaunchKernelGGL((dwconv7x7_kernel<float, XT>), dim3((unsigned)blocks), dim3(256), 0, s, (const float*)x, B,
-                       (int)H, (int)W, (int)C, w, bias, (float*)y);
-  else
-    return CMB_ERR_BAD_ARG;
+  DT_SWITCH(dtype, hipLaunchKernelGGL((dwconv7x7_kernel<T, XT>), dim3(grid_for(total, 256, 65535)), dim3(256), 0, s, (const T*)x,
+                                      B, (int)H, (int)W, (int)C, w, bias, (T*)y));
   CMB_CHECK_LAUNCH();
   return CMB_OK;
 }
@@ -444,14 +427,8 @@ extern "C" int cmb_dwconv7x7_wgrad(int dtype, const void* x, const void* dy, int
   if (B == 0) return CMB_OK;
   const dim3 grid((unsigned)slots, (unsigned)(C / 64));
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CMB_BF16)
-    hipLaunchKernelGGL(dwconv7x7_wgrad_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)dy, (int)B,
-                       (int)H, (int)W, (int)C, partial);
-  else if (dtype == CMB_F32)
-    hipLaunchKernelGGL(dwconv7x7_wgrad_kernel<float>, grid, dim3(256), 0, s, (const float*)x, (const float*)dy, (int)B,
-                       (int)H, (int)W, (int)C, partial);
-  else
-    return CMB_ERR_BAD_ARG;
+  DT_SWITCH(dtype, hipLaunchKernelGGL(dwconv7x7_wgrad_kernel<T>, grid, dim3(256), 0, s, (const T*)x, (const T*)dy, (int)B, (int)H,
+                                      (int)W, (int)C, partial));
   CMB_CHECK_LAUNCH();
   return CMB_OK;
 }

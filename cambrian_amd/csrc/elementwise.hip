@@ -2,16 +2,10 @@
 // activation helpers, token mean, embedding splice (bit-exact gather/scatter), patch gathers and the
 // bilinear token-grid resampler.  All use 16/32-byte vector accesses along the contiguous dimension.
 #include "common.h"
+#include "launch.h"
 #include "resample_core.h"
 
 namespace {
-
-inline unsigned grid_for(int64_t items, int threads = 256, int64_t cap = 65535) {
-  int64_t b = (items + threads - 1) / threads;
-  if (b > cap) b = cap;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
 
 // ---------------------------------------------------------------------------------------------
 // transpose: out[C, R_pad] = in[R, C]^T, zero fill for r >= R.  64x64 tiles through LDS.
@@ -29,8 +23,7 @@ __global__ void __launch_bounds__(256) transpose_kernel(const T* __restrict__ in
     float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const int64_t gr = r0 + row, gc = c0 + cv * 8;
     if (gr < R && gc < C) Vec8<T>::load(in + gr * ld_in + gc, v);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) tile[row * LD + cv * 8 + e] = (T)v[e];
+    FOR8(e) tile[row * LD + cv * 8 + e] = (T)v[e];
   }
   __syncthreads();
 #pragma unroll
@@ -39,8 +32,7 @@ __global__ void __launch_bounds__(256) transpose_kernel(const T* __restrict__ in
     const int64_t gc = c0 + c, gr = r0 + rv * 8;
     if (gc < C && gr < R_pad) {
       float v[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = (float)tile[(rv * 8 + e) * LD + c];
+      FOR8(e) v[e] = (float)tile[(rv * 8 + e) * LD + c];
       Vec8<T>::store(out + gc * R_pad + gr, v);
     }
   }
@@ -82,8 +74,7 @@ __global__ void __launch_bounds__(256) weight_prep_kernel(const cmb_prep_job one
       else Vec8<bf16_t>::load(reinterpret_cast<const bf16_t*>(j.src) + gr * j.ld_src + gc, v);
       if (j.dst) Vec8<bf16_t>::store(reinterpret_cast<bf16_t*>(j.dst) + gr * j.cols + gc, v);
     }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) tile[row * LD + cv * 8 + e] = (bf16_t)v[e];
+    FOR8(e) tile[row * LD + cv * 8 + e] = (bf16_t)v[e];
   }
   if (!j.dst_t) return;   // (uniform per workgroup)
   __syncthreads();
@@ -93,8 +84,7 @@ __global__ void __launch_bounds__(256) weight_prep_kernel(const cmb_prep_job one
     const int64_t gc = c0 + c, gr = r0 + rv * 8;
     if (gc < j.cols && gr < j.rows_pad) {
       bf16x8_t o;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = tile[(rv * 8 + e) * LD + c];
+      FOR8(e) o[e] = tile[(rv * 8 + e) * LD + c];
       *reinterpret_cast<bf16x8_t*>(reinterpret_cast<bf16_t*>(j.dst_t) + gc * j.rows_pad + gr) = o;
     }
   }
@@ -121,16 +111,13 @@ __global__ void __launch_bounds__(256) colsum_kernel(const T* __restrict__ in, i
       Vec8<T>::load(in + r * ld_in + cv * 8, v);
       if (scale) {
         const float f = scale[r * ld_scale + (cv * 8) / group];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] = fmaf(f, v[e], acc[e]);
+        FOR8(e) acc[e] = fmaf(f, v[e], acc[e]);
       } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] += v[e];
+        FOR8(e) acc[e] += v[e];
       }
     }
   }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) red[wave][lane * 8 + e] = acc[e];
+  FOR8(e) red[wave][lane * 8 + e] = acc[e];
   __syncthreads();
   for (int i = threadIdx.x; i < 512; i += 256) {
     const int64_t col = (int64_t)blockIdx.x * 512 + i;
@@ -161,13 +148,11 @@ __global__ void __launch_bounds__(256) act_mul_kernel(int act, const T* __restri
     const int c = (int)(i - r * nv) * 8;
     float av[8], o[8];
     Vec8<T>::load(a + r * lda + c, av);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = act_apply(act, av[e]);
+    FOR8(e) o[e] = act_apply(act, av[e]);
     if (b) {
       float bv[8];
       Vec8<T>::load(b + r * ldb + c, bv);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] *= bv[e];
+      FOR8(e) o[e] *= bv[e];
     }
     Vec8<T>::store(y + r * ldy + c, o);
   }
@@ -181,8 +166,7 @@ __global__ void __launch_bounds__(256) act_bwd_kernel(int act, const T* __restri
     float g[8], p[8], o[8];
     Vec8<T>::load(dy + i * 8, g);
     Vec8<T>::load(pre + i * 8, p);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = g[e] * act_grad(act, p[e]);
+    FOR8(e) o[e] = g[e] * act_grad(act, p[e]);
     Vec8<T>::store(dx + i * 8, o);
   }
 }
@@ -201,12 +185,10 @@ __global__ void __launch_bounds__(256) token_mean_kernel(const T* __restrict__ x
     for (int t = tg; t < Tn; t += 32) {
       float v[8];
       Vec8<T>::load(x + ((int64_t)b * Tn + t) * D + c0, v);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) acc[e] += v[e];
+      FOR8(e) acc[e] += v[e];
     }
   }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) red[tg][cl * 8 + e] = acc[e];
+  FOR8(e) red[tg][cl * 8 + e] = acc[e];
   __syncthreads();
   const int col = blockIdx.x * 64 + threadIdx.x;
   if (threadIdx.x < 64 && col < D) {
@@ -231,8 +213,7 @@ __global__ void __launch_bounds__(256) token_mean_bwd_kernel(const T* __restrict
     float gv[8], a[8];
     Vec8<T>::load(g + b * D + c, gv);
     load8f(acc + row * D + c, a);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) a[e] += gv[e] * inv;
+    FOR8(e) a[e] += gv[e] * inv;
     Vec8<float>::store(acc + row * D + c, a);
   }
 }
@@ -311,8 +292,7 @@ __global__ void __launch_bounds__(256) embed_splice_bwd_kernel(const T* __restri
       if (j < side) {
         Vec8<T>::store(dfeat + ((int64_t)b * side * side + i * side + j) * H + c * 8, v);
       } else if (dnew_part) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) dnew_part[(int64_t)blockIdx.x * H + c * 8 + e] = v[e];
+        FOR8(e) dnew_part[(int64_t)blockIdx.x * H + c * 8 + e] = v[e];
       }
     }
   }
@@ -422,8 +402,7 @@ __global__ void __launch_bounds__(256) resample_kernel(const T* __restrict__ in,
     Vec8<T>::load(base + ((int64_t)y1 * Wi + x0) * ld_in, v10);
     Vec8<T>::load(base + ((int64_t)y1 * Wi + x1) * ld_in, v11);
     const float hy = 1.f - ly, hx = 1.f - lx;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = hy * (hx * v00[e] + lx * v01[e]) + ly * (hx * v10[e] + lx * v11[e]);
+    FOR8(e) o[e] = hy * (hx * v00[e] + lx * v01[e]) + ly * (hx * v10[e] + lx * v11[e]);
     Vec8<T>::store(out + b * bs_out + ((int64_t)oy * Wo + ox) * ld_out + cv * 8, o);
   }
 }
@@ -462,8 +441,7 @@ __global__ void __launch_bounds__(256) resample_bwd_kernel(const T* __restrict__
           const float w = wy * cmb_resample_weight(ox, sx, Wi, ix);
           float g[8];
           Vec8<T>::load(base + ((int64_t)oy * Wo + ox) * ld_dout, g);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc[e] += w * g[e];
+          FOR8(e) acc[e] += w * g[e];
         }
       }
     }
@@ -472,11 +450,6 @@ __global__ void __launch_bounds__(256) resample_bwd_kernel(const T* __restrict__
 }
 
 }  // namespace
-
-#define DT_SWITCH(dtype, ...)                                   \
-  if ((dtype) == CMB_BF16) { typedef bf16_t T; __VA_ARGS__; }   \
-  else if ((dtype) == CMB_F32) { typedef float T; __VA_ARGS__; } \
-  else return CMB_ERR_BAD_ARG;
 
 extern "C" int cmb_transpose(int dtype, const void* in, int64_t R, int64_t C, int64_t ld_in, void* out,
                              int64_t R_pad, void* stream) {

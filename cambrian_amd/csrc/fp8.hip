@@ -6,6 +6,7 @@
 // with v_cvt_pk_fp8_f32 in OCP mode (e4m3fn, round to nearest even); values are clamped to +-448 first so the cast
 // can never overflow to NaN.
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -79,12 +80,8 @@ extern "C" int cmb_quantize_fp8_rows(int dtype, const void* x, int64_t ldx, int6
   const int64_t es = dtype == CMB_BF16 ? 2 : 4;
   if (!cmb_aligned16(x) || !cmb_aligned16(q) || (ldx * es) % 16 != 0) return CMB_ERR_ALIGNMENT;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CMB_BF16)
-    hipLaunchKernelGGL(quantize_fp8_rows_kernel<bf16_t>, dim3((unsigned)rows), dim3(Q_THREADS), 0, s, (const bf16_t*)x,
-                       ldx, (int)K, (uint8_t*)q, ldq, inv_scale);
-  else
-    hipLaunchKernelGGL(quantize_fp8_rows_kernel<float>, dim3((unsigned)rows), dim3(Q_THREADS), 0, s, (const float*)x, ldx,
-                       (int)K, (uint8_t*)q, ldq, inv_scale);
+  DT_SWITCH(dtype, hipLaunchKernelGGL(quantize_fp8_rows_kernel<T>, dim3((unsigned)rows), dim3(Q_THREADS), 0, s, (const T*)x, ldx,
+                                      (int)K, (uint8_t*)q, ldq, inv_scale));
   CMB_CHECK_LAUNCH();
   return CMB_OK;
 }

@@ -6,6 +6,7 @@
 //   * SwiGLU gate: h = silu(g) * u and its backward (dg, du) in one pass each.
 // Roofline class: HBM (one wave-instruction = 1 KiB contiguous; fp32 math).
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -28,8 +29,7 @@ __global__ void __launch_bounds__(256) ce_fwd_kernel(const T* __restrict__ logit
     for (int e = 1; e < 8; ++e) vm = fmaxf(vm, v[e]);
     const float mn = fmaxf(m, vm);
     float acc = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc += cmb_exp(v[e] - mn);
+    FOR8(e) acc += cmb_exp(v[e] - mn);
     s = s * cmb_exp(m - mn) + acc;
     m = mn;
   }
@@ -78,14 +78,11 @@ __global__ void __launch_bounds__(256) ce_bwd_kernel(const T* logits, int64_t ld
   for (int i = threadIdx.x; i < nv; i += 256) {
     float v[8];
     Vec8<T>::load(x + i * 8, v);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = cmb_exp(v[e] - l);
+    FOR8(e) v[e] = cmb_exp(v[e] - l);
     if (i == lab_vec) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] -= (e == lab_e) ? 1.f : 0.f;
+      FOR8(e) v[e] -= (e == lab_e) ? 1.f : 0.f;
     }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] *= sc;
+    FOR8(e) v[e] *= sc;
     Vec8<T>::store(d + i * 8, v);
   }
   for (int i = nv * 8 + threadIdx.x; i < V; i += 256)
@@ -106,8 +103,7 @@ __global__ void __launch_bounds__(256) swiglu_bwd_kernel(const T* __restrict__ d
     Vec8<T>::load(dh + r * lddh + c, hv);
     Vec8<T>::load(g + r * ldg + c, gv);
     Vec8<T>::load(u + r * ldu + c, uv);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
+    FOR8(e) {
       const float sg = cmb_sigmoid(gv[e]);
       const float silu = gv[e] * sg;
       ou[e] = hv[e] * silu;
@@ -150,8 +146,7 @@ __global__ void __launch_bounds__(256) qkv_rope_kernel(T* __restrict__ packed, c
         float c[8], sn[8], oa[8], ob[8];
         load8f(ct + gi * 8, c);
         load8f(st + gi * 8, sn);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
+        FOR8(e) {
           const float s_ = MERGE ? -sn[e] : sn[e];
           oa[e] = a[e] * c[e] - bb[e] * s_;
           ob[e] = bb[e] * c[e] + a[e] * s_;
@@ -175,12 +170,8 @@ extern "C" int cmb_cross_entropy_fwd(int dtype, const void* logits, int64_t rows
   if (rows == 0) return CMB_OK;
   const bool vec = cmb_aligned16(logits) && (ld * (dtype == CMB_BF16 ? 2 : 4)) % 16 == 0;
   hipStream_t s = (hipStream_t)stream;
-#define CE_FWD(T, VEC)                                                                                              \
-  hipLaunchKernelGGL((ce_fwd_kernel<T, VEC>), dim3((unsigned)rows), dim3(256), 0, s, (const T*)logits, ld, (int)V, \
-                     labels, ignore_index, lse, loss)
-  if (dtype == CMB_BF16) { if (vec) CE_FWD(bf16_t, true); else CE_FWD(bf16_t, false); }
-  else { if (vec) CE_FWD(float, true); else CE_FWD(float, false); }
-#undef CE_FWD
+  DT_SWITCH(dtype, BOOL_SWITCH(vec, VEC, hipLaunchKernelGGL((ce_fwd_kernel<T, VEC>), dim3((unsigned)rows), dim3(256), 0, s,
+                                                            (const T*)logits, ld, (int)V, labels, ignore_index, lse, loss)));
   CMB_CHECK_LAUNCH();
   return CMB_OK;
 }
@@ -194,12 +185,9 @@ extern "C" int cmb_cross_entropy_bwd(int dtype, const void* logits, int64_t rows
   const int64_t es = dtype == CMB_BF16 ? 2 : 4;
   const bool vec = cmb_aligned16(logits) && cmb_aligned16(dlogits) && (ld * es) % 16 == 0 && (ldd * es) % 16 == 0;
   hipStream_t s = (hipStream_t)stream;
-#define CE_BWD(T, VEC)                                                                                              \
-  hipLaunchKernelGGL((ce_bwd_kernel<T, VEC>), dim3((unsigned)rows), dim3(256), 0, s, (const T*)logits, ld, (int)V, \
-                     labels, ignore_index, lse, scale, (T*)dlogits, ldd)
-  if (dtype == CMB_BF16) { if (vec) CE_BWD(bf16_t, true); else CE_BWD(bf16_t, false); }
-  else { if (vec) CE_BWD(float, true); else CE_BWD(float, false); }
-#undef CE_BWD
+  DT_SWITCH(dtype, BOOL_SWITCH(vec, VEC, hipLaunchKernelGGL((ce_bwd_kernel<T, VEC>), dim3((unsigned)rows), dim3(256), 0, s,
+                                                            (const T*)logits, ld, (int)V, labels, ignore_index, lse, scale,
+                                                            (T*)dlogits, ldd)));
   CMB_CHECK_LAUNCH();
   return CMB_OK;
 }
@@ -209,16 +197,9 @@ extern "C" int cmb_swiglu_bwd(int dtype, const void* dh, int64_t lddh, const voi
   if (!dh || !g || !u || !dg || !du || rows < 0 || D <= 0 || (D & 7)) return CMB_ERR_BAD_ARG;
   if (rows == 0) return CMB_OK;
   hipStream_t s = (hipStream_t)stream;
-  int64_t blocks = (rows * (D >> 3) + 255) / 256;
-  if (blocks > 65535) blocks = 65535;
-  if (dtype == CMB_BF16)
-    hipLaunchKernelGGL(swiglu_bwd_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, s, (const bf16_t*)dh, lddh,
-                       (const bf16_t*)g, ldg, (const bf16_t*)u, ldu, rows, (int)D, (bf16_t*)dg, lddg, (bf16_t*)du, lddu);
-  else if (dtype == CMB_F32)
-    hipLaunchKernelGGL(swiglu_bwd_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, (const float*)dh, lddh,
-                       (const float*)g, ldg, (const float*)u, ldu, rows, (int)D, (float*)dg, lddg, (float*)du, lddu);
-  else
-    return CMB_ERR_BAD_ARG;
+  DT_SWITCH(dtype, hipLaunchKernelGGL(swiglu_bwd_kernel<T>, dim3(grid_for(rows * (D >> 3), 256, 65535)), dim3(256), 0, s,
+                                      (const T*)dh, lddh, (const T*)g, ldg, (const T*)u, ldu, rows, (int)D, (T*)dg, lddg,
+                                      (T*)du, lddu));
   CMB_CHECK_LAUNCH();
   return CMB_OK;
 }
@@ -230,14 +211,9 @@ extern "C" int cmb_qkv_rope(int dtype, int32_t merge, void* packed, const float*
   if (B == 0) return CMB_OK;
   hipStream_t s = (hipStream_t)stream;
   const int64_t ntok = B * S;
-  const int64_t blocks = ntok > 65535 ? 65535 : ntok;
-#define QKV(T, M)                                                                                                  \
-  hipLaunchKernelGGL((qkv_rope_kernel<T, M>), dim3((unsigned)blocks), dim3(256), 0, s, (T*)packed, cos_t, sin_t, ntok, \
-                     (int)S, nh, nkv, Dh, (T*)q, (T*)k, (T*)v)
-  if (dtype == CMB_BF16) { if (merge) QKV(bf16_t, true); else QKV(bf16_t, false); }
-  else if (dtype == CMB_F32) { if (merge) QKV(float, true); else QKV(float, false); }
-  else return CMB_ERR_BAD_ARG;
-#undef QKV
+  DT_SWITCH(dtype, BOOL_SWITCH(merge, MERGE, hipLaunchKernelGGL((qkv_rope_kernel<T, MERGE>), dim3(grid_for(ntok, 1, 65535)),
+                                                                dim3(256), 0, s, (T*)packed, cos_t, sin_t, ntok, (int)S, nh,
+                                                                nkv, Dh, (T*)q, (T*)k, (T*)v)));
   CMB_CHECK_LAUNCH();
   return CMB_OK;
 }

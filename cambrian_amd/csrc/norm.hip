@@ -2,7 +2,9 @@
 // one wave (64 lanes) owns one row, 16-byte (bf16) / 32-byte (fp32) vector accesses, the row is
 // held in registers between the statistics pass and the normalisation pass (one HBM read, one
 // write per element), fp32 math throughout.
+#include <type_traits>
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -45,57 +47,39 @@ __global__ void __launch_bounds__(256) layernorm_fwd_kernel(
     const T* xr = x + row * ldx;
     const float* ar = add ? add + (int64_t)window_pos((uint32_t)row, side, grid_r) * D : nullptr;
     float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-        Vec8<T>::load(xr + vi * 8, v[c]);
-        if (ar) {
-          float a[8];
-          load8f(ar + vi * 8, a);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[c][e] += a[e];
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += v[c][e];
+    FOR_ROW_CHUNKS(c, vi) {
+      Vec8<T>::load(xr + vi * 8, v[c]);
+      if (ar) {
+        float a[8];
+        load8f(ar + vi * 8, a);
+        FOR8(e) v[c][e] += a[e];
       }
+      FOR8(e) s += v[c][e];
     }
     const float mean = wave_sum(s) / (float)D;
     float q = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float d = v[c][e] - mean;
-          q += d * d;
-        }
+    FOR_ROW_CHUNKS(c, vi) {
+      FOR8(e) {
+        const float d = v[c][e] - mean;
+        q += d * d;
       }
     }
     const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
     T* yr = y + row * ldy;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-        float o[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (v[c][e] - mean) * rstd;
-        if (gamma) {
-          if constexpr (kHoist) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = o[e] * gg[c][e] + bb[c][e];
-          } else {
-            float g8[8], b8[8];
-            load8f(gamma + vi * 8, g8);
-            load8f(beta + vi * 8, b8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = o[e] * g8[e] + b8[e];
-          }
+    FOR_ROW_CHUNKS(c, vi) {
+      float o[8];
+      FOR8(e) o[e] = (v[c][e] - mean) * rstd;
+      if (gamma) {
+        if constexpr (kHoist) {
+          FOR8(e) o[e] = o[e] * gg[c][e] + bb[c][e];
+        } else {
+          float g8[8], b8[8];
+          load8f(gamma + vi * 8, g8);
+          load8f(beta + vi * 8, b8);
+          FOR8(e) o[e] = o[e] * g8[e] + b8[e];
         }
-        Vec8<T>::store(yr + vi * 8, o);
       }
+      Vec8<T>::store(yr + vi * 8, o);
     }
     if (lane == 0) {
       if (mean_out) mean_out[row] = mean;
@@ -130,11 +114,7 @@ __global__ void __launch_bounds__(256) layernorm_fwd_multi_kernel(const T* __res
   auto fetch = [&](int64_t row) {
     if (row < rows) {
       const T* xr = x + row * ldx;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int vi = lane + c * 64;
-        if (vi < nvec) Vec8<T>::load(xr + vi * 8, nxt[c]);
-      }
+      FOR_ROW_CHUNKS(c, vi) Vec8<T>::load(xr + vi * 8, nxt[c]);
     }
   };
   fetch(wave_global);
@@ -142,54 +122,36 @@ __global__ void __launch_bounds__(256) layernorm_fwd_multi_kernel(const T* __res
     float xv[NCH][8];
 #pragma unroll
     for (int c = 0; c < NCH; ++c)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) xv[c][e] = nxt[c][e];
+      FOR8(e) xv[c][e] = nxt[c][e];
     fetch(row + nwaves);
     const int wp = window_pos((uint32_t)row, side, grid_r);
     for (int l = 0; l < mp.layers; ++l) {
       const float* ar = mp.add[l] ? mp.add[l] + (int64_t)wp * D : nullptr;
       float v[NCH][8];
       float s = 0.f;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int vi = lane + c * 64;
-        if (vi < nvec) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[c][e] = xv[c][e];
-          if (ar) {
-            float a[8];
-            load8f(ar + vi * 8, a);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[c][e] += a[e];
-          }
-#pragma unroll
-          for (int e = 0; e < 8; ++e) s += v[c][e];
+      FOR_ROW_CHUNKS(c, vi) {
+        FOR8(e) v[c][e] = xv[c][e];
+        if (ar) {
+          float a[8];
+          load8f(ar + vi * 8, a);
+          FOR8(e) v[c][e] += a[e];
         }
+        FOR8(e) s += v[c][e];
       }
       const float mean = wave_sum(s) / (float)D;
       float q = 0.f;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int vi = lane + c * 64;
-        if (vi < nvec) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float d = v[c][e] - mean;
-            q += d * d;
-          }
+      FOR_ROW_CHUNKS(c, vi) {
+        FOR8(e) {
+          const float d = v[c][e] - mean;
+          q += d * d;
         }
       }
       const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
       T* yr = (T*)mp.y[l] + row * (int64_t)D;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int vi = lane + c * 64;
-        if (vi < nvec) {
-          float o[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = (v[c][e] - mean) * rstd;
-          Vec8<T>::store(yr + vi * 8, o);
-        }
+      FOR_ROW_CHUNKS(c, vi) {
+        float o[8];
+        FOR8(e) o[e] = (v[c][e] - mean) * rstd;
+        Vec8<T>::store(yr + vi * 8, o);
       }
       if (lane == 0) {
         mp.mean[l][row] = mean;
@@ -213,8 +175,7 @@ template <> struct Raw8<bf16_t> {
   bf16x8_t v;
   __device__ __forceinline__ void load(const bf16_t* p) { v = *reinterpret_cast<const bf16x8_t*>(p); }
   __device__ __forceinline__ void get(float (&o)[8]) const {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o[i] = (float)v[i];
+    FOR8(i) o[i] = (float)v[i];
   }
 };
 template <> struct Raw8<float> {
@@ -250,58 +211,35 @@ __global__ void __launch_bounds__(256) layernorm_fwd_lds_kernel(
   Raw8<T> cur[NCH], nxt[NCH];
   int64_t row = wave_global;
   if (row < rows) {
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) cur[c].load(x + row * ldx + vi * 8);
-    }
+    FOR_ROW_CHUNKS(c, vi) cur[c].load(x + row * ldx + vi * 8);
   }
   for (; row < rows; row += nwaves) {
     const int64_t nrow = row + nwaves;
     if (nrow < rows) {
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int vi = lane + c * 64;
-        if (vi < nvec) nxt[c].load(x + nrow * ldx + vi * 8);
-      }
+      FOR_ROW_CHUNKS(c, vi) nxt[c].load(x + nrow * ldx + vi * 8);
     }
     float v[NCH][8];
     float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-        cur[c].get(v[c]);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += v[c][e];
-      }
+    FOR_ROW_CHUNKS(c, vi) {
+      cur[c].get(v[c]);
+      FOR8(e) s += v[c][e];
     }
     const float mean = wave_sum(s) / (float)D;
     float q = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float d = v[c][e] - mean;
-          q += d * d;
-        }
+    FOR_ROW_CHUNKS(c, vi) {
+      FOR8(e) {
+        const float d = v[c][e] - mean;
+        q += d * d;
       }
     }
     const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
     T* yr = y + row * ldy;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-        float o[8], g8[8], b8[8];
-        load8f(ln_sm + vi * 8, g8);
-        load8f(ln_sm + D + vi * 8, b8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (v[c][e] - mean) * rstd * g8[e] + b8[e];
-        Vec8<T>::store(yr + vi * 8, o);
-      }
+    FOR_ROW_CHUNKS(c, vi) {
+      float o[8], g8[8], b8[8];
+      load8f(ln_sm + vi * 8, g8);
+      load8f(ln_sm + D + vi * 8, b8);
+      FOR8(e) o[e] = (v[c][e] - mean) * rstd * g8[e] + b8[e];
+      Vec8<T>::store(yr + vi * 8, o);
     }
     if (lane == 0) {
       if (mean_out) mean_out[row] = mean;
@@ -325,43 +263,25 @@ __global__ void __launch_bounds__(256) row_stats_kernel(const T* __restrict__ x,
   Raw8<T> cur[NCH], nxt[NCH];
   int64_t row = wave_global;
   if (row < rows) {
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) cur[c].load(x + row * ldx + vi * 8);
-    }
+    FOR_ROW_CHUNKS(c, vi) cur[c].load(x + row * ldx + vi * 8);
   }
   for (; row < rows; row += nwaves) {
     const int64_t nrow = row + nwaves;
     if (nrow < rows) {
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int vi = lane + c * 64;
-        if (vi < nvec) nxt[c].load(x + nrow * ldx + vi * 8);
-      }
+      FOR_ROW_CHUNKS(c, vi) nxt[c].load(x + nrow * ldx + vi * 8);
     }
     float v[NCH][8];
     float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-        cur[c].get(v[c]);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += v[c][e];
-      }
+    FOR_ROW_CHUNKS(c, vi) {
+      cur[c].get(v[c]);
+      FOR8(e) s += v[c][e];
     }
     const float mean = wave_sum(s) / (float)D;
     float q = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float d = v[c][e] - mean;
-          q += d * d;
-        }
+    FOR_ROW_CHUNKS(c, vi) {
+      FOR8(e) {
+        const float d = v[c][e] - mean;
+        q += d * d;
       }
     }
     const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
@@ -402,8 +322,7 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(
   float pg[NCH][8], pb[NCH][8], pa[NCH][8];
 #pragma unroll
   for (int c = 0; c < NCH; ++c)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { pg[c][e] = 0.f; pb[c][e] = 0.f; pa[c][e] = 0.f; }
+    FOR8(e) { pg[c][e] = 0.f; pb[c][e] = 0.f; pa[c][e] = 0.f; }
 
   const int64_t wave_global = (int64_t)blockIdx.x * 4 + wave;
   const int64_t nwaves = (int64_t)gridDim.x * 4;
@@ -422,70 +341,53 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(
     const T* dyr = dy + row * lddy;
     float xh[NCH][8], g[NCH][8];
     float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-        float xv[8], dv[8];
-        Vec8<T>::load(xr + vi * 8, xv);
-        Vec8<T>::load(dyr + vi * 8, dv);
-        if (ar) {
-          float a[8];
-          load8f(ar + vi * 8, a);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) xv[e] += a[e];
+    FOR_ROW_CHUNKS(c, vi) {
+      float xv[8], dv[8];
+      Vec8<T>::load(xr + vi * 8, xv);
+      Vec8<T>::load(dyr + vi * 8, dv);
+      if (ar) {
+        float a[8];
+        load8f(ar + vi * 8, a);
+        FOR8(e) xv[e] += a[e];
+      }
+      float gg[8];
+      if (gamma) load8f(gamma + vi * 8, gg);
+      FOR8(e) {
+        xh[c][e] = (xv[e] - mean) * rstd;
+        if (gamma) {
+          pg[c][e] += dv[e] * xh[c][e];
+          pb[c][e] += dv[e];
+          g[c][e] = dv[e] * gg[e];
+        } else {
+          g[c][e] = dv[e];
         }
-        float gg[8];
-        if (gamma) load8f(gamma + vi * 8, gg);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          xh[c][e] = (xv[e] - mean) * rstd;
-          if (gamma) {
-            pg[c][e] += dv[e] * xh[c][e];
-            pb[c][e] += dv[e];
-            g[c][e] = dv[e] * gg[e];
-          } else {
-            g[c][e] = dv[e];
-          }
-          s1 += g[c][e];
-          s2 += g[c][e] * xh[c][e];
-        }
+        s1 += g[c][e];
+        s2 += g[c][e] * xh[c][e];
       }
     }
     const float c1 = wave_sum(s1) / (float)D;
     const float c2 = wave_sum(s2) / (float)D;
     TDx* dxr = dx + row * lddx;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-        float o[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          o[e] = (g[c][e] - c1 - xh[c][e] * c2) * rstd;
-          pa[c][e] += o[e];
-        }
-        if (ACCUM) {
-          float old[8];
-          Vec8<TDx>::load(dxr + vi * 8, old);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] += old[e];
-        }
-        Vec8<TDx>::store(dxr + vi * 8, o);
+    FOR_ROW_CHUNKS(c, vi) {
+      float o[8];
+      FOR8(e) {
+        o[e] = (g[c][e] - c1 - xh[c][e] * c2) * rstd;
+        pa[c][e] += o[e];
       }
+      if (ACCUM) {
+        float old[8];
+        Vec8<TDx>::load(dxr + vi * 8, old);
+        FOR8(e) o[e] += old[e];
+      }
+      Vec8<TDx>::store(dxr + vi * 8, o);
     }
   }
 
   // block-level combine of the partial sums, one quantity at a time through sred[4][D], into this block's partial row
   auto combine = [&](float (&part)[NCH][8], float* row) {
     __syncthreads();
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sred[wave * D + vi * 8 + e] = part[c][e];
-      }
+    FOR_ROW_CHUNKS(c, vi) {
+      FOR8(e) sred[wave * D + vi * 8 + e] = part[c][e];
     }
     __syncthreads();
     for (int col = threadIdx.x; col < D; col += 256)
@@ -539,8 +441,7 @@ layernorm_bwd_multi_kernel(const T* __restrict__ x, int64_t ldx, int64_t rows, i
   for (int l = 0; l < LC; ++l)
 #pragma unroll
     for (int c = 0; c < NCH; ++c)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) pa[l][c][e] = 0.f;
+      FOR8(e) pa[l][c][e] = 0.f;
   const int64_t wave_global = (int64_t)blockIdx.x * 4 + wave;
   const int64_t nwaves = (int64_t)gridDim.x * 4;
   for (int64_t w = wave_global; w < nwin; w += nwaves) {
@@ -559,23 +460,14 @@ layernorm_bwd_multi_kernel(const T* __restrict__ x, int64_t ldx, int64_t rows, i
 #pragma unroll
     for (int l = 0; l < LC; ++l) {
       if (l < mp.layers) {
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          const int vi = lane + c * 64;
-          if (vi < nvec) raw[l][c].load(reinterpret_cast<const T*>(mp.dy[l]) + row * (int64_t)D + vi * 8);
-        }
+        FOR_ROW_CHUNKS(c, vi) raw[l][c].load(reinterpret_cast<const T*>(mp.dy[l]) + row * (int64_t)D + vi * 8);
       }
     }
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-        Vec8<T>::load(x + row * ldx + vi * 8, xv[c]);
-        if (ACCUM) load8f(dx + row * lddx + vi * 8, acc[c]);
-        else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc[c][e] = 0.f;
-        }
+    FOR_ROW_CHUNKS(c, vi) {
+      Vec8<T>::load(x + row * ldx + vi * 8, xv[c]);
+      if (ACCUM) load8f(dx + row * lddx + vi * 8, acc[c]);
+      else {
+        FOR8(e) acc[c][e] = 0.f;
       }
     }
 #pragma unroll
@@ -585,44 +477,30 @@ layernorm_bwd_multi_kernel(const T* __restrict__ x, int64_t ldx, int64_t rows, i
         const float* ar = mp.add[l] ? mp.add[l] + (int64_t)pos * D : nullptr;
         float xh[NCH][8], g[NCH][8];
         float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          const int vi = lane + c * 64;
-          if (vi < nvec) {
-            raw[l][c].get(g[c]);
-            float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if (ar) load8f(ar + vi * 8, a);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              xh[c][e] = (xv[c][e] + a[e] - mean) * rstd;
-              s1 += g[c][e];
-              s2 += g[c][e] * xh[c][e];
-            }
+        FOR_ROW_CHUNKS(c, vi) {
+          raw[l][c].get(g[c]);
+          float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+          if (ar) load8f(ar + vi * 8, a);
+          FOR8(e) {
+            xh[c][e] = (xv[c][e] + a[e] - mean) * rstd;
+            s1 += g[c][e];
+            s2 += g[c][e] * xh[c][e];
           }
         }
         const float c1 = wave_sum(s1) / (float)D;
         const float c2 = wave_sum(s2) / (float)D;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          const int vi = lane + c * 64;
-          if (vi < nvec) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const float o = (g[c][e] - c1 - xh[c][e] * c2) * rstd;
-              acc[c][e] += o;
-              pa[l][c][e] += o;
-            }
+        FOR_ROW_CHUNKS(c, vi) {
+          FOR8(e) {
+            const float o = (g[c][e] - c1 - xh[c][e] * c2) * rstd;
+            acc[c][e] += o;
+            pa[l][c][e] += o;
           }
         }
       }
     }
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-        if (mp.dx_out) Vec8<T>::store(reinterpret_cast<T*>(mp.dx_out) + row * (int64_t)D + vi * 8, acc[c]);   // (block-uniform)
-        else Vec8<float>::store(dx + row * lddx + vi * 8, acc[c]);
-      }
+    FOR_ROW_CHUNKS(c, vi) {
+      if (mp.dx_out) Vec8<T>::store(reinterpret_cast<T*>(mp.dx_out) + row * (int64_t)D + vi * 8, acc[c]);   // (block-uniform)
+      else Vec8<float>::store(dx + row * lddx + vi * 8, acc[c]);
     }
   }
   // block-level combine of each layer's partial sums through sred[4][D] into the workgroup's partial row of mp.dadd[l]
@@ -631,13 +509,8 @@ layernorm_bwd_multi_kernel(const T* __restrict__ x, int64_t ldx, int64_t rows, i
   for (int l = 0; l < LC; ++l) {
     if (l < mp.layers && mp.add[l] && mp.dadd[l]) {   // block-uniform
       __syncthreads();
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        const int vi = lane + c * 64;
-        if (vi < nvec) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) sred[wave * D + vi * 8 + e] = pa[l][c][e];
-        }
+      FOR_ROW_CHUNKS(c, vi) {
+        FOR8(e) sred[wave * D + vi * 8 + e] = pa[l][c][e];
       }
       __syncthreads();
       float* row = mp.dadd[l] + ((int64_t)blockIdx.x * gridDim.y + pos) * D;
@@ -662,27 +535,17 @@ __global__ void __launch_bounds__(256) rmsnorm_fwd_kernel(const T* __restrict__ 
     float v[NCH][8];
     const T* xr = x + row * (int64_t)D;
     float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-        Vec8<T>::load(xr + vi * 8, v[c]);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += v[c][e] * v[c][e];
-      }
+    FOR_ROW_CHUNKS(c, vi) {
+      Vec8<T>::load(xr + vi * 8, v[c]);
+      FOR8(e) s += v[c][e] * v[c][e];
     }
     const float rstd = rsqrtf(wave_sum(s) / (float)D + eps);
     T* yr = y + row * (int64_t)D;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-        float ww[8], o[8];
-        load8f(w + vi * 8, ww);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = ww[e] * (v[c][e] * rstd);
-        Vec8<T>::store(yr + vi * 8, o);
-      }
+    FOR_ROW_CHUNKS(c, vi) {
+      float ww[8], o[8];
+      load8f(w + vi * 8, ww);
+      FOR8(e) o[e] = ww[e] * (v[c][e] * rstd);
+      Vec8<T>::store(yr + vi * 8, o);
     }
     if (lane == 0 && rstd_out) rstd_out[row] = rstd;
   }
@@ -704,54 +567,38 @@ __global__ void __launch_bounds__(256) rmsnorm_bwd_kernel(const T* __restrict__ 
   float pw[HAS_DW ? NCH : 1][8];
 #pragma unroll
   for (int c = 0; c < (HAS_DW ? NCH : 1); ++c)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) pw[c][e] = 0.f;
+    FOR8(e) pw[c][e] = 0.f;
   for (int64_t row = wave_global; row < rows; row += nwaves) {
     const float rstd = rstd_in[row];
     const T* xr = x + row * (int64_t)D;
     const T* dyr = dy + row * (int64_t)D;
     float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-        float xv[8], dv[8], ww[8];
-        Vec8<T>::load(xr + vi * 8, xv);
-        Vec8<T>::load(dyr + vi * 8, dv);
-        load8f(w + vi * 8, ww);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float xh = xv[e] * rstd;
-          if (HAS_DW) pw[HAS_DW ? c : 0][e] += dv[e] * xh;
-          s += dv[e] * ww[e] * xh;
-        }
+    FOR_ROW_CHUNKS(c, vi) {
+      float xv[8], dv[8], ww[8];
+      Vec8<T>::load(xr + vi * 8, xv);
+      Vec8<T>::load(dyr + vi * 8, dv);
+      load8f(w + vi * 8, ww);
+      FOR8(e) {
+        const float xh = xv[e] * rstd;
+        if (HAS_DW) pw[HAS_DW ? c : 0][e] += dv[e] * xh;
+        s += dv[e] * ww[e] * xh;
       }
     }
     const float c2 = wave_sum(s) / (float)D;
     T* dxr = dx + row * (int64_t)D;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-        float xv[8], dv[8], ww[8], o[8];
-        Vec8<T>::load(xr + vi * 8, xv);
-        Vec8<T>::load(dyr + vi * 8, dv);
-        load8f(w + vi * 8, ww);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (dv[e] * ww[e] - xv[e] * rstd * c2) * rstd;
-        Vec8<T>::store(dxr + vi * 8, o);
-      }
+    FOR_ROW_CHUNKS(c, vi) {
+      float xv[8], dv[8], ww[8], o[8];
+      Vec8<T>::load(xr + vi * 8, xv);
+      Vec8<T>::load(dyr + vi * 8, dv);
+      load8f(w + vi * 8, ww);
+      FOR8(e) o[e] = (dv[e] * ww[e] - xv[e] * rstd * c2) * rstd;
+      Vec8<T>::store(dxr + vi * 8, o);
     }
   }
   if (HAS_DW) {
     __syncthreads();
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sred[wave * D + vi * 8 + e] = pw[HAS_DW ? c : 0][e];
-      }
+    FOR_ROW_CHUNKS(c, vi) {
+      FOR8(e) sred[wave * D + vi * 8 + e] = pw[HAS_DW ? c : 0][e];
     }
     __syncthreads();
     for (int col = threadIdx.x; col < D; col += 256) {
@@ -801,8 +648,7 @@ __global__ void __launch_bounds__(256) rope_apply_kernel(T* __restrict__ x, cons
       load8f(ct + gi * 8, c);
       load8f(st + gi * 8, s);
       float oa[8], ob[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
+      FOR8(e) {
         const float sn = inverse ? -s[e] : s[e];
         oa[e] = a[e] * c[e] - b[e] * sn;
         ob[e] = b[e] * c[e] + a[e] * sn;
@@ -830,32 +676,21 @@ __global__ void __launch_bounds__(256) add_rmsnorm_fwd_kernel(const T* __restric
     const T* rr = res + row * (int64_t)D;
     T* sr = sum + row * (int64_t)D;
     float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-        float a[8];
-        Vec8<T>::load(xr + vi * 8, v[c]);
-        Vec8<T>::load(rr + vi * 8, a);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[c][e] = (float)(T)(v[c][e] + a[e]);  // the stream is stored in T: normalise what is stored
-        Vec8<T>::store(sr + vi * 8, v[c]);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += v[c][e] * v[c][e];
-      }
+    FOR_ROW_CHUNKS(c, vi) {
+      float a[8];
+      Vec8<T>::load(xr + vi * 8, v[c]);
+      Vec8<T>::load(rr + vi * 8, a);
+      FOR8(e) v[c][e] = (float)(T)(v[c][e] + a[e]);  // the stream is stored in T: normalise what is stored
+      Vec8<T>::store(sr + vi * 8, v[c]);
+      FOR8(e) s += v[c][e] * v[c][e];
     }
     const float rstd = rsqrtf(wave_sum(s) / (float)D + eps);
     T* yr = y + row * (int64_t)D;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-        float ww[8], o[8];
-        load8f(w + vi * 8, ww);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = ww[e] * (v[c][e] * rstd);
-        Vec8<T>::store(yr + vi * 8, o);
-      }
+    FOR_ROW_CHUNKS(c, vi) {
+      float ww[8], o[8];
+      load8f(w + vi * 8, ww);
+      FOR8(e) o[e] = ww[e] * (v[c][e] * rstd);
+      Vec8<T>::store(yr + vi * 8, o);
     }
     if (lane == 0) rstd_out[row] = rstd;
   }
@@ -879,36 +714,25 @@ __global__ void __launch_bounds__(256) rmsnorm_bwd_add_kernel(const T* __restric
     const T* dyr = dy + row * (int64_t)D;
     vec_t xs[NCH], ds[NCH];
     float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-        xs[c] = *reinterpret_cast<const vec_t*>(xr + vi * 8);
-        ds[c] = *reinterpret_cast<const vec_t*>(dyr + vi * 8);
-        float ww[8];
-        load8f(w + vi * 8, ww);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += (float)ds[c][e] * ww[e] * ((float)xs[c][e] * rstd);
-      }
+    FOR_ROW_CHUNKS(c, vi) {
+      xs[c] = *reinterpret_cast<const vec_t*>(xr + vi * 8);
+      ds[c] = *reinterpret_cast<const vec_t*>(dyr + vi * 8);
+      float ww[8];
+      load8f(w + vi * 8, ww);
+      FOR8(e) s += (float)ds[c][e] * ww[e] * ((float)xs[c][e] * rstd);
     }
     const float c2 = wave_sum(s) / (float)D;
     T* dxr = dx + row * (int64_t)D;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int vi = lane + c * 64;
-      if (vi < nvec) {
-        float ww[8], o[8];
-        load8f(w + vi * 8, ww);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = ((float)ds[c][e] * ww[e] - (float)xs[c][e] * rstd * c2) * rstd;
-        if (dadd) {
-          float a[8];
-          Vec8<T>::load(dadd + row * (int64_t)D + vi * 8, a);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] += a[e];
-        }
-        Vec8<T>::store(dxr + vi * 8, o);
+    FOR_ROW_CHUNKS(c, vi) {
+      float ww[8], o[8];
+      load8f(w + vi * 8, ww);
+      FOR8(e) o[e] = ((float)ds[c][e] * ww[e] - (float)xs[c][e] * rstd * c2) * rstd;
+      if (dadd) {
+        float a[8];
+        Vec8<T>::load(dadd + row * (int64_t)D + vi * 8, a);
+        FOR8(e) o[e] += a[e];
       }
+      Vec8<T>::store(dxr + vi * 8, o);
     }
   }
 }
@@ -922,22 +746,6 @@ int nch_for(int64_t D) {
   return -1;
 }
 
-inline int row_grid(int64_t rows) {
-  int64_t blocks = (rows + 3) / 4;
-  if (blocks > 8192) blocks = 8192;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
-}
-
-#define DISPATCH_NCH(nch, ...)                \
-  switch (nch) {                              \
-    case 2: { constexpr int NCH = 2; __VA_ARGS__; break; }   \
-    case 4: { constexpr int NCH = 4; __VA_ARGS__; break; }   \
-    case 8: { constexpr int NCH = 8; __VA_ARGS__; break; }   \
-    case 16: { constexpr int NCH = 16; __VA_ARGS__; break; } \
-    default: return CMB_ERR_SHAPE;            \
-  }
-
 template <typename T>
 int ln_fwd(const void* x, int64_t rows, int64_t D, int64_t ldx, const float* add, int side, int grid_r,
            const float* gamma, const float* beta, float eps, void* y, int64_t ldy, float* mean, float* rstd,
@@ -948,19 +756,16 @@ int ln_fwd(const void* x, int64_t rows, int64_t D, int64_t ldx, const float* add
     // the towers' affine LayerNorms: parameters in LDS, next row in flight (layernorm_fwd_lds_kernel)
     // ~4 rows per wave: enough for the prefetch to run ahead, few enough that small launches still fill the chip
     // (profiles/r04_lab.md: 2048 / 4096 / 8192 / 1024-workgroup caps per shape); knob values > 1 = an explicit cap
-    int64_t blocks = (rows + 15) / 16;
-    const int64_t cap = variant > 1 ? variant : 8192;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
+    const unsigned blocks = grid_for(rows, 16, variant > 1 ? variant : 8192);
     const size_t smem = (size_t)2 * D * sizeof(float);
-    DISPATCH_NCH(nch, hipLaunchKernelGGL((layernorm_fwd_lds_kernel<T, NCH>), dim3((unsigned)blocks), dim3(256), smem, s,
+    DISPATCH_NCH(nch, hipLaunchKernelGGL((layernorm_fwd_lds_kernel<T, NCH>), dim3(blocks), dim3(256), smem, s,
                                          (const T*)x, rows, (int)D, ldx, gamma, beta, eps, (T*)y, ldy, mean, rstd));
     CMB_CHECK_LAUNCH();
     return CMB_OK;
   }
   // (a grid capped at the resident-wave capacity, 2048 workgroups, so that a wave walks more rows per parameter load was
   // measured SLOWER: 152 vs 126 us on 147456 x 1024 — fewer waves per CU hide less of the one-row-at-a-time latency)
-  DISPATCH_NCH(nch, hipLaunchKernelGGL((layernorm_fwd_kernel<T, NCH>), dim3(row_grid(rows)), dim3(256), 0, s,
+  DISPATCH_NCH(nch, hipLaunchKernelGGL((layernorm_fwd_kernel<T, NCH>), dim3(grid_for(rows, 4, 8192)), dim3(256), 0, s,
                                        (const T*)x, rows, (int)D, ldx, add, side, grid_r, gamma, beta, eps,
                                        (T*)y, ldy, mean, rstd));
   CMB_CHECK_LAUNCH();
@@ -971,18 +776,15 @@ int ln_fwd(const void* x, int64_t rows, int64_t D, int64_t ldx, const float* add
 // unless that leaves the chip mostly idle (the SVA query-side LayerNorms: 13 824 rows = 216 workgroups, 61 us = 0.16 of
 // the HBM peak, profiles/r03_hbm_kernels_table.md): then CMB_KNOB_LN_BWD_ROWS rows per workgroup (~4 rows per wave)
 static int64_t ln_bwd_blocks(int64_t nwin) {
-  int64_t blocks = (nwin + 63) / 64;
-  if (blocks < 1024) blocks = (nwin + cmb_knob(CMB_KNOB_LN_BWD_ROWS) - 1) / cmb_knob(CMB_KNOB_LN_BWD_ROWS);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  return blocks;
+  return grid_for(nwin, (nwin + 63) / 64 < 1024 ? cmb_knob(CMB_KNOB_LN_BWD_ROWS) : 64, 2048);
 }
 
-template <typename T, typename TDx, bool ACCUM>
+template <typename T, bool ACCUM>
 int ln_bwd(const void* dy, int64_t lddy, const void* x, int64_t ldx, int64_t rows, int64_t D, const float* add,
            int side, int grid_r, const float* gamma, const float* mean, const float* rstd, void* dx,
            int64_t lddx, float* dgamma, float* dbeta, float* dadd, float* workspace, int64_t workspace_floats,
            hipStream_t s) {
+  typedef std::conditional_t<ACCUM, float, T> TDx;   // the cross-layer accumulator is fp32
   const int nch = nch_for(D);
   if (nch > 8) return CMB_ERR_SHAPE;  // register budget: the backward supports D <= 4096 (ConvNeXt-XXL stage 4: 3072)
   const int npos = grid_r * grid_r;
@@ -1002,18 +804,10 @@ int ln_bwd(const void* dy, int64_t lddy, const void* x, int64_t ldx, int64_t row
   dbeta = dbeta_out ? slab : nullptr;
   if (dbeta_out) slab += slots * D;
   dadd = dadd_out ? slab : nullptr;
-  if (nch == 2)
-    hipLaunchKernelGGL((layernorm_bwd_kernel<T, TDx, 2, ACCUM>), dim3((unsigned)blocks, npos), dim3(256), smem, s,
-                       (const T*)dy, lddy, (const T*)x, ldx, rows, (int)D, add, side, grid_r, gamma, mean, rstd,
-                       (TDx*)dx, lddx, dgamma, dbeta, dadd);
-  else if (nch == 4)
-    hipLaunchKernelGGL((layernorm_bwd_kernel<T, TDx, 4, ACCUM>), dim3((unsigned)blocks, npos), dim3(256), smem, s,
-                       (const T*)dy, lddy, (const T*)x, ldx, rows, (int)D, add, side, grid_r, gamma, mean, rstd,
-                       (TDx*)dx, lddx, dgamma, dbeta, dadd);
-  else  // 2048 < D <= 4096: the per-lane partial sums spill into the AGPR half of the register file (one wave per SIMD)
-    hipLaunchKernelGGL((layernorm_bwd_kernel<T, TDx, 8, ACCUM>), dim3((unsigned)blocks, npos), dim3(256), smem, s,
-                       (const T*)dy, lddy, (const T*)x, ldx, rows, (int)D, add, side, grid_r, gamma, mean, rstd,
-                       (TDx*)dx, lddx, dgamma, dbeta, dadd);
+  // NCH = 8, 2048 < D <= 4096: the per-lane partial sums spill into the AGPR half of the register file (one wave per SIMD)
+  DISPATCH_NCH8(nch, hipLaunchKernelGGL((layernorm_bwd_kernel<T, TDx, NCH, ACCUM>), dim3((unsigned)blocks, npos), dim3(256),
+                                        smem, s, (const T*)dy, lddy, (const T*)x, ldx, rows, (int)D, add, side, grid_r,
+                                        gamma, mean, rstd, (TDx*)dx, lddx, dgamma, dbeta, dadd));
   CMB_CHECK_LAUNCH();
   if (dgamma && !det_sum(dgamma, slots, D, dgamma_out, s)) return CMB_ERR_LAUNCH;
   if (dbeta && !det_sum(dbeta, slots, D, dbeta_out, s)) return CMB_ERR_LAUNCH;
@@ -1032,12 +826,8 @@ extern "C" int cmb_layernorm_fwd(int dtype, const void* x, int64_t rows, int64_t
   if (add && (side <= 0 || grid_r <= 0 || side % grid_r)) return CMB_ERR_BAD_ARG;
   if (rows == 0) return CMB_OK;
   if (!add) { side = 1; grid_r = 1; }
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == CMB_BF16)
-    return ln_fwd<bf16_t>(x, rows, D, ldx, add, side, grid_r, gamma, beta, eps, y, ldy, mean, rstd, s);
-  if (dtype == CMB_F32)
-    return ln_fwd<float>(x, rows, D, ldx, add, side, grid_r, gamma, beta, eps, y, ldy, mean, rstd, s);
-  return CMB_ERR_BAD_ARG;
+  DT_SWITCH(dtype, return ln_fwd<T>(x, rows, D, ldx, add, side, grid_r, gamma, beta, eps, y, ldy, mean, rstd,
+                                    (hipStream_t)stream));
 }
 
 extern "C" int cmb_layernorm_fwd_multi(const cmb_ln_fwd_multi_desc* d, void* stream) {
@@ -1061,16 +851,10 @@ extern "C" int cmb_layernorm_fwd_multi(const cmb_ln_fwd_multi_desc* d, void* str
   if (!any_add) { side = 1; grid_r = 1; }
   if (d->rows == 0) return CMB_OK;
   hipStream_t s = (hipStream_t)stream;
-  int64_t blocks = (d->rows + 15) / 16;   // ~4 rows per wave, each written `layers` times
-  if (blocks > 8192) blocks = 8192;
-  const int nch = nch_for(d->D);
-  if (nch != 2) return CMB_ERR_SHAPE;
-#define LN_FWD_MULTI(T_, NCH_)                                                                                                  \
-  hipLaunchKernelGGL((layernorm_fwd_multi_kernel<T_, NCH_>), dim3((unsigned)blocks), dim3(256), 0, s, (const T_*)d->x, d->rows, \
-                     (int)d->D, d->ldx, side, grid_r, d->eps, mp)
-  if (d->dtype == CMB_BF16) LN_FWD_MULTI(bf16_t, 2);
-  else LN_FWD_MULTI(float, 2);
-#undef LN_FWD_MULTI
+  const unsigned blocks = grid_for(d->rows, 16, 8192);   // ~4 rows per wave, each written `layers` times
+  if (nch_for(d->D) != 2) return CMB_ERR_SHAPE;
+  DT_SWITCH(d->dtype, hipLaunchKernelGGL((layernorm_fwd_multi_kernel<T, 2>), dim3(blocks), dim3(256), 0, s, (const T*)d->x,
+                                         d->rows, (int)d->D, d->ldx, side, grid_r, d->eps, mp));
   CMB_CHECK_LAUNCH();
   return CMB_OK;
 }
@@ -1081,17 +865,9 @@ extern "C" int cmb_row_stats(int dtype, const void* x, int64_t rows, int64_t D, 
   if (rows == 0) return CMB_OK;
   hipStream_t s = (hipStream_t)stream;
   const int nch = nch_for(D);
-  int64_t blocks = (rows + 15) / 16;   // ~4 rows per wave (as layernorm_fwd_lds_kernel's launch)
-  if (blocks > 8192) blocks = 8192;
-  if (dtype == CMB_BF16) {
-    DISPATCH_NCH(nch, hipLaunchKernelGGL((row_stats_kernel<bf16_t, NCH>), dim3((unsigned)blocks), dim3(256), 0, s, (const bf16_t*)x,
-                                         rows, (int)D, ldx, eps, mean, rstd));
-  } else if (dtype == CMB_F32) {
-    DISPATCH_NCH(nch, hipLaunchKernelGGL((row_stats_kernel<float, NCH>), dim3((unsigned)blocks), dim3(256), 0, s, (const float*)x,
-                                         rows, (int)D, ldx, eps, mean, rstd));
-  } else {
-    return CMB_ERR_BAD_ARG;
-  }
+  const unsigned blocks = grid_for(rows, 16, 8192);   // ~4 rows per wave (as layernorm_fwd_lds_kernel's launch)
+  DT_SWITCH(dtype, DISPATCH_NCH(nch, hipLaunchKernelGGL((row_stats_kernel<T, NCH>), dim3(blocks), dim3(256), 0, s, (const T*)x,
+                                                        rows, (int)D, ldx, eps, mean, rstd)));
   CMB_CHECK_LAUNCH();
   return CMB_OK;
 }
@@ -1108,22 +884,9 @@ extern "C" int cmb_layernorm_bwd(int dtype, const void* dy, int64_t lddy, const 
   if (rows == 0) return CMB_OK;
   if (!add) { side = 1; grid_r = 1; }
   if (add && rows % ((int64_t)side * side)) return CMB_ERR_SHAPE;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == CMB_BF16) {
-    if (dx_accumulate)
-      return ln_bwd<bf16_t, float, true>(dy, lddy, x, ldx, rows, D, add, side, grid_r, gamma, mean, rstd, dx,
-                                         lddx, dgamma, dbeta, dadd, workspace, workspace_floats, s);
-    return ln_bwd<bf16_t, bf16_t, false>(dy, lddy, x, ldx, rows, D, add, side, grid_r, gamma, mean, rstd, dx,
-                                         lddx, dgamma, dbeta, dadd, workspace, workspace_floats, s);
-  }
-  if (dtype == CMB_F32) {
-    if (dx_accumulate)
-      return ln_bwd<float, float, true>(dy, lddy, x, ldx, rows, D, add, side, grid_r, gamma, mean, rstd, dx,
-                                        lddx, dgamma, dbeta, dadd, workspace, workspace_floats, s);
-    return ln_bwd<float, float, false>(dy, lddy, x, ldx, rows, D, add, side, grid_r, gamma, mean, rstd, dx,
-                                       lddx, dgamma, dbeta, dadd, workspace, workspace_floats, s);
-  }
-  return CMB_ERR_BAD_ARG;
+  DT_SWITCH(dtype, BOOL_SWITCH(dx_accumulate, ACCUM,
+                               return ln_bwd<T, ACCUM>(dy, lddy, x, ldx, rows, D, add, side, grid_r, gamma, mean, rstd, dx, lddx,
+                                                       dgamma, dbeta, dadd, workspace, workspace_floats, (hipStream_t)stream)));
 }
 
 extern "C" int64_t cmb_layernorm_bwd_workspace(int64_t rows, int64_t D, int32_t grid_r) {
@@ -1134,12 +897,7 @@ extern "C" int64_t cmb_layernorm_bwd_workspace(int64_t rows, int64_t D, int32_t 
 
 // workgroups along the windows (~8 rows per wave: amortises the end-of-workgroup combine) and layers per launch
 // (CMB_KNOB_LN_MULTI_CHUNK, 4 ... 7; <= 6: two waves per SIMD) of cmb_layernorm_bwd_multi
-static int64_t ln_multi_blocks(int64_t nwin) {
-  int64_t blocks = (nwin + 31) / 32;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  return blocks;
-}
+static int64_t ln_multi_blocks(int64_t nwin) { return grid_for(nwin, 32, 2048); }
 static int ln_multi_chunk() {
   const int k = cmb_knob(CMB_KNOB_LN_MULTI_CHUNK);
   return (k < 4 || k > 7) ? 4 : k;
@@ -1196,20 +954,20 @@ extern "C" int cmb_layernorm_bwd_multi(const cmb_ln_multi_desc* d, void* stream)
       mp.dadd[l] = (on && d->add[l0 + l] && d->dadd[l0 + l]) ? d->workspace + (int64_t)l * blocks * npos * d->D : nullptr;
     }
     const bool acc = d->accumulate || l0 > 0;
-#define LN_MULTI_LAUNCH(T_, ACC_, LC_)                                                                                  \
-  hipLaunchKernelGGL((layernorm_bwd_multi_kernel<T_, 2, ACC_, LC_>), dim3((unsigned)blocks, npos), dim3(256), smem, s,  \
-                     (const T_*)d->x, d->ldx, d->rows, (int)d->D, side, grid_r, mp, d->dx, d->lddx)
-#define LN_MULTI_T(T_)                                                                      \
-  do {                                                                                      \
-    if (mp.layers > 6) { if (acc) LN_MULTI_LAUNCH(T_, true, 7); else LN_MULTI_LAUNCH(T_, false, 7); } \
-    else if (mp.layers > 5) { if (acc) LN_MULTI_LAUNCH(T_, true, 6); else LN_MULTI_LAUNCH(T_, false, 6); } \
-    else if (mp.layers > 4) { if (acc) LN_MULTI_LAUNCH(T_, true, 5); else LN_MULTI_LAUNCH(T_, false, 5); } \
-    else if (mp.layers > 2) { if (acc) LN_MULTI_LAUNCH(T_, true, 4); else LN_MULTI_LAUNCH(T_, false, 4); } \
-    else { if (acc) LN_MULTI_LAUNCH(T_, true, 2); else LN_MULTI_LAUNCH(T_, false, 2); }      \
-  } while (0)
-    if (d->dtype == CMB_BF16) LN_MULTI_T(bf16_t);
-    else LN_MULTI_T(float);
-#undef LN_MULTI_T
+    // partial-sum sets the kernel is compiled for: 2, 4, 5, 6 or 7 (mp.layers <= kChunk <= 7)
+    const int lc = mp.layers > 4 ? mp.layers : mp.layers > 2 ? 4 : 2;
+#define LN_MULTI_LAUNCH                                                                                                       \
+  DT_SWITCH(d->dtype, BOOL_SWITCH(acc, ACCUM,                                                                                 \
+                                  hipLaunchKernelGGL((layernorm_bwd_multi_kernel<T, 2, ACCUM, LC>), dim3((unsigned)blocks, npos), \
+                                                     dim3(256), smem, s, (const T*)d->x, d->ldx, d->rows, (int)d->D, side,     \
+                                                     grid_r, mp, d->dx, d->lddx)))
+    switch (lc) {
+      INT_CASE(LC, 2, LN_MULTI_LAUNCH)
+      INT_CASE(LC, 4, LN_MULTI_LAUNCH)
+      INT_CASE(LC, 5, LN_MULTI_LAUNCH)
+      INT_CASE(LC, 6, LN_MULTI_LAUNCH)
+      INT_CASE(LC, 7, LN_MULTI_LAUNCH)
+    }
 #undef LN_MULTI_LAUNCH
     CMB_CHECK_LAUNCH();
     for (int l = 0; l < mp.layers; ++l)
@@ -1224,15 +982,8 @@ extern "C" int cmb_rmsnorm_fwd(int dtype, const void* x, int64_t rows, int64_t D
   if (rows == 0) return CMB_OK;
   hipStream_t s = (hipStream_t)stream;
   const int nch = nch_for(D);
-  if (dtype == CMB_BF16) {
-    DISPATCH_NCH(nch, hipLaunchKernelGGL((rmsnorm_fwd_kernel<bf16_t, NCH>), dim3(row_grid(rows)), dim3(256), 0,
-                                         s, (const bf16_t*)x, rows, (int)D, w, eps, (bf16_t*)y, rstd));
-  } else if (dtype == CMB_F32) {
-    DISPATCH_NCH(nch, hipLaunchKernelGGL((rmsnorm_fwd_kernel<float, NCH>), dim3(row_grid(rows)), dim3(256), 0, s,
-                                         (const float*)x, rows, (int)D, w, eps, (float*)y, rstd));
-  } else {
-    return CMB_ERR_BAD_ARG;
-  }
+  DT_SWITCH(dtype, DISPATCH_NCH(nch, hipLaunchKernelGGL((rmsnorm_fwd_kernel<T, NCH>), dim3(grid_for(rows, 4, 8192)), dim3(256),
+                                                        0, s, (const T*)x, rows, (int)D, w, eps, (T*)y, rstd)));
   CMB_CHECK_LAUNCH();
   return CMB_OK;
 }
@@ -1241,17 +992,11 @@ template <typename T>
 static int rms_bwd(const void* dy, const void* x, int64_t rows, int64_t D, const float* w, const float* rstd,
                    void* dx, float* dw, hipStream_t s) {
   const int nch = nch_for(D);
-  int64_t blocks = dw ? (rows + 63) / 64 : (rows + 3) / 4;
-  if (blocks > 4096) blocks = 4096;
-  if (blocks < 1) blocks = 1;
+  const unsigned blocks = grid_for(rows, dw ? 64 : 4, 4096);
   const size_t smem = dw ? (size_t)4 * D * sizeof(float) : 0;
-  if (dw) {
-    DISPATCH_NCH(nch, hipLaunchKernelGGL((rmsnorm_bwd_kernel<T, NCH, true>), dim3((unsigned)blocks), dim3(256),
-                                         smem, s, (const T*)dy, (const T*)x, rows, (int)D, w, rstd, (T*)dx, dw));
-  } else {
-    DISPATCH_NCH(nch, hipLaunchKernelGGL((rmsnorm_bwd_kernel<T, NCH, false>), dim3((unsigned)blocks), dim3(256),
-                                         smem, s, (const T*)dy, (const T*)x, rows, (int)D, w, rstd, (T*)dx, dw));
-  }
+  BOOL_SWITCH(dw != nullptr, HAS_DW,
+              DISPATCH_NCH(nch, hipLaunchKernelGGL((rmsnorm_bwd_kernel<T, NCH, HAS_DW>), dim3(blocks), dim3(256), smem, s,
+                                                   (const T*)dy, (const T*)x, rows, (int)D, w, rstd, (T*)dx, dw)));
   CMB_CHECK_LAUNCH();
   return CMB_OK;
 }
@@ -1260,10 +1005,7 @@ extern "C" int cmb_rmsnorm_bwd(int dtype, const void* dy, const void* x, int64_t
                                const float* w, const float* rstd, void* dx, float* dw, void* stream) {
   if (!dy || !x || !w || !rstd || !dx || rows < 0 || D <= 0 || (D & 7)) return CMB_ERR_BAD_ARG;
   if (rows == 0) return CMB_OK;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == CMB_BF16) return rms_bwd<bf16_t>(dy, x, rows, D, w, rstd, dx, dw, s);
-  if (dtype == CMB_F32) return rms_bwd<float>(dy, x, rows, D, w, rstd, dx, dw, s);
-  return CMB_ERR_BAD_ARG;
+  DT_SWITCH(dtype, return rms_bwd<T>(dy, x, rows, D, w, rstd, dx, dw, (hipStream_t)stream));
 }
 
 extern "C" int cmb_rope_table(const int64_t* position_ids, int64_t ntok, int64_t Dh, float base,
@@ -1271,9 +1013,7 @@ extern "C" int cmb_rope_table(const int64_t* position_ids, int64_t ntok, int64_t
   if (!position_ids || !cos_t || !sin_t || ntok < 0 || Dh <= 0 || (Dh & 1)) return CMB_ERR_BAD_ARG;
   if (ntok == 0) return CMB_OK;
   const int half = (int)(Dh / 2);
-  int64_t blocks = (ntok * half + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(rope_table_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, position_ids,
+  hipLaunchKernelGGL(rope_table_kernel, dim3(grid_for(ntok * half, 256, 4096)), dim3(256), 0, (hipStream_t)stream, position_ids,
                      ntok, half, (int)Dh, base, cos_t, sin_t);
   CMB_CHECK_LAUNCH();
   return CMB_OK;
@@ -1286,15 +1026,8 @@ extern "C" int cmb_rope_apply(int dtype, void* x, const float* cos_t, const floa
   hipStream_t s = (hipStream_t)stream;
   const int64_t items = H * (Dh / 16);
   int threads = items >= 256 ? 256 : (int)((items + 63) / 64 * 64);
-  int64_t blocks = ntok > 65535 ? 65535 : ntok;
-  if (dtype == CMB_BF16)
-    hipLaunchKernelGGL(rope_apply_kernel<bf16_t>, dim3((unsigned)blocks), dim3(threads), 0, s, (bf16_t*)x, cos_t,
-                       sin_t, ntok, (int)H, (int)Dh, row_stride, inverse);
-  else if (dtype == CMB_F32)
-    hipLaunchKernelGGL(rope_apply_kernel<float>, dim3((unsigned)blocks), dim3(threads), 0, s, (float*)x, cos_t,
-                       sin_t, ntok, (int)H, (int)Dh, row_stride, inverse);
-  else
-    return CMB_ERR_BAD_ARG;
+  DT_SWITCH(dtype, hipLaunchKernelGGL(rope_apply_kernel<T>, dim3(grid_for(ntok, 1, 65535)), dim3(threads), 0, s, (T*)x, cos_t,
+                                      sin_t, ntok, (int)H, (int)Dh, row_stride, inverse));
   CMB_CHECK_LAUNCH();
   return CMB_OK;
 }
@@ -1306,17 +1039,9 @@ extern "C" int cmb_add_rmsnorm_fwd(int dtype, const void* x, const void* res, in
   const int nch = nch_for(D);
   if (nch < 0) return CMB_ERR_SHAPE;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CMB_BF16) {
-    DISPATCH_NCH(nch, hipLaunchKernelGGL((add_rmsnorm_fwd_kernel<bf16_t, NCH>), dim3(row_grid(rows)), dim3(256), 0, s,
-                                         (const bf16_t*)x, (const bf16_t*)res, rows, (int)D, w, eps, (bf16_t*)sum,
-                                         (bf16_t*)y, rstd));
-  } else if (dtype == CMB_F32) {
-    DISPATCH_NCH(nch, hipLaunchKernelGGL((add_rmsnorm_fwd_kernel<float, NCH>), dim3(row_grid(rows)), dim3(256), 0, s,
-                                         (const float*)x, (const float*)res, rows, (int)D, w, eps, (float*)sum,
-                                         (float*)y, rstd));
-  } else {
-    return CMB_ERR_BAD_ARG;
-  }
+  DT_SWITCH(dtype, DISPATCH_NCH(nch, hipLaunchKernelGGL((add_rmsnorm_fwd_kernel<T, NCH>), dim3(grid_for(rows, 4, 8192)),
+                                                        dim3(256), 0, s, (const T*)x, (const T*)res, rows, (int)D, w, eps,
+                                                        (T*)sum, (T*)y, rstd)));
   CMB_CHECK_LAUNCH();
   return CMB_OK;
 }
@@ -1328,17 +1053,9 @@ extern "C" int cmb_rmsnorm_bwd_add(int dtype, const void* dy, const void* x, con
   const int nch = nch_for(D);
   if (nch < 0) return CMB_ERR_SHAPE;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == CMB_BF16) {
-    DISPATCH_NCH(nch, hipLaunchKernelGGL((rmsnorm_bwd_add_kernel<bf16_t, NCH>), dim3(row_grid(rows)), dim3(256), 0, s,
-                                         (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)dadd, rows, (int)D, w, rstd,
-                                         (bf16_t*)dx));
-  } else if (dtype == CMB_F32) {
-    DISPATCH_NCH(nch, hipLaunchKernelGGL((rmsnorm_bwd_add_kernel<float, NCH>), dim3(row_grid(rows)), dim3(256), 0, s,
-                                         (const float*)dy, (const float*)x, (const float*)dadd, rows, (int)D, w, rstd,
-                                         (float*)dx));
-  } else {
-    return CMB_ERR_BAD_ARG;
-  }
+  DT_SWITCH(dtype, DISPATCH_NCH(nch, hipLaunchKernelGGL((rmsnorm_bwd_add_kernel<T, NCH>), dim3(grid_for(rows, 4, 8192)),
+                                                        dim3(256), 0, s, (const T*)dy, (const T*)x, (const T*)dadd, rows,
+                                                        (int)D, w, rstd, (T*)dx)));
   CMB_CHECK_LAUNCH();
   return CMB_OK;
 }
