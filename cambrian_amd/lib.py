@@ -316,6 +316,24 @@ def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def call(symbol: str, *args, device, what: Optional[str] = None) -> None:
+    """The launch idiom of every status-returning entry point: ``symbol(*args, stream of device)`` on the loaded library,
+    a non-zero status raised under the name ``what`` (default: the symbol).  Queries that return a size or an id call
+    ``load()`` themselves."""
+    rc = getattr(load(), symbol)(*args, stream_ptr(device))
+    if rc != 0:
+        check(rc, what or symbol)
+
+
+def env_flag(name: str, default: bool) -> bool:
+    """An on/off switch of the environment, read now: a switch that defaults to on is off only for "0", one that
+    defaults to off is on only for "1"."""
+    v = os.environ.get(name)
+    if v is None:
+        return default
+    return v != "0" if default else v == "1"
+
+
 def require_gpu(*tensors: Optional[torch.Tensor]) -> None:
     for t in tensors:
         if t is not None and not t.is_cuda:

@@ -41,7 +41,7 @@ STATIC_PATH = True
 _TOWER_STREAMS = os.environ.get("CAMBRIAN_AMD_TOWER_STREAMS", "0")   # frozen towers on side HIP streams (encode_images)
 
 
-_PAIR_TOWERS = os.environ.get("CAMBRIAN_AMD_PAIR_TOWERS", "1") != "0"   # two frozen ViT trunks in lock-step (encode_images)
+_PAIR_TOWERS = L.env_flag("CAMBRIAN_AMD_PAIR_TOWERS", True)   # two frozen ViT trunks in lock-step (encode_images)
 
 
 def _pair_rounds_gain(ta, tb, batch: int, n_cu: int = 256) -> float:

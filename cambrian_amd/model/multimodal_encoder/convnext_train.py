@@ -56,9 +56,8 @@ class DwConv7x7Fn(torch.autograd.Function):
                 raise L.CambrianAmdError("depthwise weight gradient needs C % 64 == 0")
             slots = min(WGRAD_SLOTS, B * ((H + 7) // 8) * ((W + 7) // 8))
             part = torch.empty((slots, 49 * C), dtype=torch.float32, device=x.device)
-            rc = L.load().cmb_dwconv7x7_wgrad(L.dtype_code(x.dtype), x.data_ptr(), dy.data_ptr(), B, H, W, C,
-                                              part.data_ptr(), slots, L.stream_ptr(x.device))
-            L.check(rc, "cmb_dwconv7x7_wgrad")
+            L.call("cmb_dwconv7x7_wgrad", L.dtype_code(x.dtype), x.data_ptr(), dy.data_ptr(), B, H, W, C, part.data_ptr(), slots,
+                   device=x.device)
             dw = ops.k_colsum(part).view(49, C)
         if ctx.needs_input_grad[2]:
             db = ops.k_colsum(dy.view(-1, C))

@@ -1,12 +1,12 @@
 """Raw launchers of the vision-tower kernels (forward only: the towers are frozen)."""
 from __future__ import annotations
 
-import os
 from typing import Optional, Tuple
 
 import torch
 
 from ... import lib as L
+from ...ops import k_resample, k_resample_bwd  # noqa: F401  (their home is next to their autograd wrappers)
 
 # Round 6 (measured, OFF by default): the frozen towers' LayerNorm -> linear pairs (ViT ln1 -> qkv, ln2 -> fc1; ConvNeXt ln -> fc1)
 # as cmb_row_stats + ONE GEMM on the un-normalised rows with the LayerNorm folded into its epilogue (cmb_gemm_desc.row_mean): the
@@ -14,7 +14,7 @@ from ... import lib as L
 # pass saves 40 % of a LayerNorm (ConvNeXt stage 3: 98.6 -> 57.2 us) and the two extra packed multiply-adds + the colsum vector cost
 # the 4-wave GEMM's one-wave-per-SIMD epilogue 3-9 % (1634 -> 1688 us): profiles/r06_lab.md.  CAMBRIAN_AMD_LN_FUSE=1 packs the
 # bf16 towers that way (tests/test_ln_fold_gpu.py keeps the path correct).  Read when a tower packs its weights.
-LN_FUSE = os.environ.get("CAMBRIAN_AMD_LN_FUSE", "0") == "1"
+LN_FUSE = L.env_flag("CAMBRIAN_AMD_LN_FUSE", False)
 
 
 def fold_ln_into_linear(w: torch.Tensor, b: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor,
@@ -35,9 +35,8 @@ def k_vit_attn(qkv: torch.Tensor, B: int, N: int, heads: int, hd: int, scale: fl
     L.require_gpu(qkv)
     assert qkv.is_contiguous() and qkv.shape == (B * N, 3 * heads * hd)
     out = torch.empty((B * N, heads * hd), dtype=qkv.dtype, device=qkv.device)
-    rc = L.load().cmb_vit_attn_fwd(L.dtype_code(qkv.dtype), qkv.data_ptr(), B, N, heads, hd, scale, out.data_ptr(),
-                                   1 if force_simple else 0, L.stream_ptr(qkv.device))
-    L.check(rc, "cmb_vit_attn_fwd")
+    L.call("cmb_vit_attn_fwd", L.dtype_code(qkv.dtype), qkv.data_ptr(), B, N, heads, hd, scale, out.data_ptr(),
+           1 if force_simple else 0, device=qkv.device)
     return out
 
 
@@ -48,9 +47,8 @@ def k_patchify(img: torch.Tensor, p: int, kpad: int, out_dtype: torch.dtype) -> 
     B, C, H, W = img.shape
     rows = B * (H // p) * (W // p)
     cols = torch.empty((rows, kpad), dtype=out_dtype, device=img.device)
-    rc = L.load().cmb_patchify_nchw(L.dtype_code(img.dtype), img.data_ptr(), B, C, H, W, p, L.dtype_code(out_dtype),
-                                    cols.data_ptr(), kpad, L.stream_ptr(img.device))
-    L.check(rc, "cmb_patchify_nchw")
+    L.call("cmb_patchify_nchw", L.dtype_code(img.dtype), img.data_ptr(), B, C, H, W, p, L.dtype_code(out_dtype), cols.data_ptr(),
+           kpad, device=img.device)
     return cols
 
 
@@ -60,9 +58,7 @@ def k_patchify2x2(x: torch.Tensor) -> torch.Tensor:
     assert x.is_contiguous()
     B, H, W, C = x.shape
     cols = torch.empty((B * (H // 2) * (W // 2), 4 * C), dtype=x.dtype, device=x.device)
-    rc = L.load().cmb_patchify2x2_nhwc(L.dtype_code(x.dtype), x.data_ptr(), B, H, W, C, cols.data_ptr(),
-                                       L.stream_ptr(x.device))
-    L.check(rc, "cmb_patchify2x2_nhwc")
+    L.call("cmb_patchify2x2_nhwc", L.dtype_code(x.dtype), x.data_ptr(), B, H, W, C, cols.data_ptr(), device=x.device)
     return cols
 
 
@@ -72,34 +68,9 @@ def k_dwconv7x7(x: torch.Tensor, w49: torch.Tensor, bias: torch.Tensor) -> torch
     assert x.is_contiguous() and w49.dtype == torch.float32 and bias.dtype == torch.float32
     B, H, W, C = x.shape
     y = torch.empty_like(x)
-    rc = L.load().cmb_dwconv7x7_nhwc(L.dtype_code(x.dtype), x.data_ptr(), B, H, W, C, w49.data_ptr(), bias.data_ptr(),
-                                     y.data_ptr(), L.stream_ptr(x.device))
-    L.check(rc, "cmb_dwconv7x7_nhwc")
+    L.call("cmb_dwconv7x7_nhwc", L.dtype_code(x.dtype), x.data_ptr(), B, H, W, C, w49.data_ptr(), bias.data_ptr(), y.data_ptr(),
+           device=x.device)
     return y
-
-
-def k_resample(x: torch.Tensor, hi: int, wi: int, out: torch.Tensor, ho: int, wo: int, col_offset: int = 0) -> None:
-    """x [B, hi*wi, C] -> out[:, :, col_offset:col_offset+C] with out [B, ho*wo, Ctot] (bilinear, fp32 lerp)."""
-    L.require_gpu(x, out)
-    B, T, C = x.shape
-    assert T == hi * wi and out.shape[0] == B and out.shape[1] == ho * wo and x.stride(2) == 1 and out.stride(2) == 1
-    optr = out.data_ptr() + col_offset * out.element_size()
-    rc = L.load().cmb_resample_bilinear(L.dtype_code(x.dtype), x.data_ptr(), B, hi, wi, C, x.stride(1), x.stride(0), optr,
-                                        ho, wo, out.stride(1), out.stride(0), L.stream_ptr(x.device))
-    L.check(rc, "cmb_resample_bilinear")
-
-
-def k_resample_bwd(dout: torch.Tensor, ho: int, wo: int, dx: torch.Tensor, hi: int, wi: int, col_offset: int = 0) -> None:
-    """Adjoint of ``k_resample``: dout[:, :, col_offset:col_offset+C] with dout [B, ho*wo, Ctot] -> dx [B, hi*wi, C], written in
-    full (cells no output refers to get 0).  Gather form in a fixed order: no atomics, bit-reproducible."""
-    L.require_gpu(dout, dx)
-    B, T, C = dx.shape
-    assert T == hi * wi and dout.shape[0] == B and dout.shape[1] == ho * wo and dx.stride(2) == 1 and dout.stride(2) == 1
-    assert dout.dtype == dx.dtype and 0 <= col_offset and col_offset + C <= dout.shape[2]
-    gptr = dout.data_ptr() + col_offset * dout.element_size()
-    rc = L.load().cmb_resample_bilinear_bwd(L.dtype_code(dx.dtype), gptr, B, ho, wo, C, dout.stride(1), dout.stride(0),
-                                            dx.data_ptr(), hi, wi, dx.stride(1), dx.stride(0), L.stream_ptr(dx.device))
-    L.check(rc, "cmb_resample_bilinear_bwd")
 
 
 def k_act_mul(a: torch.Tensor, b: Optional[torch.Tensor], act: int) -> torch.Tensor:
@@ -107,15 +78,12 @@ def k_act_mul(a: torch.Tensor, b: Optional[torch.Tensor], act: int) -> torch.Ten
     L.require_gpu(a, b)
     rows, D = a.shape
     y = torch.empty((rows, D), dtype=a.dtype, device=a.device)
-    rc = L.load().cmb_act_mul(L.dtype_code(a.dtype), act, a.data_ptr(), a.stride(0), L.ptr(b),
-                              0 if b is None else b.stride(0), rows, D, y.data_ptr(), D, L.stream_ptr(a.device))
-    L.check(rc, "cmb_act_mul")
+    L.call("cmb_act_mul", L.dtype_code(a.dtype), act, a.data_ptr(), a.stride(0), L.ptr(b), 0 if b is None else b.stride(0), rows, D,
+           y.data_ptr(), D, device=a.device)
     return y
 
 
 def k_bcast_rows(dst: torch.Tensor, ld: int, nrows: int, src: torch.Tensor) -> None:
     """dst[r*ld : r*ld + D] = src for r in range(nrows) (CLS rows of the token buffers)."""
     L.require_gpu(dst, src)
-    rc = L.load().cmb_bcast_rows(L.dtype_code(dst.dtype), dst.data_ptr(), ld, nrows, src.numel(), src.data_ptr(),
-                                 L.stream_ptr(dst.device))
-    L.check(rc, "cmb_bcast_rows")
+    L.call("cmb_bcast_rows", L.dtype_code(dst.dtype), dst.data_ptr(), ld, nrows, src.numel(), src.data_ptr(), device=dst.device)

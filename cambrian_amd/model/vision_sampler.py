@@ -22,12 +22,10 @@ from typing import List, Optional, Sequence
 import torch
 import torch.nn as nn
 
-import os
-
 from .. import lib as L
 from .. import ops
 
-ABSORB_KV = os.environ.get("CAMBRIAN_AMD_ABSORB_KV", "1") != "0"
+ABSORB_KV = L.env_flag("CAMBRIAN_AMD_ABSORB_KV", True)
 
 
 

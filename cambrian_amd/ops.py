@@ -1,10 +1,13 @@
 """Host-side operators over the C-ABI kernels.
 
 Two layers:
-  * ``k_*``  — thin, stateless launchers (no autograd): validate, fill the C structs, call the library.
-  * ``*Fn`` / functional wrappers — ``torch.autograd.Function`` objects that pair each forward kernel
-    with its backward kernels, so the reference's modules (cambrian/model/vision_sampler.py,
-    cambrian_arch.py) can be re-stated on top of them without touching torch's own math kernels.
+  * ``k_*``  — thin, stateless launchers (no autograd), one per entry point: validate, allocate the outputs, fill the C
+    structs, launch through ``lib.call`` (size / id queries through ``lib.load()``).
+  * ``*Fn`` / functional wrappers — ``torch.autograd.Function`` objects that pair each forward launcher
+    with its backward launchers, so the reference's modules (cambrian/model/vision_sampler.py,
+    cambrian_arch.py) can be re-stated on top of them without touching torch's own math kernels.  They hold the autograd
+    bookkeeping only (reshapes, what is saved, early returns) and never call the library themselves.
+This module imports nothing from ``model/``; ``vit_ops`` holds the tower-only launchers and re-exports the resample pair.
 
 Compute dtype is the dtype of the activation tensor (bf16 for training, fp32 for the parity path);
 parameters stay fp32 masters and are cast per call (the cast is itself ``cmb_cast``).
@@ -43,10 +46,13 @@ def k_cast(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     if xc.dtype == dtype:
         return xc
     out = torch.empty(xc.shape, dtype=dtype, device=xc.device)
-    rc = L.load().cmb_cast(L.dtype_code(xc.dtype), xc.data_ptr(), L.dtype_code(dtype), out.data_ptr(), xc.numel(),
-                           L.stream_ptr(xc.device))
-    L.check(rc, "cmb_cast")
+    L.call("cmb_cast", L.dtype_code(xc.dtype), xc.data_ptr(), L.dtype_code(dtype), out.data_ptr(), xc.numel(), device=xc.device)
     return out
+
+
+def _param_grad(t: Optional[torch.Tensor], dtype: torch.dtype) -> Optional[torch.Tensor]:
+    """A parameter's gradient as it leaves the fp32 accumulators, in the parameter's own dtype."""
+    return t if t is None or dtype == torch.float32 else t.to(dtype)
 
 
 def _gemm_desc(dt: int, M: int, N: int, K: int, a: torch.Tensor, a_map: RowMap, w: torch.Tensor, ldb: int, out: torch.Tensor,
@@ -191,9 +197,8 @@ def k_quantize_fp8_rows(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     rows, K = x.shape
     q = torch.empty((rows, K), dtype=torch.uint8, device=x.device)
     inv = torch.empty((rows,), dtype=torch.float32, device=x.device)
-    rc = L.load().cmb_quantize_fp8_rows(L.dtype_code(x.dtype), x.data_ptr(), x.stride(0), rows, K, q.data_ptr(), K,
-                                        inv.data_ptr(), L.stream_ptr(x.device))
-    L.check(rc, f"cmb_quantize_fp8_rows({rows}x{K})")
+    L.call("cmb_quantize_fp8_rows", L.dtype_code(x.dtype), x.data_ptr(), x.stride(0), rows, K, q.data_ptr(), K, inv.data_ptr(),
+           device=x.device, what=f"cmb_quantize_fp8_rows({rows}x{K})")
     return q, inv
 
 
@@ -418,9 +423,7 @@ def k_transpose(x: torch.Tensor, r_pad: Optional[int] = None) -> torch.Tensor:
         x = x.contiguous()
     r_pad = r_pad or pad_to(R, 8)
     out = torch.empty((Cc, r_pad), dtype=x.dtype, device=x.device)
-    rc = L.load().cmb_transpose(L.dtype_code(x.dtype), x.data_ptr(), R, Cc, x.stride(0), out.data_ptr(), r_pad,
-                                L.stream_ptr(x.device))
-    L.check(rc, "cmb_transpose")
+    L.call("cmb_transpose", L.dtype_code(x.dtype), x.data_ptr(), R, Cc, x.stride(0), out.data_ptr(), r_pad, device=x.device)
     return out
 
 
@@ -466,23 +469,24 @@ def k_colsum(x: torch.Tensor, out: Optional[torch.Tensor] = None, row_scale: Opt
     if row_scale is not None:
         if row_scale.dtype != torch.float32 or row_scale.dim() != 2 or row_scale.stride(1) != 1 or row_scale.shape != (R, Cc // group):
             raise L.CambrianAmdError("colsum row_scale must be fp32 [R, C / group]")
-        rc = L.load().cmb_colsum_scaled(L.dtype_code(x.dtype), x.data_ptr(), R, Cc, x.stride(0), row_scale.data_ptr(),
-                                        row_scale.stride(0), group, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                        L.stream_ptr(x.device))
-        L.check(rc, "cmb_colsum_scaled")
+        L.call("cmb_colsum_scaled", L.dtype_code(x.dtype), x.data_ptr(), R, Cc, x.stride(0), row_scale.data_ptr(),
+               row_scale.stride(0), group, out.data_ptr(), ws.data_ptr(), ws.numel(), device=x.device)
         return out
-    rc = L.load().cmb_colsum(L.dtype_code(x.dtype), x.data_ptr(), R, Cc, x.stride(0), out.data_ptr(), ws.data_ptr(),
-                             ws.numel(), L.stream_ptr(x.device))
-    L.check(rc, "cmb_colsum")
+    L.call("cmb_colsum", L.dtype_code(x.dtype), x.data_ptr(), R, Cc, x.stride(0), out.data_ptr(), ws.data_ptr(), ws.numel(),
+           device=x.device)
     return out
 
 
 def k_token_mean(x3: torch.Tensor) -> torch.Tensor:
     B, T, D = x3.shape
     out = torch.empty((B, D), dtype=x3.dtype, device=x3.device)
-    rc = L.load().cmb_token_mean_fwd(L.dtype_code(x3.dtype), x3.data_ptr(), B, T, D, out.data_ptr(), L.stream_ptr(x3.device))
-    L.check(rc, "cmb_token_mean_fwd")
+    L.call("cmb_token_mean_fwd", L.dtype_code(x3.dtype), x3.data_ptr(), B, T, D, out.data_ptr(), device=x3.device)
     return out
+
+
+def k_token_mean_bwd(g: torch.Tensor, B: int, T: int, D: int, acc: torch.Tensor) -> None:
+    """acc (fp32 [B*T, D]) += g[b] / T for every token of sample b (cmb_token_mean_bwd)."""
+    L.call("cmb_token_mean_bwd", L.dtype_code(g.dtype), g.data_ptr(), B, T, D, acc.data_ptr(), device=g.device)
 
 
 def k_segment_sum(x: torch.Tensor, rep: int) -> torch.Tensor:
@@ -499,10 +503,8 @@ def k_layernorm_fwd(x, gamma, beta, eps, add=None, side=1, grid_r=1, want_stats=
     y = torch.empty((rows, D), dtype=x.dtype, device=x.device)
     mean = torch.empty((rows,), dtype=torch.float32, device=x.device) if want_stats else None
     rstd = torch.empty((rows,), dtype=torch.float32, device=x.device) if want_stats else None
-    rc = L.load().cmb_layernorm_fwd(L.dtype_code(x.dtype), x.data_ptr(), rows, D, x.stride(0), L.ptr(add), side, grid_r,
-                                    L.ptr(gamma), L.ptr(beta), eps, y.data_ptr(), D, L.ptr(mean), L.ptr(rstd),
-                                    L.stream_ptr(x.device))
-    L.check(rc, "cmb_layernorm_fwd")
+    L.call("cmb_layernorm_fwd", L.dtype_code(x.dtype), x.data_ptr(), rows, D, x.stride(0), L.ptr(add), side, grid_r,
+           L.ptr(gamma), L.ptr(beta), eps, y.data_ptr(), D, L.ptr(mean), L.ptr(rstd), device=x.device)
     return y, mean, rstd
 
 
@@ -527,7 +529,7 @@ def k_layernorm_fwd_multi(x: torch.Tensor, adds, eps: float, side: int = 1, grid
             d.add[i] = None if a is None else a.data_ptr()
             d.y[i], d.mean[i], d.rstd[i] = y.data_ptr(), mean.data_ptr(), rstd.data_ptr()
             out.append((y, mean, rstd))
-        L.check(L.load().cmb_layernorm_fwd_multi(C.byref(d), L.stream_ptr(x.device)), "cmb_layernorm_fwd_multi")
+        L.call("cmb_layernorm_fwd_multi", C.byref(d), device=x.device)
     return out
 
 
@@ -537,9 +539,8 @@ def k_row_stats(x: torch.Tensor, eps: float) -> Tuple[torch.Tensor, torch.Tensor
     rows, D = x.shape
     mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
     rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
-    rc = L.load().cmb_row_stats(L.dtype_code(x.dtype), x.data_ptr(), rows, D, x.stride(0), eps, mean.data_ptr(), rstd.data_ptr(),
-                                L.stream_ptr(x.device))
-    L.check(rc, "cmb_row_stats")
+    L.call("cmb_row_stats", L.dtype_code(x.dtype), x.data_ptr(), rows, D, x.stride(0), eps, mean.data_ptr(), rstd.data_ptr(),
+           device=x.device)
     return mean, rstd
 
 
@@ -563,12 +564,186 @@ def k_layernorm_bwd(dy, x, mean, rstd, gamma=None, add=None, side=1, grid_r=1, d
     nslab = (dgamma is not None) + (dbeta is not None) + (dadd is not None)
     per = L.load().cmb_layernorm_bwd_workspace(rows, D, grid_r if add is not None else 1) if rows > 0 else 0
     ws = torch.empty((max(nslab * per, 1),), dtype=torch.float32, device=dev)
-    rc = L.load().cmb_layernorm_bwd(L.dtype_code(x.dtype), dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), rows, D,
-                                    L.ptr(add), side, grid_r, L.ptr(gamma), mean.data_ptr(), rstd.data_ptr(),
-                                    dx.data_ptr(), D, acc, L.ptr(dgamma), L.ptr(dbeta), L.ptr(dadd), ws.data_ptr(),
-                                    ws.numel(), L.stream_ptr(dev))
-    L.check(rc, "cmb_layernorm_bwd")
+    L.call("cmb_layernorm_bwd", L.dtype_code(x.dtype), dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), rows, D,
+           L.ptr(add), side, grid_r, L.ptr(gamma), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(), D, acc, L.ptr(dgamma),
+           L.ptr(dbeta), L.ptr(dadd), ws.data_ptr(), ws.numel(), device=dev)
     return (None if dx_acc is not None else dx), dgamma, dbeta, dadd
+
+
+# ---- LLM-side launchers: operands are what the autograd nodes below prepared (2-D, contiguous, one dtype) ----------------
+def k_rmsnorm_fwd(x2: torch.Tensor, w32: torch.Tensor, eps: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(y, rstd) = (rmsnorm(x2) * w32, fp32 [rows]) of contiguous rows x2 [rows, D] (cmb_rmsnorm_fwd)."""
+    rows, D = x2.shape
+    y = torch.empty_like(x2)
+    rstd = torch.empty((rows,), dtype=torch.float32, device=x2.device)
+    L.call("cmb_rmsnorm_fwd", L.dtype_code(x2.dtype), x2.data_ptr(), rows, D, w32.data_ptr(), eps, y.data_ptr(), rstd.data_ptr(),
+           device=x2.device)
+    return y, rstd
+
+
+def k_add_rmsnorm_fwd(x2: torch.Tensor, d2: torch.Tensor, w32: torch.Tensor, eps: float):
+    """(s, y, rstd) = (x2 + d2, rmsnorm(s) * w32, fp32 [rows]) in one pass (cmb_add_rmsnorm_fwd)."""
+    rows, D = x2.shape
+    s = torch.empty_like(x2)
+    y = torch.empty_like(x2)
+    rstd = torch.empty((rows,), dtype=torch.float32, device=x2.device)
+    L.call("cmb_add_rmsnorm_fwd", L.dtype_code(x2.dtype), x2.data_ptr(), d2.data_ptr(), rows, D, w32.data_ptr(), eps,
+           s.data_ptr(), y.data_ptr(), rstd.data_ptr(), device=x2.device)
+    return s, y, rstd
+
+
+def k_rmsnorm_bwd(gy: torch.Tensor, x2: torch.Tensor, w32: torch.Tensor, rstd: torch.Tensor, add: Optional[torch.Tensor] = None,
+                  want_dw: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """(dx, dw) of y = rmsnorm(x2) * w32, with ``add`` (a gradient that reaches x2 by another route) summed into dx.
+    Trainable weight (``want_dw``): the two-pass cmb_rmsnorm_bwd that also reduces dw (fp32 [D]), then an ATen ``dx + add``.
+    Frozen weight: the single-pass cmb_rmsnorm_bwd_add (row kept in registers, ``add`` read in the same pass), dw None."""
+    rows, D = x2.shape
+    dx = torch.empty_like(x2)
+    if not want_dw:
+        L.call("cmb_rmsnorm_bwd_add", L.dtype_code(x2.dtype), gy.data_ptr(), x2.data_ptr(), L.ptr(add), rows, D, w32.data_ptr(),
+               rstd.data_ptr(), dx.data_ptr(), device=x2.device)
+        return dx, None
+    dw = torch.zeros((D,), dtype=torch.float32, device=x2.device)
+    L.call("cmb_rmsnorm_bwd", L.dtype_code(x2.dtype), gy.data_ptr(), x2.data_ptr(), rows, D, w32.data_ptr(), rstd.data_ptr(),
+           dx.data_ptr(), dw.data_ptr(), device=x2.device)
+    return (dx if add is None else dx + add), dw
+
+
+def k_rope_apply(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, inverse: bool = False) -> torch.Tensor:
+    """Rotates the contiguous x [ntok, H, Dh] IN PLACE by the cos / sin rows of ``rope_table`` (``inverse``: back)."""
+    ntok, H, Dh = x.shape
+    L.call("cmb_rope_apply", L.dtype_code(x.dtype), x.data_ptr(), cos.data_ptr(), sin.data_ptr(), ntok, H, Dh, H * Dh,
+           1 if inverse else 0, device=x.device, what="cmb_rope_apply(inverse)" if inverse else None)
+    return x
+
+
+def k_qkv_rope(packed: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+               merge: bool = False) -> None:
+    """cmb_qkv_rope over token-major q [B, S, nh, hd], k / v [B, S, nkv, hd] and packed [B, S, (nh + 2 nkv) hd]: split (packed
+    -> q, k, v with RoPE on q and k) or ``merge`` (the backward: q, k, v -> packed with the inverse rotation)."""
+    B, S, nh, hd = q.shape
+    L.call("cmb_qkv_rope", L.dtype_code(packed.dtype), 1 if merge else 0, packed.data_ptr(), cos.data_ptr(), sin.data_ptr(), B, S,
+           nh, k.shape[2], hd, q.data_ptr(), k.data_ptr(), v.data_ptr(), device=packed.device,
+           what="cmb_qkv_rope(merge)" if merge else "cmb_qkv_rope(split)")
+
+
+def k_act_bwd(g: torch.Tensor, pre: torch.Tensor, act: int) -> torch.Tensor:
+    """g * act'(pre) over dense tensors of one shape and dtype (cmb_act_bwd)."""
+    gp = torch.empty_like(pre)
+    L.call("cmb_act_bwd", L.dtype_code(g.dtype), act, g.data_ptr(), pre.data_ptr(), pre.numel(), gp.data_ptr(), device=g.device)
+    return gp
+
+
+def k_swiglu_fwd(g2: torch.Tensor, u2: torch.Tensor, cols: Optional[int] = None, u_col: int = 0, what: Optional[str] = None):
+    """h [rows, cols] = silu(g2[:, :cols]) * u2[:, u_col:u_col + cols] (cmb_act_mul; row strides taken from the tensors).  The
+    packed gate|up form passes the one [rows, 2I] tensor twice with ``cols`` = ``u_col`` = I."""
+    rows = g2.shape[0]
+    cols = g2.shape[1] if cols is None else cols
+    h = torch.empty((rows, cols), dtype=g2.dtype, device=g2.device)
+    L.call("cmb_act_mul", L.dtype_code(g2.dtype), L.ACT_SILU, g2.data_ptr(), g2.stride(0), u2.data_ptr() + u_col * u2.element_size(),
+           u2.stride(0), rows, cols, h.data_ptr(), cols, device=g2.device, what=what or "cmb_act_mul(silu)")
+    return h
+
+
+def k_swiglu_bwd(dh2: torch.Tensor, g2: torch.Tensor, u2: torch.Tensor, dg: torch.Tensor, du: torch.Tensor,
+                 cols: Optional[int] = None, u_col: int = 0, what: Optional[str] = None) -> None:
+    """Backward of ``k_swiglu_fwd`` (cmb_swiglu_bwd): dg[:, :cols] and du[:, u_col:u_col + cols] from dh2 [rows, cols]; the packed
+    form passes its one [rows, 2I] gradient buffer as both ``dg`` and ``du``."""
+    rows = g2.shape[0]
+    cols = g2.shape[1] if cols is None else cols
+    es = g2.element_size()
+    L.call("cmb_swiglu_bwd", L.dtype_code(g2.dtype), dh2.data_ptr(), dh2.stride(0), g2.data_ptr(), g2.stride(0),
+           u2.data_ptr() + u_col * es, u2.stride(0), rows, cols, dg.data_ptr(), dg.stride(0), du.data_ptr() + u_col * es,
+           du.stride(0), device=g2.device, what=what)
+
+
+def k_cross_entropy_fwd(logits: torch.Tensor, labels: torch.Tensor, ignore_index: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(lse, loss_rows) fp32 [T] of row-major logits [T, V] and contiguous int64 labels [T] (cmb_cross_entropy_fwd)."""
+    T, V = logits.shape
+    lse = torch.empty((T,), dtype=torch.float32, device=logits.device)
+    loss_rows = torch.empty((T,), dtype=torch.float32, device=logits.device)
+    L.call("cmb_cross_entropy_fwd", L.dtype_code(logits.dtype), logits.data_ptr(), T, V, logits.stride(0), labels.data_ptr(),
+           ignore_index, lse.data_ptr(), loss_rows.data_ptr(), device=logits.device)
+    return lse, loss_rows
+
+
+def k_cross_entropy_bwd(logits: torch.Tensor, labels: torch.Tensor, ignore_index: int, lse: torch.Tensor, scale: torch.Tensor,
+                        out: torch.Tensor) -> None:
+    """out = scale * d(loss rows) / d(logits) (``scale`` an fp32 device scalar; ``out`` may be ``logits`` itself)."""
+    T, V = logits.shape
+    L.call("cmb_cross_entropy_bwd", L.dtype_code(logits.dtype), logits.data_ptr(), T, V, logits.stride(0), labels.data_ptr(),
+           ignore_index, lse.data_ptr(), scale.data_ptr(), out.data_ptr(), out.stride(0), device=logits.device)
+
+
+def k_flash_attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: int, n: int,
+                     key_valid: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """q [B, H, S, D], k / v [B, HKV, S, D] as transposed views of token-major storage -> (out [B, S, H, D], lse [B, H, S])."""
+    B, H, S, D = q.shape
+    HKV = k.shape[1]
+    out = torch.empty((B, S, H, D), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
+    L.call("cmb_flash_attn_fwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), B, S, H, HKV, D, S * H * D, H * D, D, S * HKV * D,
+           HKV * D, D, scale, causal, n, L.ptr(key_valid), out.data_ptr(), lse.data_ptr(), device=q.device)
+    return out, lse
+
+
+def k_flash_attn_bwd(q, k, v, out, dout, lse, scale: float, causal: int, n: int, key_valid: Optional[torch.Tensor]):
+    """Operands laid out as in ``k_flash_attn_fwd`` (``out`` / ``dout`` like q, ``lse`` contiguous) -> (dq [B, S, H, D],
+    dk, dv [B, S, HKV, D]): the dQ kernel and the dK/dV kernel of flash_bwd.hip."""
+    B, H, S, D = q.shape
+    HKV = k.shape[1]
+    dq = torch.empty((B, S, H, D), dtype=q.dtype, device=q.device)
+    dk = torch.empty((B, S, HKV, D), dtype=q.dtype, device=q.device)
+    dv = torch.empty((B, S, HKV, D), dtype=q.dtype, device=q.device)
+    dvec = torch.empty((2, B, H, S), dtype=torch.float32, device=q.device)   # [0] D, [1] lse * log2 e (flash2.hip)
+    L.call("cmb_flash_attn_bwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), B, S,
+           H, HKV, D, S * H * D, H * D, D, S * HKV * D, HKV * D, D, scale, causal, n, L.ptr(key_valid), dvec.data_ptr(),
+           dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), device=q.device)
+    return dq, dk, dv
+
+
+def k_embed_splice_fwd(ids: torch.Tensor, table: torch.Tensor, feat: torch.Tensor, newline: torch.Tensor, side: int,
+                       image_token: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Contiguous ids [B, S], table [V, H], feat [B, side^2, H], newline [H] of one dtype -> (inputs_embeds [B, S, H], the
+    position of each sample's visual span, int32 [B]) (cmb_embed_splice_fwd)."""
+    B, S = ids.shape
+    V, H = table.shape
+    out = torch.empty((B, S, H), dtype=feat.dtype, device=feat.device)
+    pos = torch.empty((B,), dtype=torch.int32, device=feat.device)
+    L.call("cmb_embed_splice_fwd", L.dtype_code(feat.dtype), ids.data_ptr(), B, S, H, image_token, table.data_ptr(), V,
+           feat.data_ptr(), side, newline.data_ptr(), out.data_ptr(), pos.data_ptr(), device=feat.device)
+    return out, pos
+
+
+def k_embed_splice_bwd(dout: torch.Tensor, pos: torch.Tensor, side: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Contiguous d(inputs_embeds) [B, S, H] -> (d feat [B, side^2, H], d newline fp32 [H]) (cmb_embed_splice_bwd)."""
+    B, S, H = dout.shape
+    dfeat = torch.empty((B, side * side, H), dtype=dout.dtype, device=dout.device)
+    dnl = torch.zeros((H,), dtype=torch.float32, device=dout.device)
+    ws = torch.empty((max(B * side * H, 1),), dtype=torch.float32, device=dout.device)   # newline partial rows
+    L.call("cmb_embed_splice_bwd", L.dtype_code(dout.dtype), dout.data_ptr(), pos.data_ptr(), B, S, H, side, dfeat.data_ptr(),
+           dnl.data_ptr(), ws.data_ptr(), ws.numel(), device=dout.device)
+    return dfeat, dnl
+
+
+def k_fold_kv_fwd(ts: Sequence[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ts = contiguous fp32 (Wk, gk, bk, Wv, gv, bv) -> ([Wk*gk ; Wv*gv] [2H, K], [Wk@bk ; Wv@bv] [2H]) (cmb_sva_fold_kv_fwd)."""
+    H, K = ts[0].shape
+    w = torch.empty((2 * H, K), dtype=torch.float32, device=ts[0].device)
+    b = torch.empty((2 * H,), dtype=torch.float32, device=ts[0].device)
+    L.call("cmb_sva_fold_kv_fwd", *[t.data_ptr() for t in ts], H, K, w.data_ptr(), b.data_ptr(), device=w.device)
+    return w, b
+
+
+def k_fold_kv_bwd(dw: torch.Tensor, db: torch.Tensor, ts: Sequence[torch.Tensor]) -> List[torch.Tensor]:
+    """Gradients of the six inputs of ``k_fold_kv_fwd`` from contiguous fp32 dw [2H, K], db [2H] (cmb_sva_fold_kv_bwd)."""
+    H, K = ts[0].shape
+    dev = ts[0].device
+    outs = [torch.empty_like(t) for t in ts]
+    ws = torch.empty((L.load().cmb_sva_fold_kv_bwd_workspace(H, K) // 4,), dtype=torch.float32, device=dev)
+    L.call("cmb_sva_fold_kv_bwd", dw.data_ptr(), db.data_ptr(), *[t.data_ptr() for t in ts], H, K, *[o.data_ptr() for o in outs],
+           ws.data_ptr(), ws.numel() * 4, device=dev)
+    return outs
 
 
 def _fill_sva(desc: SvaDesc, q, kvs, masks, r_list, B, qside, heads, hd, window_major=False):
@@ -599,8 +774,7 @@ def k_sva_attn_fwd(q, kvs, masks, r_list, B, qside, heads, hd, window_major=Fals
     out = torch.empty((Bq, heads * hd), dtype=q.dtype, device=q.device)
     lse = torch.empty((Bq, heads), dtype=torch.float32, device=q.device)
     d.out, d.ldo, d.lse = out.data_ptr(), out.stride(0), lse.data_ptr()
-    rc = L.load().cmb_sva_attn_fwd(C.byref(d), L.stream_ptr(q.device))
-    L.check(rc, "cmb_sva_attn_fwd")
+    L.call("cmb_sva_attn_fwd", C.byref(d), device=q.device)
     return out, lse
 
 
@@ -616,8 +790,7 @@ def k_sva_attn_bwd(dout, q, kvs, masks, r_list, out, lse, B, qside, heads, hd, w
     d.dq, d.lddq = dq.data_ptr(), dq.stride(0)
     for i, t in enumerate(dkvs):
         d.dkv[i] = t.data_ptr()
-    rc = L.load().cmb_sva_attn_bwd(C.byref(d), L.stream_ptr(q.device))
-    L.check(rc, "cmb_sva_attn_bwd")
+    L.call("cmb_sva_attn_bwd", C.byref(d), device=q.device)
     return dq, dkvs
 
 
@@ -632,7 +805,7 @@ def k_sva_attn_bwd(dout, q, kvs, masks, r_list, out, lse, B, qside, heads, hd, w
 # window (direct calls of a layer, the re-computation forward of activation checkpointing, eval) nothing is cached: weights
 # may have changed in ways no version counter shows (ZeRO-2 writes the all-gathered shards straight into the flat buckets).
 # CAMBRIAN_AMD_PREP_WEIGHTS=0 restores the per-use launches (A/B runs).
-PREP_WEIGHTS = os.environ.get("CAMBRIAN_AMD_PREP_WEIGHTS", "1") != "0"
+PREP_WEIGHTS = L.env_flag("CAMBRIAN_AMD_PREP_WEIGHTS", True)
 _PREP: dict = {}
 _PREP_EPOCH = 0
 _PREP_ACTIVE = False
@@ -686,7 +859,7 @@ def weight_step_begin() -> None:
         table = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(dev)
         _PREP_TABLE = (sig, table, len(live), tile0)
     _, table, n, tiles = _PREP_TABLE
-    L.check(L.load().cmb_weight_prep(table.data_ptr(), n, tiles, L.stream_ptr(dev)), "cmb_weight_prep")
+    L.call("cmb_weight_prep", table.data_ptr(), n, tiles, device=dev)
     for key, e, base in live:
         e.epoch, e.src_ptr = _PREP_EPOCH, _prep_src_ptr(base, e)
 
@@ -709,7 +882,7 @@ def prepare_step_weight(w: torch.Tensor) -> None:
     j = L.PrepJob()
     j.src, j.dst, j.dst_t, j.ld_src, j.src_dtype = w.data_ptr(), w_c.data_ptr(), w_t.data_ptr(), K, L.F32
     j.rows, j.cols, j.rows_pad, j.tile0, j.reserved = N, K, w_t.shape[1], 0, 0
-    L.check(L.load().cmb_weight_prep_one(C.byref(j), L.stream_ptr(w.device)), "cmb_weight_prep_one")
+    L.call("cmb_weight_prep_one", C.byref(j), device=w.device)
     _PREP_TMP[id(w)] = (weakref.ref(w), w_c, w_t)
 
 
@@ -748,7 +921,7 @@ def prepared_weight(weight: torch.Tensor, dt: torch.dtype):
         _PREP[key] = e
     if e.epoch != _PREP_EPOCH or e.src_ptr != weight.data_ptr():   # first sight in this window: prepare it on the spot
         j = _prep_job(e, base, 0)
-        L.check(L.load().cmb_weight_prep_one(C.byref(j), L.stream_ptr(weight.device)), "cmb_weight_prep_one")
+        L.call("cmb_weight_prep_one", C.byref(j), device=weight.device)
         e.epoch, e.src_ptr = _PREP_EPOCH, weight.data_ptr()
     return e.w_c, e.w_t
 
@@ -757,7 +930,7 @@ def prepared_weight(weight: torch.Tensor, dt: torch.dtype):
 # autograd: linear
 # ================================================================================================
 # CAMBRIAN_AMD_TN_WGRAD=0: weight gradients through transposed copies + the NT kernels (A/B runs, tests of the old path)
-TN_WGRAD = os.environ.get("CAMBRIAN_AMD_TN_WGRAD", "1") != "0"
+TN_WGRAD = L.env_flag("CAMBRIAN_AMD_TN_WGRAD", True)
 
 
 def _tn_wgrad_wins(rows: int, n_out: int, k_in: int) -> bool:
@@ -787,6 +960,30 @@ def _as_dtype_contig(t: torch.Tensor, dt: torch.dtype) -> torch.Tensor:
     if t.dtype == dt and t.is_contiguous():
         return t
     return k_cast(t.contiguous(), dt)
+
+
+def _wgrad_into(g: torch.Tensor, x: torch.Tensor, out: torch.Tensor) -> None:
+    """out[N, K] (fp32: a whole weight gradient or a column slice of one, row stride out.stride(0)) = g[R, N]^T x[R, K], the one
+    place that picks the route of a weight gradient."""
+    R, N = g.shape
+    K = x.shape[1]
+    dt = g.dtype
+    if (dt == torch.bfloat16 and R > 0 and N % 8 == 0 and K % 8 == 0 and x.stride(1) == 1 and x.stride(0) % 8 == 0
+            and x.data_ptr() % 16 == 0 and g.data_ptr() % 16 == 0 and g.stride(1) == 1 and g.stride(0) % 8 == 0
+            and TN_WGRAD and _tn_wgrad_wins(R, N, K)):  # everything cmb_gemm_tn checks (gemm_tn_dispatch)
+        # dW = g^T x with g and x as they lie (cmb_gemm_tn: transposing LDS reads, rows beyond R contribute zero)
+        k_gemm_tn(g, x, out=out, split_k=_tn_splits(N, K, R), M=N, N=K, ldc=out.stride(0))
+    else:  # fp32 parity path / odd widths: transposed copies for the NT kernel
+        ks = _kstep(dt)
+        m_pad = pad_to(R, ks)
+        k_gemm(k_transpose(g, m_pad), k_transpose(x, m_pad), out=out, split_k=_wgrad_splits(N, K, m_pad, ks))
+
+
+def _wgrad(g: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """g[R, N]^T x[R, K] as a new fp32 [N, K] tensor."""
+    out = torch.empty((g.shape[1], x.shape[1]), dtype=torch.float32, device=g.device)
+    _wgrad_into(g, x, out)
+    return out
 
 
 class LinearFn(torch.autograd.Function):
@@ -845,8 +1042,7 @@ class LinearFn(torch.autograd.Function):
         dt = x.dtype
         dy = _as_dtype_contig(dy, dt)
         need_x, need_w, need_b, _, need_res = ctx.needs_input_grad[:5]
-        M, K = x.shape
-        N = w_c.shape[0]
+        M, N = x.shape[0], w_c.shape[0]
         dres = None
         if need_res:
             if ctx.link is not None and ctx.role == 2:
@@ -857,11 +1053,7 @@ class LinearFn(torch.autograd.Function):
         if colscale is not None:
             g = dy * colscale.to(dt)  # LayerScale belongs to the frozen towers; kept for completeness
         if ctx.act != L.ACT_NONE:
-            gp = torch.empty_like(pre)
-            rc = L.load().cmb_act_bwd(L.dtype_code(dt), ctx.act, g.data_ptr(), pre.data_ptr(), pre.numel(), gp.data_ptr(),
-                                      L.stream_ptr(g.device))
-            L.check(rc, "cmb_act_bwd")
-            g = gp
+            g = k_act_bwd(g, pre, ctx.act)
         dx = dw = db = None
         ks = _kstep(dt)
         if need_x:
@@ -877,27 +1069,14 @@ class LinearFn(torch.autograd.Function):
         elif ctx.link is not None and ctx.role == 1 and "g" in ctx.link:
             dx = ctx.link.pop("g")                       # (never expected: the sink was armed because x requires grad)
         if need_w:
-            if (dt == torch.bfloat16 and M > 0 and N % 8 == 0 and K % 8 == 0 and x.stride(1) == 1 and x.stride(0) % 8 == 0
-                    and x.data_ptr() % 16 == 0 and g.data_ptr() % 16 == 0 and g.stride(1) == 1 and g.stride(0) % 8 == 0
-                    and TN_WGRAD and _tn_wgrad_wins(M, N, K)):  # everything cmb_gemm_tn checks (gemm_tn_dispatch)
-                # dW = g^T x with g and x as they lie (cmb_gemm_tn: transposing LDS reads, rows beyond M contribute zero)
-                dw = k_gemm_tn(g, x, split_k=_tn_splits(N, K, M))
-            else:  # fp32 parity path / odd widths: transposed copies for the NT kernel
-                m_pad = pad_to(M, ks)
-                g_t = k_transpose(g, m_pad)  # [N, M_pad]
-                x_t = k_transpose(x, m_pad)  # [K, M_pad]
-                dw = k_gemm(g_t, x_t, out_dtype=torch.float32, split_k=_wgrad_splits(N, K, m_pad, ks))
-            if ctx.w_dtype != torch.float32:
-                dw = dw.to(ctx.w_dtype)
+            dw = _param_grad(_wgrad(g, x), ctx.w_dtype)
         if need_b and ctx.has_bias:
-            db = k_colsum(g)
-            if ctx.b_dtype != torch.float32:
-                db = db.to(ctx.b_dtype)
+            db = _param_grad(k_colsum(g), ctx.b_dtype)
         return dx, dw, db, None, dres, None, None, None, None, None
 
 
 # CAMBRIAN_AMD_LINK_RESIDUAL_GRADS=0: autograd sums the two gradients of a block's input itself (A/B runs)
-LINK_RESIDUAL_GRADS = os.environ.get("CAMBRIAN_AMD_LINK_RESIDUAL_GRADS", "1") != "0"
+LINK_RESIDUAL_GRADS = L.env_flag("CAMBRIAN_AMD_LINK_RESIDUAL_GRADS", True)
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, act: int = L.ACT_NONE,
@@ -927,16 +1106,14 @@ class LayerNormFn(torch.autograd.Function):
         x, g32, mean, rstd = ctx.saved_tensors
         dy = _as_dtype_contig(dy, x.dtype)
         dx, dgamma, dbeta, _ = k_layernorm_bwd(dy, x, mean, rstd, gamma=g32)
-        if ctx.p_dtype != torch.float32:
-            dgamma, dbeta = dgamma.to(ctx.p_dtype), dbeta.to(ctx.p_dtype)
-        return dx, dgamma, dbeta, None
+        return dx, _param_grad(dgamma, ctx.p_dtype), _param_grad(dbeta, ctx.p_dtype), None
 
 
 def layernorm(x, gamma, beta, eps: float = 1e-5):
     return LayerNormFn.apply(x, gamma, beta, eps)
 
 
-DEFER_LN_BWD = os.environ.get("CAMBRIAN_AMD_DEFER_LN_BWD", "1") != "0"   # (A/B runs: 0 = one LayerNorm backward per SVA layer)
+DEFER_LN_BWD = L.env_flag("CAMBRIAN_AMD_DEFER_LN_BWD", True)   # (A/B runs: 0 = one LayerNorm backward per SVA layer)
 # parked layers per flush (= the 5-layer launches of cmb_layernorm_bwd_multi, CMB_KNOB_LN_MULTI_CHUNK; 0 = only when the
 # shared-gradient node runs)
 DEFER_LN_FLUSH = int(os.environ.get("CAMBRIAN_AMD_DEFER_LN_FLUSH", "5"))
@@ -944,7 +1121,7 @@ DEFER_LN_FLUSH = int(os.environ.get("CAMBRIAN_AMD_DEFER_LN_FLUSH", "5"))
 
 # the last multi-layer launch of a tower's deferred LayerNorm backward writes d(x) in x's dtype (no separate cast of the fp32
 # accumulator); CAMBRIAN_AMD_LN_BWD_FINAL_CAST=0: accumulator + cmb_cast as before (A/B runs)
-LN_BWD_FINAL_CAST = os.environ.get("CAMBRIAN_AMD_LN_BWD_FINAL_CAST", "1") != "0"
+LN_BWD_FINAL_CAST = L.env_flag("CAMBRIAN_AMD_LN_BWD_FINAL_CAST", True)
 
 
 class GradAccumulator:
@@ -1029,7 +1206,7 @@ def k_layernorm_bwd_multi(x: torch.Tensor, items, side: int, grid_r: int, dx: to
         ws = torch.empty((max(L.load().cmb_layernorm_bwd_multi_workspace(C.byref(d)), 1),), dtype=torch.float32,
                          device=x.device)   # partial rows of the fixed-order table-gradient sums
         d.workspace, d.workspace_floats = ws.data_ptr(), ws.numel()
-        L.check(L.load().cmb_layernorm_bwd_multi(C.byref(d), L.stream_ptr(x.device)), "cmb_layernorm_bwd_multi")
+        L.call("cmb_layernorm_bwd_multi", C.byref(d), device=x.device)
 
 
 class SharedGradFn(torch.autograd.Function):
@@ -1089,7 +1266,7 @@ def shared_grad(x: torch.Tensor, holder: GradAccumulator, pos_params=()) -> torc
 # launches.  A slot is served from the multi-layer pass at most once per holder: re-computation forwards (activation
 # checkpointing) and geometries that differ from the first request's take the per-layer kernel.  The normalised tensors were
 # alive until the backward anyway (the attention core saves them).  CAMBRIAN_AMD_LN_FWD_MULTI=0: per-layer launches (A/B runs).
-LN_FWD_MULTI = os.environ.get("CAMBRIAN_AMD_LN_FWD_MULTI", "1") != "0"
+LN_FWD_MULTI = L.env_flag("CAMBRIAN_AMD_LN_FWD_MULTI", True)
 
 
 def _materialised(p: torch.Tensor) -> bool:
@@ -1165,9 +1342,7 @@ class SvaNormFn(torch.autograd.Function):
                                             want_dadd=need_pos)
         elif need_pos and add is not None:
             _, _, _, dpos = k_layernorm_bwd(dn, x, mean, rstd, add=add, side=ctx.side, grid_r=ctx.grid_r)
-        if dpos is not None and ctx.pos_dtype != torch.float32:
-            dpos = dpos.to(ctx.pos_dtype)
-        return None, dpos, None, None, None, None, None
+        return None, _param_grad(dpos, ctx.pos_dtype), None, None, None, None, None
 
 
 def sva_norm(x, pos, holder, side, grid_r, eps=1e-5):
@@ -1187,11 +1362,7 @@ class FoldKVFn(torch.autograd.Function):
             L.require_gpu(t)
             if t.dtype != torch.float32:
                 raise L.CambrianAmdError("fold_kv: fp32 tensors expected (ops.fold_kv up-casts other parameter dtypes)")
-        H, K = ts[0].shape
-        w = torch.empty((2 * H, K), dtype=torch.float32, device=ts[0].device)
-        b = torch.empty((2 * H,), dtype=torch.float32, device=ts[0].device)
-        rc = L.load().cmb_sva_fold_kv_fwd(*[t.data_ptr() for t in ts], H, K, w.data_ptr(), b.data_ptr(), L.stream_ptr(w.device))
-        L.check(rc, "cmb_sva_fold_kv_fwd")
+        w, b = k_fold_kv_fwd(ts)
         ctx.save_for_backward(*ts)
         return w, b
 
@@ -1202,12 +1373,7 @@ class FoldKVFn(torch.autograd.Function):
         dev = ts[0].device
         dw = torch.zeros((2 * H, K), dtype=torch.float32, device=dev) if dw is None else dw.contiguous().float()
         db = torch.zeros((2 * H,), dtype=torch.float32, device=dev) if db is None else db.contiguous().float()
-        outs = [torch.empty_like(t) for t in ts]
-        ws = torch.empty((L.load().cmb_sva_fold_kv_bwd_workspace(H, K) // 4,), dtype=torch.float32, device=dev)
-        rc = L.load().cmb_sva_fold_kv_bwd(dw.data_ptr(), db.data_ptr(), *[t.data_ptr() for t in ts], H, K,
-                                          *[o.data_ptr() for o in outs], ws.data_ptr(), ws.numel() * 4, L.stream_ptr(dev))
-        L.check(rc, "cmb_sva_fold_kv_bwd")
-        return tuple(outs)
+        return tuple(k_fold_kv_bwd(dw, db, ts))
 
 
 def fold_kv(wk, gk, bk, wv, gv, bv):
@@ -1324,9 +1490,7 @@ class HeadExpandFn(torch.autograd.Function):
             k_gemm_batched(dU, w_c, dx, batch=heads, M=Bq, N=hd, K=Cin, lda=heads * Cin, ldb=Cin, ldc=C, a_bs=Cin,
                            b_bs=hd * Cin, c_bs=hd)
         if ctx.needs_input_grad[1]:
-            dw = _per_head_wgrad(x, dU, heads, hd, Cin)
-            if ctx.w_dtype != torch.float32:
-                dw = dw.to(ctx.w_dtype)
+            dw = _param_grad(_per_head_wgrad(x, dU, heads, hd, Cin), ctx.w_dtype)
         return dx, dw, None
 
 
@@ -1369,9 +1533,7 @@ class HeadContractFn(torch.autograd.Function):
             k_gemm_batched(dy, w_t, dxb, batch=heads, M=Bq, N=Cin, K=hd, lda=C, ldb=w_t.stride(0), ldc=heads * Cin, a_bs=hd,
                            b_bs=hd, c_bs=Cin)
         if ctx.needs_input_grad[1]:
-            dw = _per_head_wgrad(dy, xb, heads, hd, Cin)
-            if ctx.w_dtype != torch.float32:
-                dw = dw.to(ctx.w_dtype)
+            dw = _param_grad(_per_head_wgrad(dy, xb, heads, hd, Cin), ctx.w_dtype)
         if len(ctx.needs_input_grad) < 4:     # called without an addend
             return dxb, dw, None
         return dxb, dw, None, (dy if ctx.needs_input_grad[3] else None)
@@ -1389,6 +1551,41 @@ def _fill_sva_abs(d, q, kvs, masks, xhat, mask_a, ra, U, bk, bv, B, qside, windo
     d.xhat, d.ldx = xhat.data_ptr(), xhat.stride(0)
     d.mask_a = None if mask_a is None else mask_a.data_ptr()
     d.U, d.bk, d.bv = U.data_ptr(), bk.data_ptr(), bv.data_ptr()
+
+
+def k_sva_abs_fwd(q, kvs, masks, xhat, mask_a, ra, U, bk, bv, B, qside, window_major):
+    """cmb_sva_abs_fwd -> (out [Bq, 1024], xbar [Bq, 16, 1024], m3 fp32 [Bq, 16], P fp32 [Bq, 16, 20])."""
+    Bq = q.shape[0]
+    out = torch.empty((Bq, 1024), dtype=q.dtype, device=q.device)
+    xbar = torch.empty((Bq, 16, 1024), dtype=q.dtype, device=q.device)
+    m3 = torch.empty((Bq, 16), dtype=torch.float32, device=q.device)
+    P = torch.empty((Bq, 16, 20), dtype=torch.float32, device=q.device)   # [0, 4) direct keys, [4, 20) window tokens
+    d = L.SvaAbsDesc()
+    _fill_sva_abs(d, q, kvs, masks, xhat, mask_a, ra, U, bk, bv, B, qside, window_major)
+    d.out, d.ldo, d.xbar, d.m3, d.P = out.data_ptr(), out.stride(0), xbar.data_ptr(), m3.data_ptr(), P.data_ptr()
+    L.call("cmb_sva_abs_fwd", C.byref(d), device=q.device)
+    return out, xbar, m3, P
+
+
+def k_sva_abs_bwd(dout, dxbar, q, kvs, masks, xhat, mask_a, ra, U, bk, bv, P, B, qside, window_major):
+    """cmb_sva_abs_bwd -> (dq, [dK|dV rows per direct tower], dU, d(cb) fp32 [Bq, 16], d xhat)."""
+    Bq, dev = q.shape[0], q.device
+    dq = torch.empty_like(q)
+    dkvs = [torch.empty_like(kv) for kv in kvs]
+    dU = torch.empty_like(U)
+    dcb = torch.empty((Bq, 16), dtype=torch.float32, device=dev)
+    dxhat = torch.empty((xhat.shape[0], 1024), dtype=q.dtype, device=dev)
+    d = L.SvaAbsDesc()
+    _fill_sva_abs(d, q, kvs, masks, xhat, mask_a, ra, U, bk, bv, B, qside, window_major)
+    # (the forward outputs are not read by the backward kernel, but the descriptor's forward fields must be set)
+    d.out, d.ldo, d.xbar, d.m3, d.P = dq.data_ptr(), dq.stride(0), dU.data_ptr(), dcb.data_ptr(), P.data_ptr()
+    d.dout, d.lddo, d.dxbar = dout.data_ptr(), dout.stride(0), dxbar.data_ptr()
+    d.dq, d.lddq = dq.data_ptr(), dq.stride(0)
+    for i, t in enumerate(dkvs):
+        d.dkv[i] = t.data_ptr()
+    d.dU, d.dcb, d.dxhat, d.lddx = dU.data_ptr(), dcb.data_ptr(), dxhat.data_ptr(), dxhat.stride(0)
+    L.call("cmb_sva_abs_bwd", C.byref(d), device=dev)
+    return dq, dkvs, dU, dcb, dxhat
 
 
 class SvaAbsorbedFn(torch.autograd.Function):
@@ -1411,14 +1608,7 @@ class SvaAbsorbedFn(torch.autograd.Function):
         kvs = [kv.contiguous() for kv in kvs]
         Uc = U.contiguous()
         bkc, bvc = bk.detach().to(torch.float32).contiguous(), bv.detach().to(torch.float32).contiguous()
-        out = torch.empty((Bq, 1024), dtype=q.dtype, device=q.device)
-        xbar = torch.empty((Bq, 16, 1024), dtype=q.dtype, device=q.device)
-        m3 = torch.empty((Bq, 16), dtype=torch.float32, device=q.device)
-        P = torch.empty((Bq, 16, 20), dtype=torch.float32, device=q.device)   # [0, 4) direct keys, [4, 20) window tokens
-        d = L.SvaAbsDesc()
-        _fill_sva_abs(d, q, kvs, masks, xhat, mask_a, ra, Uc, bkc, bvc, B, qside, window_major)
-        d.out, d.ldo, d.xbar, d.m3, d.P = out.data_ptr(), out.stride(0), xbar.data_ptr(), m3.data_ptr(), P.data_ptr()
-        L.check(L.load().cmb_sva_abs_fwd(C.byref(d), L.stream_ptr(q.device)), "cmb_sva_abs_fwd")
+        out, xbar, m3, P = k_sva_abs_fwd(q, kvs, masks, xhat, mask_a, ra, Uc, bkc, bvc, B, qside, window_major)
         ctx.cfg = (B, qside, ra, window_major)
         ctx.masks, ctx.mask_a = masks, mask_a
         ctx.b_dtypes = (bk.dtype, bv.dtype)
@@ -1430,25 +1620,10 @@ class SvaAbsorbedFn(torch.autograd.Function):
     def backward(ctx, dout, dxbar, _dm3):
         q, U, bk, bv, xhat, P, m3, *kvs = ctx.saved_tensors
         B, qside, ra, window_major = ctx.cfg
-        Bq = q.shape[0]
-        dev = q.device
         dout = torch.zeros_like(q) if dout is None else _as_dtype_contig(dout, q.dtype)
         dxbar = torch.zeros_like(U) if dxbar is None else _as_dtype_contig(dxbar, q.dtype)
-        dq = torch.empty_like(q)
-        dkvs = [torch.empty_like(kv) for kv in kvs]
-        dU = torch.empty_like(U)
-        dcb = torch.empty((Bq, 16), dtype=torch.float32, device=dev)
-        dxhat = torch.empty((xhat.shape[0], 1024), dtype=q.dtype, device=dev)
-        d = L.SvaAbsDesc()
-        _fill_sva_abs(d, q, kvs, ctx.masks, xhat, ctx.mask_a, ra, U, bk, bv, B, qside, window_major)
-        # (the forward outputs are not read by the backward kernel, but the descriptor's forward fields must be set)
-        d.out, d.ldo, d.xbar, d.m3, d.P = dq.data_ptr(), dq.stride(0), dU.data_ptr(), dcb.data_ptr(), P.data_ptr()
-        d.dout, d.lddo, d.dxbar = dout.data_ptr(), dout.stride(0), dxbar.data_ptr()
-        d.dq, d.lddq = dq.data_ptr(), dq.stride(0)
-        for i, t in enumerate(dkvs):
-            d.dkv[i] = t.data_ptr()
-        d.dU, d.dcb, d.dxhat, d.lddx = dU.data_ptr(), dcb.data_ptr(), dxhat.data_ptr(), dxhat.stride(0)
-        L.check(L.load().cmb_sva_abs_bwd(C.byref(d), L.stream_ptr(dev)), "cmb_sva_abs_bwd")
+        dq, dkvs, dU, dcb, dxhat = k_sva_abs_bwd(dout, dxbar, q, kvs, ctx.masks, xhat, ctx.mask_a, ra, U, bk, bv, P, B, qside,
+                                                 window_major)
         dbk = dbv = None
         if ctx.needs_input_grad[2]:   # d b_k[c] = sum_q d(cb)[q, h(c)] q[q, c]
             dbk = k_colsum(q, row_scale=dcb, group=64).to(ctx.b_dtypes[0])
@@ -1459,7 +1634,7 @@ class SvaAbsorbedFn(torch.autograd.Function):
 
 # CAMBRIAN_AMD_FUSE_CONTRACT_ADD=1: the one-key towers' output is added to the windowed tower's W_v Xb inside the per-head GEMM's
 # epilogue (a batched residual) instead of by an ATen add over [Bq, 1024].  Measured neutral (profiles/r06_lab.md section 25): off.
-FUSE_CONTRACT_ADD = os.environ.get("CAMBRIAN_AMD_FUSE_CONTRACT_ADD", "0") == "1"
+FUSE_CONTRACT_ADD = L.env_flag("CAMBRIAN_AMD_FUSE_CONTRACT_ADD", False)
 
 
 def sva_absorbed_attention(qh, kvs_direct, masks_direct, xhat, mask_a, ra: int, wk, bk, wv, bv, B: int, qside: int,
@@ -1501,8 +1676,7 @@ class TokenMeanFn(torch.autograd.Function):
             acc = ctx.holder.get(B * T, D, g.device)
         else:
             acc = torch.zeros((B * T, D), dtype=torch.float32, device=g.device)
-        rc = L.load().cmb_token_mean_bwd(L.dtype_code(g.dtype), g.data_ptr(), B, T, D, acc.data_ptr(), L.stream_ptr(g.device))
-        L.check(rc, "cmb_token_mean_bwd")
+        k_token_mean_bwd(g, B, T, D, acc)
         if ctx.holder is not None:
             return None, None
         return k_cast(acc, ctx.x_dtype).view(B, T, D), None
@@ -1525,13 +1699,8 @@ class EmbedSpliceFn(torch.autograd.Function):
         tab = k_cast(table, dt)
         nl = k_cast(newline, dt)
         featc = feat if feat.is_contiguous() else feat.contiguous()
-        out = torch.empty((B, S, H), dtype=dt, device=feat.device)
-        pos = torch.empty((B,), dtype=torch.int32, device=feat.device)
         idc = ids if ids.is_contiguous() else ids.contiguous()
-        rc = L.load().cmb_embed_splice_fwd(L.dtype_code(dt), idc.data_ptr(), B, S, H, image_token, tab.data_ptr(), V,
-                                           featc.data_ptr(), side, nl.data_ptr(), out.data_ptr(), pos.data_ptr(),
-                                           L.stream_ptr(feat.device))
-        L.check(rc, "cmb_embed_splice_fwd")
+        out, pos = k_embed_splice_fwd(idc, tab, featc, nl, side, image_token)
         ctx.cfg = (B, S, H, side, dt, newline.dtype, V, table.dtype, image_token)
         ctx.save_for_backward(pos, idc)
         ctx.mark_non_differentiable(pos)
@@ -1555,13 +1724,7 @@ class EmbedSpliceFn(torch.autograd.Function):
             dtable = torch.zeros((V, H), dtype=torch.float32, device=dout.device)
             dtable.index_add_(0, idx, dout[text].float())
             dtable = dtable.to(tab_dtype)
-        dfeat = torch.empty((B, side * side, H), dtype=dt, device=dout.device)
-        dnl = torch.zeros((H,), dtype=torch.float32, device=dout.device)
-        ws = torch.empty((max(B * side * H, 1),), dtype=torch.float32, device=dout.device)   # newline partial rows
-        rc = L.load().cmb_embed_splice_bwd(L.dtype_code(dt), dout.data_ptr(), pos.data_ptr(), B, S, H, side,
-                                           dfeat.data_ptr(), dnl.data_ptr(), ws.data_ptr(), ws.numel(),
-                                           L.stream_ptr(dout.device))
-        L.check(rc, "cmb_embed_splice_bwd")
+        dfeat, dnl = k_embed_splice_bwd(dout, pos, side)
         return None, dtable, dfeat, dnl.to(nl_dtype), None, None
 
 
@@ -1580,12 +1743,7 @@ class RmsNormFn(torch.autograd.Function):
         x2 = x.reshape(-1, D)
         x2 = x2 if x2.is_contiguous() else x2.contiguous()
         w32 = k_cast(weight, torch.float32)
-        rows = x2.shape[0]
-        y = torch.empty_like(x2)
-        rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
-        rc = L.load().cmb_rmsnorm_fwd(L.dtype_code(x.dtype), x2.data_ptr(), rows, D, w32.data_ptr(), eps, y.data_ptr(),
-                                      rstd.data_ptr(), L.stream_ptr(x.device))
-        L.check(rc, "cmb_rmsnorm_fwd")
+        y, rstd = k_rmsnorm_fwd(x2, w32, eps)
         ctx.save_for_backward(x2, w32, rstd)
         ctx.shape, ctx.w_dtype = shape, weight.dtype
         return y.view(shape)
@@ -1595,19 +1753,8 @@ class RmsNormFn(torch.autograd.Function):
         x2, w32, rstd = ctx.saved_tensors
         rows, D = x2.shape
         dy2 = _as_dtype_contig(dy.reshape(rows, D), x2.dtype)
-        dx = torch.empty_like(x2)
-        dw = torch.zeros((D,), dtype=torch.float32, device=x2.device) if ctx.needs_input_grad[1] else None
-        if dw is None:  # frozen weight: single-pass kernel (row kept in registers)
-            rc = L.load().cmb_rmsnorm_bwd_add(L.dtype_code(x2.dtype), dy2.data_ptr(), x2.data_ptr(), None, rows, D,
-                                              w32.data_ptr(), rstd.data_ptr(), dx.data_ptr(), L.stream_ptr(x2.device))
-            L.check(rc, "cmb_rmsnorm_bwd_add")
-        else:
-            rc = L.load().cmb_rmsnorm_bwd(L.dtype_code(x2.dtype), dy2.data_ptr(), x2.data_ptr(), rows, D, w32.data_ptr(),
-                                          rstd.data_ptr(), dx.data_ptr(), L.ptr(dw), L.stream_ptr(x2.device))
-            L.check(rc, "cmb_rmsnorm_bwd")
-        if dw is not None and ctx.w_dtype != torch.float32:
-            dw = dw.to(ctx.w_dtype)
-        return dx.view(ctx.shape), dw, None
+        dx, dw = k_rmsnorm_bwd(dy2, x2, w32, rstd, want_dw=ctx.needs_input_grad[1])
+        return dx.view(ctx.shape), _param_grad(dw, ctx.w_dtype), None
 
 
 def rmsnorm(x, weight, eps: float = 1e-6):
@@ -1622,20 +1769,8 @@ class RmsNormForkFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, eps: float):
-        shape = x.shape
-        D = shape[-1]
-        x2 = x.reshape(-1, D)
-        x2 = x2 if x2.is_contiguous() else x2.contiguous()
-        w32 = k_cast(weight, torch.float32)
-        rows = x2.shape[0]
-        y = torch.empty_like(x2)
-        rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
-        rc = L.load().cmb_rmsnorm_fwd(L.dtype_code(x.dtype), x2.data_ptr(), rows, D, w32.data_ptr(), eps, y.data_ptr(),
-                                      rstd.data_ptr(), L.stream_ptr(x.device))
-        L.check(rc, "cmb_rmsnorm_fwd")
-        ctx.save_for_backward(x2, w32, rstd)
-        ctx.shape, ctx.w_dtype = shape, weight.dtype
-        return x, y.view(shape)          # x returned as is: autograd hands out an alias of it
+        # RmsNormFn's forward on this node's ctx (same launch, same saved tensors); x returned as is: autograd hands out an alias
+        return x, RmsNormFn.forward(ctx, x, weight, eps)
 
     @staticmethod
     def backward(ctx, g_x, g_y):
@@ -1645,27 +1780,14 @@ class RmsNormForkFn(torch.autograd.Function):
             return g_x, None, None
         gy = _as_dtype_contig(g_y.reshape(rows, D), x2.dtype)
         gs = None if g_x is None else _as_dtype_contig(g_x.reshape(rows, D), x2.dtype)
-        dx = torch.empty_like(x2)
-        dw = None
-        if ctx.needs_input_grad[1]:  # trainable norm weight (finetune stage): the two-pass kernel that also reduces dw
-            dw = torch.zeros((D,), dtype=torch.float32, device=x2.device)
-            rc = L.load().cmb_rmsnorm_bwd(L.dtype_code(x2.dtype), gy.data_ptr(), x2.data_ptr(), rows, D, w32.data_ptr(),
-                                          rstd.data_ptr(), dx.data_ptr(), dw.data_ptr(), L.stream_ptr(x2.device))
-            L.check(rc, "cmb_rmsnorm_bwd")
-            if gs is not None:
-                dx = dx + gs
-            if ctx.w_dtype != torch.float32:
-                dw = dw.to(ctx.w_dtype)
-        else:
-            rc = L.load().cmb_rmsnorm_bwd_add(L.dtype_code(x2.dtype), gy.data_ptr(), x2.data_ptr(), L.ptr(gs), rows, D,
-                                              w32.data_ptr(), rstd.data_ptr(), dx.data_ptr(), L.stream_ptr(x2.device))
-            L.check(rc, "cmb_rmsnorm_bwd_add")
+        # (a trainable norm weight — finetune stage — takes the two-pass kernel that also reduces dw: k_rmsnorm_bwd)
+        dx, dw = k_rmsnorm_bwd(gy, x2, w32, rstd, add=gs, want_dw=ctx.needs_input_grad[1])
         out = dx.view(ctx.shape)
         # a buffer this call allocated and hands to exactly one receiver: whoever gets THIS object as its incoming gradient may
         # write into it (ScatterQueryRowsFn.backward: no 400 MB clone per in-LLM SVA layer).  Autograd's own sums of several
         # gradients are new tensors without the mark.
         out._cmb_exclusive = True
-        return out, dw, None
+        return out, _param_grad(dw, ctx.w_dtype), None
 
 
 def rmsnorm_fork(x, weight, eps: float = 1e-6):
@@ -1680,9 +1802,7 @@ def rope_table(position_ids: torch.Tensor, head_dim: int, base: float) -> Tuple[
     ntok = pid.numel()
     cos = torch.empty((ntok, head_dim // 2), dtype=torch.float32, device=pid.device)
     sin = torch.empty_like(cos)
-    rc = L.load().cmb_rope_table(pid.data_ptr(), ntok, head_dim, base, cos.data_ptr(), sin.data_ptr(),
-                                 L.stream_ptr(pid.device))
-    L.check(rc, "cmb_rope_table")
+    L.call("cmb_rope_table", pid.data_ptr(), ntok, head_dim, base, cos.data_ptr(), sin.data_ptr(), device=pid.device)
     return cos, sin
 
 
@@ -1691,23 +1811,13 @@ class RopeFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, cos, sin):
-        y = x.contiguous().clone()
-        ntok, H, Dh = y.shape
-        rc = L.load().cmb_rope_apply(L.dtype_code(y.dtype), y.data_ptr(), cos.data_ptr(), sin.data_ptr(), ntok, H, Dh,
-                                     H * Dh, 0, L.stream_ptr(y.device))
-        L.check(rc, "cmb_rope_apply")
         ctx.save_for_backward(cos, sin)
-        return y
+        return k_rope_apply(x.contiguous().clone(), cos, sin)
 
     @staticmethod
     def backward(ctx, dy):
         cos, sin = ctx.saved_tensors
-        g = dy.contiguous().clone()
-        ntok, H, Dh = g.shape
-        rc = L.load().cmb_rope_apply(L.dtype_code(g.dtype), g.data_ptr(), cos.data_ptr(), sin.data_ptr(), ntok, H, Dh,
-                                     H * Dh, 1, L.stream_ptr(g.device))
-        L.check(rc, "cmb_rope_apply(inverse)")
-        return g, None, None
+        return k_rope_apply(dy.contiguous().clone(), cos, sin, inverse=True), None, None
 
 
 def rope(x, cos, sin):
@@ -1720,9 +1830,8 @@ def rope(x, cos, sin):
 def k_copy_rows(src: Optional[torch.Tensor], src_map: Optional[RowMap], dst: torch.Tensor, dst_map: RowMap, rows: int,
                 D: int) -> None:
     L.require_gpu(src, dst)
-    rc = L.load().cmb_copy_rows(L.dtype_code(dst.dtype), L.ptr(src), None if src_map is None else C.byref(src_map),
-                                dst.data_ptr(), C.byref(dst_map), rows, D, L.stream_ptr(dst.device))
-    L.check(rc, "cmb_copy_rows")
+    L.call("cmb_copy_rows", L.dtype_code(dst.dtype), L.ptr(src), None if src_map is None else C.byref(src_map), dst.data_ptr(),
+           C.byref(dst_map), rows, D, device=dst.device)
 
 
 def hook_row_map(S: int, H: int, side: int) -> RowMap:
@@ -1819,16 +1928,10 @@ class CrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, ignore_index: int, inplace: bool):
         L.require_gpu(logits, labels)
-        T, V = logits.shape
         if logits.stride(1) != 1:
             raise L.CambrianAmdError("logits must be row-major")
         labels = labels.to(torch.int64).contiguous()
-        lse = torch.empty((T,), dtype=torch.float32, device=logits.device)
-        loss_rows = torch.empty((T,), dtype=torch.float32, device=logits.device)
-        rc = L.load().cmb_cross_entropy_fwd(L.dtype_code(logits.dtype), logits.data_ptr(), T, V, logits.stride(0),
-                                            labels.data_ptr(), ignore_index, lse.data_ptr(), loss_rows.data_ptr(),
-                                            L.stream_ptr(logits.device))
-        L.check(rc, "cmb_cross_entropy_fwd")
+        lse, loss_rows = k_cross_entropy_fwd(logits, labels, ignore_index)
         n_valid = (labels != ignore_index).sum().to(torch.float32)
         ctx.save_for_backward(logits, labels, lse, n_valid)
         ctx.ignore_index, ctx.inplace = ignore_index, inplace
@@ -1837,13 +1940,9 @@ class CrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         logits, labels, lse, n_valid = ctx.saved_tensors
-        T, V = logits.shape
         scale = (g.to(torch.float32) / n_valid).reshape(1).contiguous()
         out = logits if ctx.inplace else torch.empty_like(logits)
-        rc = L.load().cmb_cross_entropy_bwd(L.dtype_code(logits.dtype), logits.data_ptr(), T, V, logits.stride(0),
-                                            labels.data_ptr(), ctx.ignore_index, lse.data_ptr(), scale.data_ptr(),
-                                            out.data_ptr(), out.stride(0), L.stream_ptr(logits.device))
-        L.check(rc, "cmb_cross_entropy_bwd")
+        k_cross_entropy_bwd(logits, labels, ctx.ignore_index, lse, scale, out)
         return out, None, None, None
 
 
@@ -1862,11 +1961,7 @@ class SwiGLUFn(torch.autograd.Function):
         g2, u2 = g.reshape(-1, D), u.reshape(-1, D)
         if g2.stride(1) != 1 or u2.stride(1) != 1:
             g2, u2 = g2.contiguous(), u2.contiguous()
-        rows = g2.shape[0]
-        h = torch.empty((rows, D), dtype=g.dtype, device=g.device)
-        rc = L.load().cmb_act_mul(L.dtype_code(g.dtype), L.ACT_SILU, g2.data_ptr(), g2.stride(0), u2.data_ptr(), u2.stride(0),
-                                  rows, D, h.data_ptr(), D, L.stream_ptr(g.device))
-        L.check(rc, "cmb_act_mul(silu)")
+        h = k_swiglu_fwd(g2, u2)
         ctx.save_for_backward(g2, u2)
         ctx.shape = shape
         return h.view(shape)
@@ -1880,10 +1975,7 @@ class SwiGLUFn(torch.autograd.Function):
             dh2 = dh2.contiguous()
         dg = torch.empty((rows, D), dtype=g2.dtype, device=g2.device)
         du = torch.empty((rows, D), dtype=g2.dtype, device=g2.device)
-        rc = L.load().cmb_swiglu_bwd(L.dtype_code(g2.dtype), dh2.data_ptr(), dh2.stride(0), g2.data_ptr(), g2.stride(0),
-                                     u2.data_ptr(), u2.stride(0), rows, D, dg.data_ptr(), D, du.data_ptr(), D,
-                                     L.stream_ptr(g2.device))
-        L.check(rc, "cmb_swiglu_bwd")
+        k_swiglu_bwd(dh2, g2, u2, dg, du)
         return dg.view(ctx.shape), du.view(ctx.shape)
 
 
@@ -1906,9 +1998,7 @@ class QkvRopeFn(torch.autograd.Function):
         q = torch.empty((B, S, nh, hd), dtype=dt, device=dev)
         k = torch.empty((B, S, nkv, hd), dtype=dt, device=dev)
         v = torch.empty((B, S, nkv, hd), dtype=dt, device=dev)
-        rc = L.load().cmb_qkv_rope(L.dtype_code(dt), 0, packed.data_ptr(), cos.data_ptr(), sin.data_ptr(), B, S, nh, nkv, hd,
-                                   q.data_ptr(), k.data_ptr(), v.data_ptr(), L.stream_ptr(dev))
-        L.check(rc, "cmb_qkv_rope(split)")
+        k_qkv_rope(packed, cos, sin, q, k, v)
         ctx.save_for_backward(cos, sin)
         ctx.cfg = (B, S, nh, nkv, hd)
         return q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2)  # [B,H,S,hd] views of token-major storage
@@ -1920,9 +2010,7 @@ class QkvRopeFn(torch.autograd.Function):
         # token-major storage; free when the attention backward returns grads laid out like its inputs
         dq, dk, dv = (t.transpose(1, 2).contiguous() for t in (dq, dk, dv))
         dp = torch.empty((B, S, (nh + 2 * nkv) * hd), dtype=dq.dtype, device=dq.device)
-        rc = L.load().cmb_qkv_rope(L.dtype_code(dq.dtype), 1, dp.data_ptr(), cos.data_ptr(), sin.data_ptr(), B, S, nh, nkv, hd,
-                                   dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), L.stream_ptr(dq.device))
-        L.check(rc, "cmb_qkv_rope(merge)")
+        k_qkv_rope(dp, cos, sin, dq, dk, dv, merge=True)
         return dp, None, None, None, None, None
 
 
@@ -1943,12 +2031,7 @@ class SwiGLUPackedFn(torch.autograd.Function):
         g2 = gu.reshape(-1, I2)
         if not g2.is_contiguous():
             g2 = g2.contiguous()
-        rows = g2.shape[0]
-        h = torch.empty((rows, I), dtype=gu.dtype, device=gu.device)
-        es = g2.element_size()
-        rc = L.load().cmb_act_mul(L.dtype_code(gu.dtype), L.ACT_SILU, g2.data_ptr(), I2, g2.data_ptr() + I * es, I2,
-                                  rows, I, h.data_ptr(), I, L.stream_ptr(gu.device))
-        L.check(rc, "cmb_act_mul(silu, packed)")
+        h = k_swiglu_fwd(g2, g2, cols=I, u_col=I, what="cmb_act_mul(silu, packed)")
         ctx.save_for_backward(g2)
         ctx.shape = shape
         return h.view(*shape[:-1], I)
@@ -1962,11 +2045,7 @@ class SwiGLUPackedFn(torch.autograd.Function):
         if dh2.stride(1) != 1:
             dh2 = dh2.contiguous()
         dgu = torch.empty((rows, I2), dtype=g2.dtype, device=g2.device)
-        es = g2.element_size()
-        rc = L.load().cmb_swiglu_bwd(L.dtype_code(g2.dtype), dh2.data_ptr(), dh2.stride(0), g2.data_ptr(), I2,
-                                     g2.data_ptr() + I * es, I2, rows, I, dgu.data_ptr(), I2, dgu.data_ptr() + I * es, I2,
-                                     L.stream_ptr(g2.device))
-        L.check(rc, "cmb_swiglu_bwd(packed)")
+        k_swiglu_bwd(dh2, g2, g2, dgu, dgu, cols=I, u_col=I, what="cmb_swiglu_bwd(packed)")
         return dgu.view(ctx.shape)
 
 
@@ -1994,22 +2073,16 @@ class CausalAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, scale=None, kv_len=None, key_valid=None):
         L.require_gpu(q, k, v, key_valid)
-        B, H, S, D = q.shape
-        HKV = k.shape[1]
+        B, _, S, D = q.shape
         scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
         causal, n = (1, S) if kv_len is None else (0, int(kv_len))
         q, k, v = _token_major(q), _token_major(k), _token_major(v)
-        out = torch.empty((B, S, H, D), dtype=q.dtype, device=q.device)
-        lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
         if key_valid is not None:
             if not causal or key_valid.shape != (B, S):
                 raise L.CambrianAmdError("key_valid is a [B, S] mask of the causal form")
             key_valid = key_valid.view(torch.uint8) if key_valid.dtype == torch.bool else key_valid.to(torch.uint8)
             key_valid = key_valid.contiguous()
-        rc = L.load().cmb_flash_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), B, S, H, HKV, D, S * H * D, H * D, D,
-                                         S * HKV * D, HKV * D, D, scale, causal, n, L.ptr(key_valid), out.data_ptr(),
-                                         lse.data_ptr(), L.stream_ptr(q.device))
-        L.check(rc, "cmb_flash_attn_fwd")
+        out, lse = k_flash_attn_fwd(q, k, v, scale, causal, n, key_valid)
         out = out.transpose(1, 2)  # [B,H,S,D] view of token-major storage: the o_proj input needs no copy
         ctx.save_for_backward(q, k, v, out, lse)
         ctx.key_valid = key_valid
@@ -2020,20 +2093,9 @@ class CausalAttnFn(torch.autograd.Function):
     def backward(ctx, dout):
         q, k, v, out, lse = ctx.saved_tensors
         scale, causal, n = ctx.cfg
-        B, H, S, D = q.shape
-        HKV = k.shape[1]
         q, out, dout = _token_major(q), _token_major(out), _token_major(dout)
         k, v = _token_major(k), _token_major(v)
-        dq = torch.empty((B, S, H, D), dtype=q.dtype, device=q.device)
-        dk = torch.empty((B, S, HKV, D), dtype=q.dtype, device=q.device)
-        dv = torch.empty((B, S, HKV, D), dtype=q.dtype, device=q.device)
-        dvec = torch.empty((2, B, H, S), dtype=torch.float32, device=q.device)   # [0] D, [1] lse * log2 e (flash2.hip)
-        lse = lse.contiguous()
-        rc = L.load().cmb_flash_attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(),
-                                         lse.data_ptr(), B, S, H, HKV, D, S * H * D, H * D, D, S * HKV * D, HKV * D, D,
-                                         scale, causal, n, L.ptr(ctx.key_valid), dvec.data_ptr(), dq.data_ptr(),
-                                         dk.data_ptr(), dv.data_ptr(), L.stream_ptr(q.device))
-        L.check(rc, "cmb_flash_attn_bwd")
+        dq, dk, dv = k_flash_attn_bwd(q, k, v, out, dout, lse.contiguous(), scale, causal, n, ctx.key_valid)
         return dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2), None, None, None
 
 
@@ -2119,25 +2181,23 @@ def decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: tor
     elif key_valid.dtype != torch.uint8:
         raise L.CambrianAmdError("decode_attention: key_valid is a bool / uint8 mask")
     scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
-    lib = L.load()
-    need = lib.cmb_decode_attn_ws(B, nh, nkv, hd, t, splits)
+    need = L.load().cmb_decode_attn_ws(B, nh, nkv, hd, t, splits)
     if need < 0:
         L.check(int(need), "cmb_decode_attn_ws")
     ws = _DECODE_WS.get(q.device)
     if need > 0 and (ws is None or ws.numel() < need):
         ws = _DECODE_WS[q.device] = torch.empty(int(need), dtype=torch.float32, device=q.device)
     out = torch.empty((B, nh * hd), dtype=dt, device=q.device)
-    rc = lib.cmb_decode_attn(L.dtype_code(dt), q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
-                             cos.data_ptr(), sin.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), kcache.stride(0),
-                             kcache.stride(1), kcache.stride(2), B, nh, nkv, hd, t, key_valid.data_ptr(), key_valid.stride(0),
-                             scale, splits, L.ptr(ws) if need > 0 else None, int(need), out.data_ptr(), L.stream_ptr(q.device))
-    L.check(rc, "cmb_decode_attn")
+    L.call("cmb_decode_attn", L.dtype_code(dt), q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+           cos.data_ptr(), sin.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), kcache.stride(0), kcache.stride(1),
+           kcache.stride(2), B, nh, nkv, hd, t, key_valid.data_ptr(), key_valid.stride(0), scale, splits,
+           L.ptr(ws) if need > 0 else None, int(need), out.data_ptr(), device=q.device)
     return out
 
 
 def decode_attention_enabled() -> bool:
     """``CAMBRIAN_AMD_DECODE_ATTN=0`` in the environment: decode steps take the stock SDPA branch (A/B runs)."""
-    return os.environ.get("CAMBRIAN_AMD_DECODE_ATTN", "1") != "0"
+    return L.env_flag("CAMBRIAN_AMD_DECODE_ATTN", True)
 
 
 # ================================================================================================
@@ -2206,14 +2266,12 @@ def grad_sqnorm(grads: Sequence[torch.Tensor]) -> torch.Tensor:
     grads = [g if g.is_contiguous() else g.contiguous() for g in grads]
     table, n, chunks = _optim_table(grads)
     dev = grads[0].device
-    lib = L.load()
-    need = int(lib.cmb_grad_sqnorm_workspace(chunks))
+    need = int(L.load().cmb_grad_sqnorm_workspace(chunks))
     ws = _OPTIM_WS.get(dev)
     if ws is None or ws.numel() < max(need, 1):
         ws = _OPTIM_WS[dev] = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
     out = torch.empty((), dtype=torch.float32, device=dev)
-    L.check(lib.cmb_grad_sqnorm(table.data_ptr(), n, chunks, ws.data_ptr(), ws.numel(), out.data_ptr(), L.stream_ptr(dev)),
-            "cmb_grad_sqnorm")
+    L.call("cmb_grad_sqnorm", table.data_ptr(), n, chunks, ws.data_ptr(), ws.numel(), out.data_ptr(), device=dev)
     return out
 
 
@@ -2238,9 +2296,8 @@ def adamw_step(grads: Sequence[torch.Tensor], params: Sequence[torch.Tensor], ex
         raise L.CambrianAmdError("adamw_step: sumsq is the fp32 device scalar of grad_sqnorm")
     table, n, chunks = _optim_table(grads, params, lows, exp_avgs, exp_avg_sqs)
     dev = grads[0].device
-    rc = L.load().cmb_adamw_step(table.data_ptr(), n, chunks, lr, beta1, beta2, eps, weight_decay, 1.0 - beta1 ** step,
-                                 1.0 - beta2 ** step, grad_scale, L.ptr(sumsq), max_norm, L.stream_ptr(dev))
-    L.check(rc, "cmb_adamw_step")
+    L.call("cmb_adamw_step", table.data_ptr(), n, chunks, lr, beta1, beta2, eps, weight_decay, 1.0 - beta1 ** step,
+           1.0 - beta2 ** step, grad_scale, L.ptr(sumsq), max_norm, device=dev)
 
 
 # ================================================================================================
@@ -2250,7 +2307,7 @@ def adamw_step(grads: Sequence[torch.Tensor], params: Sequence[torch.Tensor], ex
 def resample_enabled() -> bool:
     """``CAMBRIAN_AMD_RESAMPLE_BWD=0`` in the environment: every resize that carries a gradient (and the eval-path query-group
     resize) takes the ATen body — permute, fp32 up-cast, ``F.interpolate``, cast, permute (A/B runs)."""
-    return os.environ.get("CAMBRIAN_AMD_RESAMPLE_BWD", "1") != "0"
+    return L.env_flag("CAMBRIAN_AMD_RESAMPLE_BWD", True)
 
 
 def resample_supported(dtype: torch.dtype, channels: int) -> bool:
@@ -2274,26 +2331,58 @@ def _vec8_rows(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous()
 
 
+def k_resample(x: torch.Tensor, hi: int, wi: int, out: torch.Tensor, ho: int, wo: int, col_offset: int = 0) -> None:
+    """x [B, hi*wi, C] -> out[:, :, col_offset:col_offset+C] with out [B, ho*wo, Ctot] (bilinear, fp32 lerp)."""
+    L.require_gpu(x, out)
+    B, T, C = x.shape
+    assert T == hi * wi and out.shape[0] == B and out.shape[1] == ho * wo and x.stride(2) == 1 and out.stride(2) == 1
+    optr = out.data_ptr() + col_offset * out.element_size()
+    L.call("cmb_resample_bilinear", L.dtype_code(x.dtype), x.data_ptr(), B, hi, wi, C, x.stride(1), x.stride(0), optr, ho, wo,
+           out.stride(1), out.stride(0), device=x.device)
+
+
+def k_resample_bwd(dout: torch.Tensor, ho: int, wo: int, dx: torch.Tensor, hi: int, wi: int, col_offset: int = 0) -> None:
+    """Adjoint of ``k_resample``: dout[:, :, col_offset:col_offset+C] with dout [B, ho*wo, Ctot] -> dx [B, hi*wi, C], written in
+    full (cells no output refers to get 0).  Gather form in a fixed order: no atomics, bit-reproducible."""
+    L.require_gpu(dout, dx)
+    B, T, C = dx.shape
+    assert T == hi * wi and dout.shape[0] == B and dout.shape[1] == ho * wo and dx.stride(2) == 1 and dout.stride(2) == 1
+    assert dout.dtype == dx.dtype and 0 <= col_offset and col_offset + C <= dout.shape[2]
+    gptr = dout.data_ptr() + col_offset * dout.element_size()
+    L.call("cmb_resample_bilinear_bwd", L.dtype_code(dx.dtype), gptr, B, ho, wo, C, dout.stride(1), dout.stride(0), dx.data_ptr(),
+           hi, wi, dx.stride(1), dx.stride(0), device=dx.device)
+
+
+def _resample_maps(maps: Sequence[torch.Tensor], side: int) -> torch.Tensor:
+    """maps [B, Hs, Ws, Cs] -> a new [B, side*side, sum Cs]: one ``k_resample`` per map into its column slice of the one buffer."""
+    B = maps[0].shape[0]
+    out = torch.empty((B, side * side, sum(m.shape[3] for m in maps)), dtype=maps[0].dtype, device=maps[0].device)
+    off = 0
+    for m in maps:
+        _, Hs, Ws, Cs = m.shape
+        k_resample(_vec8_rows(m.reshape(B, Hs * Ws, Cs)), Hs, Ws, out, side, side, col_offset=off)
+        off += Cs
+    return out
+
+
 class ResampleBilinearFn(torch.autograd.Function):
     """x [B, hi*wi, C] (strided rows are read in place) -> [B, ho*wo, C]; backward = the adjoint gather kernel."""
 
     @staticmethod
     def forward(ctx, x, hi: int, wi: int, ho: int, wo: int):
-        from .model.multimodal_encoder import vit_ops
         x = _vec8_rows(x)
         B, _, C = x.shape
         out = torch.empty((B, ho * wo, C), dtype=x.dtype, device=x.device)
-        vit_ops.k_resample(x, hi, wi, out, ho, wo)
+        k_resample(x, hi, wi, out, ho, wo)
         ctx.grids = (hi, wi, ho, wo)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        from .model.multimodal_encoder import vit_ops
         hi, wi, ho, wo = ctx.grids
         g = _vec8_rows(g)
         dx = torch.empty((g.shape[0], hi * wi, g.shape[2]), dtype=g.dtype, device=g.device)
-        vit_ops.k_resample_bwd(g, ho, wo, dx, hi, wi)
+        k_resample_bwd(g, ho, wo, dx, hi, wi)
         return dx, None, None, None, None
 
 
@@ -2317,27 +2406,18 @@ class ResampleConcatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, side: int, *maps):
-        from .model.multimodal_encoder import vit_ops
-        B = maps[0].shape[0]
-        out = torch.empty((B, side * side, sum(m.shape[3] for m in maps)), dtype=maps[0].dtype, device=maps[0].device)
-        off = 0
-        for m in maps:
-            _, Hs, Ws, Cs = m.shape
-            vit_ops.k_resample(_vec8_rows(m.reshape(B, Hs * Ws, Cs)), Hs, Ws, out, side, side, col_offset=off)
-            off += Cs
         ctx.side, ctx.shapes = side, [tuple(m.shape) for m in maps]
-        return out
+        return _resample_maps(maps, side)
 
     @staticmethod
     def backward(ctx, g):
-        from .model.multimodal_encoder import vit_ops
         g = _vec8_rows(g)
         grads, off = [], 0
         for k, (B, Hs, Ws, Cs) in enumerate(ctx.shapes):
             dx = None
             if ctx.needs_input_grad[1 + k]:
                 dx = torch.empty((B, Hs * Ws, Cs), dtype=g.dtype, device=g.device)
-                vit_ops.k_resample_bwd(g, ctx.side, ctx.side, dx, Hs, Ws, col_offset=off)
+                k_resample_bwd(g, ctx.side, ctx.side, dx, Hs, Ws, col_offset=off)
                 dx = dx.view(B, Hs, Ws, Cs)
             grads.append(dx)
             off += Cs
@@ -2373,13 +2453,7 @@ class AddRmsNormFn(torch.autograd.Function):
         if d2.dtype != x2.dtype:
             d2 = d2.to(x2.dtype)
         w32 = k_cast(weight, torch.float32)
-        rows = x2.shape[0]
-        s = torch.empty_like(x2)
-        y = torch.empty_like(x2)
-        rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
-        rc = L.load().cmb_add_rmsnorm_fwd(L.dtype_code(x2.dtype), x2.data_ptr(), d2.data_ptr(), rows, D, w32.data_ptr(), eps,
-                                          s.data_ptr(), y.data_ptr(), rstd.data_ptr(), L.stream_ptr(x.device))
-        L.check(rc, "cmb_add_rmsnorm_fwd")
+        s, y, rstd = k_add_rmsnorm_fwd(x2, d2, w32, eps)
         ctx.save_for_backward(s, w32, rstd)
         ctx.shape, ctx.w_dtype = shape, weight.dtype
         return s.view(shape), y.view(shape)
@@ -2388,28 +2462,13 @@ class AddRmsNormFn(torch.autograd.Function):
     def backward(ctx, g_s, g_y):
         s, w32, rstd = ctx.saved_tensors
         rows, D = s.shape
-        need_w = ctx.needs_input_grad[2]
         if g_y is None:
             return g_s, g_s, None, None
         gy = _as_dtype_contig(g_y.reshape(rows, D), s.dtype)
         gs = None if g_s is None else _as_dtype_contig(g_s.reshape(rows, D), s.dtype)
-        dw = None
-        dx = torch.empty_like(s)
-        if need_w:  # trainable norm weight (finetune stage): the two-pass kernel that also reduces dw
-            dw = torch.zeros((D,), dtype=torch.float32, device=s.device)
-            rc = L.load().cmb_rmsnorm_bwd(L.dtype_code(s.dtype), gy.data_ptr(), s.data_ptr(), rows, D, w32.data_ptr(),
-                                          rstd.data_ptr(), dx.data_ptr(), dw.data_ptr(), L.stream_ptr(s.device))
-            L.check(rc, "cmb_rmsnorm_bwd")
-            if gs is not None:
-                dx = dx + gs
-            if ctx.w_dtype != torch.float32:
-                dw = dw.to(ctx.w_dtype)
-        else:
-            rc = L.load().cmb_rmsnorm_bwd_add(L.dtype_code(s.dtype), gy.data_ptr(), s.data_ptr(), L.ptr(gs), rows, D,
-                                              w32.data_ptr(), rstd.data_ptr(), dx.data_ptr(), L.stream_ptr(s.device))
-            L.check(rc, "cmb_rmsnorm_bwd_add")
-        dx = dx.view(ctx.shape)
-        return dx, dx, dw, None
+        dx, dw = k_rmsnorm_bwd(gy, s, w32, rstd, add=gs, want_dw=ctx.needs_input_grad[2])
+        dx = dx.view(ctx.shape)    # one tensor for two inputs: not marked as handed to one receiver (RmsNormForkFn)
+        return dx, dx, _param_grad(dw, ctx.w_dtype), None
 
 
 def add_rmsnorm(x, delta, weight, eps: float = 1e-6):
@@ -2426,7 +2485,7 @@ def add_rmsnorm(x, delta, weight, eps: float = 1e-6):
 def commuted_proj_enabled(config=None) -> bool:
     """``CAMBRIAN_AMD_COMMUTED_PROJ=1`` in the environment (read at call time) or ``config.mm_commuted_aux_projection``.
     Off by default: every path is then exactly what it was."""
-    return os.environ.get("CAMBRIAN_AMD_COMMUTED_PROJ", "0") == "1" or bool(getattr(config, "mm_commuted_aux_projection", False))
+    return L.env_flag("CAMBRIAN_AMD_COMMUTED_PROJ", False) or bool(getattr(config, "mm_commuted_aux_projection", False))
 
 
 # partial products (the dense stages' ``base`` and every commuted stage's Y_s) in fp32: the pre-activation is then rounded
@@ -2434,7 +2493,7 @@ def commuted_proj_enabled(config=None) -> bool:
 # price is the wider base / Y_s traffic of cmb_resample_accum.  CAMBRIAN_AMD_COMMUTED_PROJ_F32=0 keeps them in the compute
 # dtype (A/B runs, tools/bench_commuted_proj.py).
 def _commuted_f32_partials() -> bool:
-    return os.environ.get("CAMBRIAN_AMD_COMMUTED_PROJ_F32", "1") != "0"
+    return L.env_flag("CAMBRIAN_AMD_COMMUTED_PROJ_F32", True)
 
 
 def stage_maps_plan(grids, out_side: int) -> List[bool]:
@@ -2486,7 +2545,7 @@ def k_resample_accum(out: torch.Tensor, ho: int, wo: int, *, base: Optional[torc
     d.pre_out = L.ptr(pre_out)
     d.ld_pre, d.batch_stride_pre = (pre_out.stride(1), pre_out.stride(0)) if pre_out is not None else (0, 0)
     d.out, d.ld_out, d.batch_stride_out = out.data_ptr(), out.stride(1), out.stride(0)
-    L.check(L.load().cmb_resample_accum(C.byref(d), L.stream_ptr(out.device)), "cmb_resample_accum")
+    L.call("cmb_resample_accum", C.byref(d), device=out.device)
     return out
 
 
@@ -2505,15 +2564,7 @@ def concat_stage_maps(maps: Sequence[torch.Tensor], out_side: int) -> torch.Tens
     maps = list(maps)
     if torch.is_grad_enabled() and any(m.requires_grad for m in maps):
         return resample_concat(maps, out_side)
-    from .model.multimodal_encoder import vit_ops
-    B = maps[0].shape[0]
-    out = torch.empty((B, out_side * out_side, sum(m.shape[3] for m in maps)), dtype=maps[0].dtype, device=maps[0].device)
-    off = 0
-    for m in maps:
-        _, Hs, Ws, Cs = m.shape
-        vit_ops.k_resample(_vec8_rows(m.reshape(B, Hs * Ws, Cs)), Hs, Ws, out, out_side, out_side, col_offset=off)
-        off += Cs
-    return out
+    return _resample_maps(maps, out_side)
 
 
 class StageMaps:
@@ -2544,28 +2595,11 @@ class StageMaps:
         return concat_stage_maps(self.maps, self.side)
 
 
-def _wgrad_into(g: torch.Tensor, x: torch.Tensor, out: torch.Tensor) -> None:
-    """out[N, K] (a column slice of the one fp32 weight gradient, row stride out.stride(0)) = g[R, N]^T x[R, K]: the two
-    routes of LinearFn.backward, writing in place."""
-    R, N = g.shape
-    K = x.shape[1]
-    dt = g.dtype
-    if (dt == torch.bfloat16 and R > 0 and N % 8 == 0 and K % 8 == 0 and x.stride(1) == 1 and x.stride(0) % 8 == 0
-            and x.data_ptr() % 16 == 0 and g.data_ptr() % 16 == 0 and g.stride(1) == 1 and g.stride(0) % 8 == 0
-            and TN_WGRAD and _tn_wgrad_wins(R, N, K)):
-        k_gemm_tn(g, x, out=out, split_k=_tn_splits(N, K, R), M=N, N=K, ldc=out.stride(0))
-    else:
-        ks = _kstep(dt)
-        m_pad = pad_to(R, ks)
-        k_gemm(k_transpose(g, m_pad), k_transpose(x, m_pad), out=out, split_k=_wgrad_splits(N, K, m_pad, ks))
-
-
 class LinearStageMapsFn(torch.autograd.Function):
     """act(concat_s R_s(X_s) @ W^T + b) with the commuted stages projected at their own resolution (see the section head)."""
 
     @staticmethod
     def forward(ctx, side: int, weight, bias, act: int, f32_partials: bool, *maps):
-        from .model.multimodal_encoder import vit_ops
         dt, dev = maps[0].dtype, maps[0].device
         B, N, P = maps[0].shape[0], weight.shape[0], side * side
         shapes = [tuple(m.shape) for m in maps]
@@ -2581,10 +2615,7 @@ class LinearStageMapsFn(torch.autograd.Function):
         xd = base = None
         if dense:   # resized first, as today, into one buffer; one GEMM over their (contiguous) weight columns
             d0, d1 = offs[dense[0]], offs[dense[-1] + 1]
-            xd = torch.empty((B, P, d1 - d0), dtype=dt, device=dev)
-            for k in dense:
-                _, Hs, Ws, Cs = shapes[k]
-                vit_ops.k_resample(_vec8_rows(maps[k].reshape(B, Hs * Ws, Cs)), Hs, Ws, xd, side, side, col_offset=offs[k] - d0)
+            xd = _resample_maps([maps[k] for k in dense], side)      # [B, P, d1 - d0]: the dense stages are neighbours
             base = k_gemm(xd.view(B * P, d1 - d0), w_c[:, d0:d1], out_dtype=pdt).view(B, P, N)
         srcs, xs = [], []
         for k, c in enumerate(plan):
@@ -2607,7 +2638,6 @@ class LinearStageMapsFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        from .model.multimodal_encoder import vit_ops
         w_c, w_t, pre, xd, *xs = ctx.saved_tensors
         side, shapes, plan, offs, dense = ctx.side, ctx.shapes, ctx.plan, ctx.offs, ctx.dense
         dt = w_c.dtype
@@ -2616,10 +2646,7 @@ class LinearStageMapsFn(torch.autograd.Function):
         need_m = list(ctx.needs_input_grad[5:])
         g = _as_dtype_contig(dy, dt)
         if ctx.act != L.ACT_NONE:
-            gp = torch.empty_like(pre)
-            L.check(L.load().cmb_act_bwd(L.dtype_code(dt), ctx.act, g.data_ptr(), pre.data_ptr(), pre.numel(), gp.data_ptr(),
-                                         L.stream_ptr(g.device)), "cmb_act_bwd")
-            g = gp
+            g = k_act_bwd(g, pre, ctx.act)
         g3 = g.view(B, P, N)
         dw = torch.empty((N, offs[-1]), dtype=torch.float32, device=g.device) if need_w else None
         if any(need_m) and w_t is None:
@@ -2635,7 +2662,7 @@ class LinearStageMapsFn(torch.autograd.Function):
                     if need_m[k]:
                         _, Hs, Ws, Cs = shapes[k]
                         dx = torch.empty((B, Hs * Ws, Cs), dtype=dt, device=g.device)
-                        vit_ops.k_resample_bwd(dxd, side, side, dx, Hs, Ws, col_offset=offs[k] - d0)
+                        k_resample_bwd(dxd, side, side, dx, Hs, Ws, col_offset=offs[k] - d0)
                         grads[k] = dx.view(B, Hs, Ws, Cs)
         xi = 0
         for k, c in enumerate(plan):
@@ -2647,19 +2674,14 @@ class LinearStageMapsFn(torch.autograd.Function):
                 continue
             _, Hs, Ws, Cs = shapes[k]
             gs = torch.empty((B, Hs * Ws, N), dtype=dt, device=g.device)  # g_s = R_s^T g: the adjoint kernel on the shared d(pre)
-            vit_ops.k_resample_bwd(g3, side, side, gs, Hs, Ws)
+            k_resample_bwd(g3, side, side, gs, Hs, Ws)
             gs = gs.view(B * Hs * Ws, N)
             if need_w:
                 _wgrad_into(gs, x, dw[:, offs[k]:offs[k + 1]])
             if need_m[k]:
                 grads[k] = k_gemm(gs, w_t[offs[k]:offs[k + 1], :N]).view(B, Hs, Ws, Cs)
-        if dw is not None and ctx.w_dtype != torch.float32:
-            dw = dw.to(ctx.w_dtype)
-        db = None
-        if need_b:
-            db = k_colsum(g)
-            if ctx.b_dtype != torch.float32:
-                db = db.to(ctx.b_dtype)
+        dw = _param_grad(dw, ctx.w_dtype)
+        db = _param_grad(k_colsum(g), ctx.b_dtype) if need_b else None
         return (None, dw, db, None, None, *grads)
 
 

@@ -243,7 +243,7 @@ def test_switch_and_fallbacks(dev, monkeypatch):
     md = [m.to(dev) for m in maps]
     wd, bd = w.to(dev), b.to(dev)
     accum = _Spy(monkeypatch, ops, "k_resample_accum")
-    resample = _Spy(monkeypatch, vit_ops, "k_resample")
+    resample = _Spy(monkeypatch, ops, "k_resample")
     want = ops.linear(ops.concat_stage_maps(md, side).reshape(-1, sum(dims)), wd, bd, act=lib.ACT_GELU_ERF)
     assert len(resample.calls) == 4 and not accum.calls
 

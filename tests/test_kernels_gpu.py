@@ -534,6 +534,34 @@ def test_add_rmsnorm_fused(dev, name, dt, frozen):
         assert rel_err(wd.grad, wr.grad) < (tol if name == "fp32" else 3e-2)
 
 
+@pytest.mark.parametrize("name,dt", DTYPES)
+@pytest.mark.parametrize("frozen", [True, False])
+@pytest.mark.parametrize("skip_used", [True, False])
+def test_rmsnorm_fork(dev, name, dt, frozen, skip_used):
+    """(x, rmsnorm(x) * w) as one node vs the plain torch expression: y, d(x) — the skip output's gradient enters the norm's
+    backward as its additive term, or is absent — and d(w) when the weight trains (the two-pass kernel + an ATen add, the
+    branch only the end-to-end finetune test reached)."""
+    ops, L = _ops()
+    g = torch.Generator().manual_seed(43)
+    rows, D = 37, 4096
+    x = _rand(g, 3, rows, D).to(dt)
+    w = (1 + 0.1 * _rand(g, D))
+    ws, wy = _rand(g, 3, rows, D), _rand(g, 3, rows, D)
+    xr = x.float().clone().requires_grad_()
+    wr = w.clone().requires_grad_(not frozen)
+    yr = wr * (xr * torch.rsqrt(xr.pow(2).mean(-1, keepdim=True) + 1e-5))
+    ((yr * wy).sum() + ((xr * ws).sum() if skip_used else 0.0)).backward()
+    xd = x.detach().to(dev).requires_grad_()
+    wd = w.to(dev).requires_grad_(not frozen)
+    xs, y = ops.rmsnorm_fork(xd, wd, 1e-5)
+    ((y.float() * wy.to(dev)).sum() + ((xs.float() * ws.to(dev)).sum() if skip_used else 0.0)).backward()
+    tol = TOL[name]
+    assert torch.equal(xs, xd) and rel_err(y, yr) < tol
+    assert rel_err(xd.grad, xr.grad) < tol
+    if not frozen:
+        assert rel_err(wd.grad, wr.grad) < (tol if name == "fp32" else 3e-2)
+
+
 # ------------------------------------------------------------------------------------------------ kernel-selection knobs
 # cmb_knob_set picks between kernels that compute the SAME function (round 4): every pair is checked against each other here
 # and — through the tests above, which run with the library's defaults — against the fp32 restatement.

@@ -110,8 +110,8 @@ def test_ops_resample_bilinear(dev, monkeypatch, name, dt, C, behind_cls):
     gi, go = (4, 6), (7, 3)
     x, g, out_ref, dx_ref = _case(gi, go, C, name)
     seen = []
-    real = vit_ops.k_resample
-    monkeypatch.setattr(vit_ops, "k_resample", lambda x_, *a, **k: (seen.append(x_.data_ptr()), real(x_, *a, **k))[1])
+    real = ops.k_resample                                 # (where the launcher lives and ops' own callers look it up)
+    monkeypatch.setattr(ops, "k_resample", lambda x_, *a, **k: (seen.append(x_.data_ptr()), real(x_, *a, **k))[1])
     if behind_cls:                                    # the tokens behind a CLS row: read in place, no copy
         parent = torch.cat([torch.ones(B, 1, C, dtype=dt), x], 1).to(dev).requires_grad_()
         xin = parent[:, 1:]
@@ -150,8 +150,8 @@ def test_ops_resample_concat(dev, monkeypatch, name, dt):
         off += c
     out_ref = torch.cat([r[0] for r in refs], -1)
     calls = []
-    real = vit_ops.k_resample_bwd
-    monkeypatch.setattr(vit_ops, "k_resample_bwd", lambda *a, **k: (calls.append(a[0].data_ptr()), real(*a, **k))[1])
+    real = ops.k_resample_bwd
+    monkeypatch.setattr(ops, "k_resample_bwd", lambda *a, **k: (calls.append(a[0].data_ptr()), real(*a, **k))[1])
 
     leaves = [m.clone().to(dev).requires_grad_() for m in maps]
     out = ops.resample_concat(leaves, side)
