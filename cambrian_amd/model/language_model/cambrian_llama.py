@@ -201,6 +201,41 @@ def use_decode_kernel(x: torch.Tensor, nh: int, nkv: int, hd: int) -> bool:
             and not (torch.is_grad_enabled() and x.requires_grad))
 
 
+def _frozen_plain(*mods) -> bool:
+    """Bias-free modules whose weights are frozen and may be kept (no ZeRO-3 unit drops their storage between uses)."""
+    return not any(m.weight.requires_grad or getattr(m, "bias", None) is not None
+                   or getattr(m, "_cmb_no_weight_cache", False) for m in mods)
+
+
+def decode_linear_weights(x: torch.Tensor, w_qkv, w_o, w_gate_up, w_down, norms) -> bool:
+    """The weights' side of "this decode step runs as five launches" (``ops.decode_linear`` around
+    ``ops.decode_attention``): the four (packed) weights present and taken by the kernel for x's rows, the norms frozen bf16
+    vectors.  Callers have checked the rest: bf16 x of at most 16 sequences inside the ``use_decode_kernel`` arm, and the
+    switch (``ops.decode_linear_enabled``) on for this batch."""
+    B = x.shape[0]
+    if any(w is None for w in (w_qkv, w_o, w_gate_up, w_down)):
+        return False
+    if any(n.weight.requires_grad or n.weight.dtype != torch.bfloat16 for n in norms):
+        return False
+    return (ops.decode_linear_supported(x.reshape(B, -1), w_qkv) and ops.decode_linear_weight_supported(B, w_o)
+            and ops.decode_linear_weight_supported(B, w_gate_up, "swiglu") and ops.decode_linear_weight_supported(B, w_down))
+
+
+def decode_layer_fused(layer, x, cos, sin, kcache, vcache, t, key_mask, w_qkv, w_o, w_gate_up, w_down):
+    """The five launches of a decode step: norm + QKV projection, attention on the cache, o_proj + skip connection,
+    norm + gate / up projection + SwiGLU, down_proj + skip connection."""
+    attn = layer.self_attn
+    B = x.shape[0]
+    nq, nk = attn.nh * attn.hd, attn.nkv * attn.hd
+    n1, n2 = layer.input_layernorm, layer.post_attention_layernorm
+    x2 = x.reshape(B, -1)
+    row = ops.decode_linear(x2, w_qkv, norm_weight=n1.weight, eps=n1.variance_epsilon)
+    o = ops.decode_attention(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t, key_mask)
+    x2 = ops.decode_linear(o, w_o, residual=x2)
+    inner = ops.decode_linear(x2, w_gate_up, norm_weight=n2.weight, eps=n2.variance_epsilon, act="swiglu")
+    return ops.decode_linear(inner, w_down, residual=x2).reshape(B, 1, -1)
+
+
 class LlamaAttention(nn.Module):
     def __init__(self, cfg, device, dtype):
         super().__init__()
@@ -293,6 +328,16 @@ class LlamaDecoderLayer(nn.Module):
         return self.mlp(h, residual=x)
 
     def decode(self, x, cos, sin, kcache, vcache, t, key_mask):
+        a, mlp = self.self_attn, self.mlp
+        if x.dtype == torch.bfloat16 and x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS and ops.decode_linear_enabled(x.shape[0]) \
+                and use_decode_kernel(x, a.nh, a.nkv, a.hd):
+            # the packed copies are the prefill's (_fused_frozen_weight: frozen bias-free projections only)
+            w = (_fused_frozen_weight(a, "_w_qkv", (a.q_proj, a.k_proj, a.v_proj)),
+                 a.o_proj.weight if _frozen_plain(a.o_proj) else None,
+                 _fused_frozen_weight(mlp, "_w_gate_up", (mlp.gate_proj, mlp.up_proj)),
+                 mlp.down_proj.weight if _frozen_plain(mlp.down_proj) else None)
+            if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm)):
+                return decode_layer_fused(self, x, cos, sin, kcache, vcache, t, key_mask, *w)
         x = x + self.self_attn.decode(self.input_layernorm(x), cos, sin, kcache, vcache, t, key_mask)
         return x + self.mlp(self.post_attention_layernorm(x))
 
@@ -581,6 +626,20 @@ def filter_logits_top_k_top_p(logits: torch.Tensor, top_k=None, top_p=None) -> t
     return logits
 
 
+def _decode_logits(self, x: torch.Tensor) -> torch.Tensor:
+    """fp32 logits of a decode step from the last layer's x [B, 1, H]: final norm + lm_head in one ``ops.decode_linear``
+    launch under the conditions of the layers' five-launch step, else the norm kernel, the stock GEMM and a cast."""
+    model, head = self.model, self.lm_head
+    a = model.layers[0].self_attn if len(model.layers) else None        # a decoder without layers keeps the stock line
+    B = x.shape[0]
+    if a is not None and use_decode_kernel(x, a.nh, a.nkv, a.hd) and x.dtype == torch.bfloat16 and B <= ops.DECODE_LINEAR_MAX_ROWS \
+            and ops.decode_linear_enabled(B) and _frozen_plain(head) and not model.norm.weight.requires_grad \
+            and model.norm.weight.dtype == torch.bfloat16 and ops.decode_linear_supported(x[:, 0], head.weight):
+        return ops.decode_linear(x[:, 0], head.weight, norm_weight=model.norm.weight, eps=model.norm.variance_epsilon,
+                                 out_dtype=torch.float32)
+    return head(model.norm(x)[:, 0]).float()
+
+
 def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: int = 16, do_sample: bool = False,
               temperature: float = 1.0, eos_token_id=None, attention_mask=None, position_ids=None, top_p=None, top_k=None,
               num_beams: int = 1, **kwargs):
@@ -660,7 +719,7 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
             x = model.embed_tokens(nxt)[:, None, :].to(model.llm_dtype)
             for layer, (kc, vc) in zip(model.layers, caches):
                 x = layer.decode(x, cos, sin, kc, vc, t, key_mask)      # [B, Lmax]: the step reads columns 0..t
-            logits = self.lm_head(model.norm(x)[:, 0]).float()
+            logits = _decode_logits(self, x)
         return torch.stack(out_ids, 1)
 
 

@@ -32,7 +32,8 @@ except Exception:  # pragma: no cover
 
 from ... import lib as L
 from ... import ops
-from .cambrian_llama import CambrianLlamaForCausalLM, CambrianLlamaModel, HipRMSNorm, _down_proj, _lin
+from .cambrian_llama import (CambrianLlamaForCausalLM, CambrianLlamaModel, HipRMSNorm, _down_proj, _frozen_plain, _lin,
+                             decode_layer_fused, decode_linear_weights, use_decode_kernel)
 
 
 class CambrianConfig(Phi3Config):
@@ -128,6 +129,13 @@ class Phi3DecoderLayer(nn.Module):
         return self.mlp(h, residual=x)
 
     def decode(self, x, cos, sin, kcache, vcache, t, key_mask):
+        a, mlp = self.self_attn, self.mlp
+        if x.dtype == torch.bfloat16 and x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS and ops.decode_linear_enabled(x.shape[0]) \
+                and use_decode_kernel(x, a.nh, a.nkv, a.hd):
+            # qkv_proj / gate_up_proj are packed as the kernel wants them: no copies
+            w = tuple(m.weight if _frozen_plain(m) else None for m in (a.qkv_proj, a.o_proj, mlp.gate_up_proj, mlp.down_proj))
+            if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm)):
+                return decode_layer_fused(self, x, cos, sin, kcache, vcache, t, key_mask, *w)
         x = x + self.self_attn.decode(self.input_layernorm(x), cos, sin, kcache, vcache, t, key_mask)
         return x + self.mlp(self.post_attention_layernorm(x))
 

@@ -2201,6 +2201,100 @@ def decode_attention_enabled() -> bool:
 
 
 # ================================================================================================
+# decode step of generate(): the layer's linears and the lm_head at M <= 16 rows as weight streams (decode_linear.hip)
+# ================================================================================================
+DECODE_LINEAR_MAX_ROWS = 16
+# Largest batch at which decode steps take the kernel by default; 0 = nowhere (the kernel stays behind the switch).  Set from
+# the measured table of profiles/decode_linear.md (tools/bench_decode_linear.py): at batch 1 / 4 / 16 on the Llama-3-8B, Yi-34B
+# and Phi-3-mini geometries the five-launch layer's median is below the stock sequence's fastest window, so it is on throughout.
+DECODE_LINEAR_DEFAULT_MAX_ROWS = 16
+
+
+def decode_linear_enabled(rows: int = 1) -> bool:
+    """Whether a decode step of ``rows`` sequences runs its linears on ``decode_linear``: ``CAMBRIAN_AMD_DECODE_LINEAR=0``
+    is the stock BLAS sequence and ``=1`` the kernel wherever it applies (A/B runs); unset, the default the measured table
+    led to."""
+    v = os.environ.get("CAMBRIAN_AMD_DECODE_LINEAR")
+    if v is None:
+        return rows <= DECODE_LINEAR_DEFAULT_MAX_ROWS
+    return v != "0"
+
+
+def decode_linear_plan(M: int, N: int, K: int, act: Optional[str] = None, cus: int = 0) -> Tuple[int, int]:
+    """(weight rows per workgroup, workgroups) of a ``decode_linear`` call: a pure function of (M, N, K, act, CU count);
+    ``cus`` = 0 takes the current device's count."""
+    rows, wgs = C.c_int32(0), C.c_int64(0)
+    L.check(L.load().cmb_decode_linear_plan(M, N, K, _decode_linear_act(act), cus, C.byref(rows), C.byref(wgs)),
+            "cmb_decode_linear_plan")
+    return rows.value, wgs.value
+
+
+def _decode_linear_act(act) -> int:
+    if act in (None, "none", 0):
+        return 0
+    if act in ("swiglu", 1):
+        return 1
+    raise L.CambrianAmdError(f"decode_linear: act is None or 'swiglu', got {act!r}")
+
+
+def _decode_linear_rows_ok(t: torch.Tensor, K: int) -> bool:
+    return (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2 and t.shape[1] == K and t.stride(1) == 1
+            and t.stride(0) % 8 == 0 and t.stride(0) >= K and t.data_ptr() % 16 == 0)
+
+
+def decode_linear_weight_supported(M: int, w: torch.Tensor, act: Optional[str] = None) -> bool:
+    """The weight's side of ``decode_linear_supported``, for ``M`` rows of x that are yet to be computed."""
+    return (w.dim() == 2 and _decode_linear_rows_ok(w, w.shape[1])
+            and bool(L.load().cmb_decode_linear_supported(M, w.shape[0], w.shape[1], _decode_linear_act(act))))
+
+
+def decode_linear_supported(x: torch.Tensor, w: torch.Tensor, act: Optional[str] = None) -> bool:
+    """Whether ``decode_linear(x, w, act=act)`` takes these operands: bf16 GPU tensors, x [M <= 16, K] and w [N, K] with
+    contiguous rows, 16-byte aligned with row strides that are multiples of 8, K % 8 == 0, N even for SwiGLU."""
+    return (w.dim() == 2 and x.dim() == 2 and x.shape[0] >= 1 and _decode_linear_rows_ok(x, w.shape[1])
+            and decode_linear_weight_supported(x.shape[0], w, act))
+
+
+def decode_linear(x: torch.Tensor, w: torch.Tensor, *, norm_weight: Optional[torch.Tensor] = None, eps: float = 0.0,
+                  act: Optional[str] = None, residual: Optional[torch.Tensor] = None,
+                  out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``epilogue(prologue(x) @ w.T)`` for bf16 x [M <= 16, K] and w [N, K] (row views are fine), one launch that reads the
+    weights once.  ``norm_weight`` [K]: RMSNorm(x; norm_weight, eps) is the operand (with the default
+    ``eps`` = 0 an all-zero row gives NaN, as the stock norm does: pass the model's eps); ``act="swiglu"``: w is packed
+    [gate; up] and the result is ``silu(gate) * up`` [M, N / 2] (``swiglu_packed``'s convention); ``residual`` [M, N]: added
+    in fp32 before the rounding; ``out_dtype``: bf16 (default) or fp32; ``out``: write into this [M, N'] tensor or row view
+    (16-byte aligned, row stride a multiple of 8) instead of a new one.  Inference only: there is no backward."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w, norm_weight, residual)):
+        raise L.CambrianAmdError("decode_linear has no backward: call it under torch.no_grad()")
+    L.require_gpu(x, w, norm_weight, residual, out)
+    code = _decode_linear_act(act)
+    if not decode_linear_supported(x, w, act):
+        raise L.CambrianAmdError(f"decode_linear: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, "
+                                 f"w {tuple(w.shape)} {w.dtype} strides {w.stride()}, act {act!r}")
+    (M, K), N = x.shape, w.shape[0]
+    cols = N // 2 if code else N
+    if norm_weight is not None and (norm_weight.dtype != torch.bfloat16 or norm_weight.shape != (K,)
+                                    or not norm_weight.is_contiguous()):
+        raise L.CambrianAmdError("decode_linear: norm_weight is a contiguous bf16 [K] vector")
+    if residual is not None and (code or residual.dtype != torch.bfloat16 or residual.shape != (M, cols)
+                                 or residual.stride(1) != 1):
+        raise L.CambrianAmdError("decode_linear: residual is bf16 [M, N] with contiguous rows, and not combined with act")
+    out_dtype = out_dtype or (torch.bfloat16 if out is None else out.dtype)
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise L.CambrianAmdError(f"decode_linear: out_dtype {out_dtype} (bf16 or fp32)")
+    if out is None:
+        ld = (cols + 7) // 8 * 8
+        out = torch.empty((M, ld), dtype=out_dtype, device=x.device)[:, :cols]
+    elif not out.is_cuda or out.dtype != out_dtype or out.shape != (M, cols) or out.stride(1) != 1:
+        raise L.CambrianAmdError(f"decode_linear: out must be a {out_dtype} GPU tensor [{M}, {cols}] with contiguous rows")
+    ld = out.stride(0)
+    L.call("cmb_decode_linear", x.data_ptr(), x.stride(0), M, L.ptr(norm_weight), float(eps), w.data_ptr(), w.stride(0), N, K,
+           code, L.ptr(residual), 0 if residual is None else residual.stride(0), out.data_ptr(), ld,
+           int(out_dtype == torch.float32), device=x.device)
+    return out
+
+
+# ================================================================================================
 # optimizer: global gradient norm and the one-pass AdamW step (optim.hip) over lists of tensors
 # ================================================================================================
 # Both kernels read a job table in device memory, one job per tensor.  The table is cached on a signature of every pointer

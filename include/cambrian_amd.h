@@ -66,7 +66,8 @@ const char* cmb_version(void);
  * the kernel-selection knobs of round 4 = 5, cmb_layernorm_fwd_multi = 9, cmb_ln_multi_desc.dx_out = 10, the workspaces of
  * the deterministic column sums = 11, cmb_decode_attn and its plan / workspace queries = 12,
  * cmb_resample_bilinear_bwd = 13).  cmb_resample_accum and its descriptor, and later the optimizer entry points
- * (cmb_optim_chunks, cmb_grad_sqnorm, cmb_grad_sqnorm_workspace, cmb_adamw_step) were ADDED under revision 13: no existing
+ * (cmb_optim_chunks, cmb_grad_sqnorm, cmb_grad_sqnorm_workspace, cmb_adamw_step), and after them the decode-step linear
+ * (cmb_decode_linear, cmb_decode_linear_supported, cmb_decode_linear_plan) were ADDED under revision 13: no existing
  * signature or layout changed, which is the rule for a bump, so a binding written against 13 still calls everything it
  * knows correctly.  Bindings must compare it
  * with the revision they
@@ -711,6 +712,32 @@ int cmb_decode_attn(int dtype, const void* q, int64_t q_ld, const void* k, int64
 int64_t cmb_decode_attn_ws(int64_t B, int32_t nh, int32_t nkv, int32_t hd, int64_t t, int32_t splits);
 int cmb_decode_attn_plan(int64_t B, int32_t nkv, int64_t t, int32_t splits, int32_t* splits_out, int64_t* chunk_out,
                          int32_t* max_splits_out);
+/* The linears of a decode step (generate(); the projections of HF LlamaDecoderLayer / Phi3DecoderLayer and the lm_head at
+ * one token per sequence): out[M, N'] = epilogue(prologue(x)[M, K] . W[N, K]^T), bf16 x and W, fp32 accumulation, 1 <= M <= 16.
+ * A stream of weights read once: non-temporal 16-byte loads straight to registers, a slab of weight rows per workgroup, K
+ * split over the workgroup's four waves and summed through LDS; no split of K across workgroups, no atomics, no workspace,
+ * the same bits on every run, and row m's bits do not depend on M.
+ *   norm_w != NULL   RMSNorm prologue, bf16 weights [K]: the result is RMSNorm(x; norm_w, norm_eps) . W^T.  x[m, k] * norm_w[k]
+ *                    is rounded to bf16 as it is read (the matrix unit's operand), the row's sum of squares is gathered on the
+ *                    same pass and rsqrt(mean + eps) scales the fp32 accumulator: the normalised row itself is never rounded,
+ *                    which differs from cmb_rmsnorm_fwd followed by a GEMM within bf16 rounding.
+ *   act              0 = none (N' = N); 1 = SwiGLU over packed [gate; up] rows, the convention of cmb_act_mul on a packed
+ *                    buffer: N = 2 I, out[m, j] = silu(acc[m, j]) * acc[m, I + j], N' = I.
+ *   residual         NULL or bf16 [M, N'] with row stride r_ld, added in fp32 before the one rounding; not with act = 1.
+ *   out_f32          0 = bf16 store, 1 = fp32 store (the logits).
+ * Everything is checked on the host before any launch and refused with CMB_ERR_BAD_ARG: x, W, out non-NULL; M in 1 .. 16;
+ * K % 8 == 0, K >= 8; N >= 1, even for act = 1; N, K <= 2^31; act in {0, 1}; out_f32 in {0, 1}; norm_eps >= 0; x_ld, w_ld >= K and
+ * o_ld, r_ld >= N', all multiples of 8 elements; every pointer given 16-byte aligned.  Rows of x past M - 1, columns past K of
+ * x and W and everything around out's [M, N'] are neither read nor written.
+ * cmb_decode_linear_supported: 1 / 0 for the shape conditions above, no launch.  cmb_decode_linear_plan: the weight rows a
+ * workgroup owns (8, 16 or 32; with act = 1 half of them gate rows and half the matching up rows) and the number of
+ * workgroups, a pure function of (M, N, K, act, CU count): the largest slab that leaves two workgroups per CU (one and a half for M > 4), 8 rows (16
+ * with act = 1) when none does.  cus = 0 asks for the current device's count (256 when there is none). */
+int cmb_decode_linear(const void* x, int64_t x_ld, int32_t M, const void* norm_w, float norm_eps, const void* W,
+                      int64_t w_ld, int64_t N, int64_t K, int32_t act, const void* residual, int64_t r_ld, void* out,
+                      int64_t o_ld, int32_t out_f32, void* stream);
+int cmb_decode_linear_supported(int32_t M, int64_t N, int64_t K, int32_t act);
+int cmb_decode_linear_plan(int32_t M, int64_t N, int64_t K, int32_t act, int32_t cus, int32_t* rows_out, int64_t* wgs_out);
 /* Backward of h = silu(g) * u (Llama MLP gate; forward is cmb_act_mul with CMB_ACT_SILU):
  * dg = dh * u * silu'(g), du = dh * silu(g); all [rows, D] with row strides. */
 int cmb_swiglu_bwd(int dtype, const void* dh, int64_t lddh, const void* g, int64_t ldg, const void* u, int64_t ldu,
