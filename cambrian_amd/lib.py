@@ -256,6 +256,9 @@ SIGNATURES = {
     "cmb_decode_linear": (C.c_int, [_p, _i64, _i32, _p, _f, _p, _i64, _i64, _i64, _i32, _p, _i64, _p, _i64, _i32, _p]),
     "cmb_decode_linear_supported": (C.c_int, [_i32, _i64, _i64, _i32]),
     "cmb_decode_linear_plan": (C.c_int, [_i32, _i64, _i64, _i32, _i32, C.POINTER(_i32), C.POINTER(_i64)]),
+    "cmb_decode_linear_fp8": (C.c_int, [_p, _i64, _i32, _p, _f, _p, _i64, _p, _i64, _i64, _i32, _p, _i64, _p, _i64, _i32, _p]),
+    "cmb_decode_linear_fp8_supported": (C.c_int, [_i32, _i64, _i64, _i32]),
+    "cmb_decode_linear_fp8_plan": (C.c_int, [_i32, _i64, _i64, _i32, _i32, C.POINTER(_i32), C.POINTER(_i64)]),
     "cmb_swiglu_bwd": (C.c_int, [C.c_int, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p]),
     "cmb_resize_coeffs": (C.c_int, [_i32, _i32, _p, _p]),
     "cmb_image_preprocess": (C.c_int, [_p, _p, _i32, _p, _p, _p, _p, _i32, _p, _p, _p]),

@@ -221,14 +221,55 @@ def decode_linear_weights(x: torch.Tensor, w_qkv, w_o, w_gate_up, w_down, norms)
             and ops.decode_linear_weight_supported(B, w_gate_up, "swiglu") and ops.decode_linear_weight_supported(B, w_down))
 
 
-def decode_layer_fused(layer, x, cos, sin, kcache, vcache, t, key_mask, w_qkv, w_o, w_gate_up, w_down):
+def _decode_fp8_tag(w: torch.Tensor):
+    return (w.data_ptr(), w._version, w.dtype)             # _frozen_transposed's tag
+
+
+def decode_fp8_copies(holder: nn.Module, B: int, entries):
+    """The quantised copies — (e4m3 bytes, fp32 row factors) per linear — of the weights a decode step streams through
+    ``ops.decode_linear_fp8``, or None when the kernel or the quantiser does not take ONE of them: the step then runs on
+    the bf16 weights exactly as without the mode, and nothing is quantised or kept for it.  ``entries``: (owner, key, w, act)
+    per linear.  A copy is cached on its ``owner`` under ``key`` with _frozen_transposed's tag and rebuilt when the weight
+    moves or changes; the entry holds ``w`` itself, so that a packed ``w`` (which _fused_frozen_weight replaces by a new
+    tensor when a part changes) cannot hand its address to its successor while the copy lives.  Every weight that needs a
+    new copy is put to ``ops.decode_linear_fp8_weight_supported`` BEFORE any is quantised (a cached one was accepted when it
+    was made, and callers keep B within 16 rows); a refusal is remembered on ``holder`` against the same tags, so the
+    following steps ask nothing again, and stale copies of a refused set are dropped.  Callers have established the
+    five-launch conditions, so no owner is a ZeRO-3 unit.  The bf16 weights stay: prefill and training use them."""
+    tags = tuple(_decode_fp8_tag(w) for _, _, w, _ in entries)
+    if holder.__dict__.get("_decode_fp8_refused") == tags:
+        return None
+    cached = [owner.__dict__.get(key) for owner, key, _, _ in entries]
+    miss = [i for i, (c, tag) in enumerate(zip(cached, tags)) if c is None or c[0] != tag]
+    if miss:
+        if not all(ops.decode_linear_fp8_weight_supported(B, entries[i][2], entries[i][3]) for i in miss):
+            holder.__dict__["_decode_fp8_refused"] = tags
+            for owner, key, _, _ in entries:
+                owner.__dict__.pop(key, None)
+            return None
+        holder.__dict__.pop("_decode_fp8_refused", None)
+        for i in miss:
+            owner, key, w, _ = entries[i]
+            cached[i] = owner.__dict__[key] = (tags[i], ops.decode_fp8_weight(w), w)
+    return [c[1] for c in cached]
+
+
+def decode_layer_fused(layer, x, cos, sin, kcache, vcache, t, key_mask, w_qkv, w_o, w_gate_up, w_down, fp8=None):
     """The five launches of a decode step: norm + QKV projection, attention on the cache, o_proj + skip connection,
-    norm + gate / up projection + SwiGLU, down_proj + skip connection."""
+    norm + gate / up projection + SwiGLU, down_proj + skip connection.  ``fp8``: the four (bytes, factors) pairs of
+    ``decode_fp8_copies`` — the linears then stream those instead of the bf16 weights."""
     attn = layer.self_attn
     B = x.shape[0]
     nq, nk = attn.nh * attn.hd, attn.nkv * attn.hd
     n1, n2 = layer.input_layernorm, layer.post_attention_layernorm
     x2 = x.reshape(B, -1)
+    if fp8 is not None:
+        q_qkv, q_o, q_gate_up, q_down = fp8
+        row = ops.decode_linear_fp8(x2, *q_qkv, norm_weight=n1.weight, eps=n1.variance_epsilon)
+        o = ops.decode_attention(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t, key_mask)
+        x2 = ops.decode_linear_fp8(o, *q_o, residual=x2)
+        inner = ops.decode_linear_fp8(x2, *q_gate_up, norm_weight=n2.weight, eps=n2.variance_epsilon, act="swiglu")
+        return ops.decode_linear_fp8(inner, *q_down, residual=x2).reshape(B, 1, -1)
     row = ops.decode_linear(x2, w_qkv, norm_weight=n1.weight, eps=n1.variance_epsilon)
     o = ops.decode_attention(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t, key_mask)
     x2 = ops.decode_linear(o, w_o, residual=x2)
@@ -327,7 +368,9 @@ class LlamaDecoderLayer(nn.Module):
         x, h = ops.add_rmsnorm(x, a, n2.weight, n2.variance_epsilon)  # x + a and norm(x + a) in one pass
         return self.mlp(h, residual=x)
 
-    def decode(self, x, cos, sin, kcache, vcache, t, key_mask):
+    def decode(self, x, cos, sin, kcache, vcache, t, key_mask, fp8=False):
+        """``fp8``: stream e4m3 copies of the weights where the five-launch step is taken (``ops.decode_fp8_enabled``,
+        resolved once by ``generate``)."""
         a, mlp = self.self_attn, self.mlp
         if x.dtype == torch.bfloat16 and x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS and ops.decode_linear_enabled(x.shape[0]) \
                 and use_decode_kernel(x, a.nh, a.nkv, a.hd):
@@ -337,7 +380,12 @@ class LlamaDecoderLayer(nn.Module):
                  _fused_frozen_weight(mlp, "_w_gate_up", (mlp.gate_proj, mlp.up_proj)),
                  mlp.down_proj.weight if _frozen_plain(mlp.down_proj) else None)
             if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm)):
-                return decode_layer_fused(self, x, cos, sin, kcache, vcache, t, key_mask, *w)
+                q8 = None
+                if fp8:
+                    q8 = decode_fp8_copies(self, x.shape[0], ((a, "_w_qkv_fp8", w[0], None), (a.o_proj, "_w_fp8", w[1], None),
+                                                              (mlp, "_w_gate_up_fp8", w[2], "swiglu"),
+                                                              (mlp.down_proj, "_w_fp8", w[3], None)))
+                return decode_layer_fused(self, x, cos, sin, kcache, vcache, t, key_mask, *w, fp8=q8)
         x = x + self.self_attn.decode(self.input_layernorm(x), cos, sin, kcache, vcache, t, key_mask)
         return x + self.mlp(self.post_attention_layernorm(x))
 
@@ -626,15 +674,20 @@ def filter_logits_top_k_top_p(logits: torch.Tensor, top_k=None, top_p=None) -> t
     return logits
 
 
-def _decode_logits(self, x: torch.Tensor) -> torch.Tensor:
+def _decode_logits(self, x: torch.Tensor, fp8: bool = False) -> torch.Tensor:
     """fp32 logits of a decode step from the last layer's x [B, 1, H]: final norm + lm_head in one ``ops.decode_linear``
-    launch under the conditions of the layers' five-launch step, else the norm kernel, the stock GEMM and a cast."""
+    launch under the conditions of the layers' five-launch step, else the norm kernel, the stock GEMM and a cast.
+    ``fp8``: that launch streams the lm_head's e4m3 copy (``ops.decode_linear_fp8``) where the kernel takes it."""
     model, head = self.model, self.lm_head
     a = model.layers[0].self_attn if len(model.layers) else None        # a decoder without layers keeps the stock line
     B = x.shape[0]
     if a is not None and use_decode_kernel(x, a.nh, a.nkv, a.hd) and x.dtype == torch.bfloat16 and B <= ops.DECODE_LINEAR_MAX_ROWS \
             and ops.decode_linear_enabled(B) and _frozen_plain(head) and not model.norm.weight.requires_grad \
             and model.norm.weight.dtype == torch.bfloat16 and ops.decode_linear_supported(x[:, 0], head.weight):
+        q8 = decode_fp8_copies(head, B, ((head, "_w_fp8", head.weight, None),)) if fp8 else None
+        if q8 is not None:
+            return ops.decode_linear_fp8(x[:, 0], *q8[0], norm_weight=model.norm.weight, eps=model.norm.variance_epsilon,
+                                         out_dtype=torch.float32)
         return ops.decode_linear(x[:, 0], head.weight, norm_weight=model.norm.weight, eps=model.norm.variance_epsilon,
                                  out_dtype=torch.float32)
     return head(model.norm(x)[:, 0]).float()
@@ -701,6 +754,7 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
         out_ids = []
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         theta = float(getattr(self.config, "rope_theta", 10000.0))
+        fp8 = ops.decode_fp8_enabled(getattr(self.config, "decode_fp8_weights", False))   # e4m3 weight stream, opt-in
         for step in range(max_new_tokens):
             if do_sample and temperature > 0:
                 warped = filter_logits_top_k_top_p(logits / temperature, top_k, top_p)
@@ -718,8 +772,8 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
             cos, sin = ops.rope_table((n_tok + step)[:, None], hd, theta)
             x = model.embed_tokens(nxt)[:, None, :].to(model.llm_dtype)
             for layer, (kc, vc) in zip(model.layers, caches):
-                x = layer.decode(x, cos, sin, kc, vc, t, key_mask)      # [B, Lmax]: the step reads columns 0..t
-            logits = _decode_logits(self, x)
+                x = layer.decode(x, cos, sin, kc, vc, t, key_mask, fp8=fp8)      # [B, Lmax]: the step reads columns 0..t
+            logits = _decode_logits(self, x, fp8)
         return torch.stack(out_ids, 1)
 
 

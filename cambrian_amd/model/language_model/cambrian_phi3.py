@@ -33,7 +33,7 @@ except Exception:  # pragma: no cover
 from ... import lib as L
 from ... import ops
 from .cambrian_llama import (CambrianLlamaForCausalLM, CambrianLlamaModel, HipRMSNorm, _down_proj, _frozen_plain, _lin,
-                             decode_layer_fused, decode_linear_weights, use_decode_kernel)
+                             decode_fp8_copies, decode_layer_fused, decode_linear_weights, use_decode_kernel)
 
 
 class CambrianConfig(Phi3Config):
@@ -128,14 +128,19 @@ class Phi3DecoderLayer(nn.Module):
         x, h = ops.add_rmsnorm(x, a, n2.weight, n2.variance_epsilon)              # :903-911 residual + norm, one pass
         return self.mlp(h, residual=x)
 
-    def decode(self, x, cos, sin, kcache, vcache, t, key_mask):
+    def decode(self, x, cos, sin, kcache, vcache, t, key_mask, fp8=False):
         a, mlp = self.self_attn, self.mlp
         if x.dtype == torch.bfloat16 and x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS and ops.decode_linear_enabled(x.shape[0]) \
                 and use_decode_kernel(x, a.nh, a.nkv, a.hd):
             # qkv_proj / gate_up_proj are packed as the kernel wants them: no copies
-            w = tuple(m.weight if _frozen_plain(m) else None for m in (a.qkv_proj, a.o_proj, mlp.gate_up_proj, mlp.down_proj))
+            mods = (a.qkv_proj, a.o_proj, mlp.gate_up_proj, mlp.down_proj)
+            w = tuple(m.weight if _frozen_plain(m) else None for m in mods)
             if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm)):
-                return decode_layer_fused(self, x, cos, sin, kcache, vcache, t, key_mask, *w)
+                q8 = None
+                if fp8:      # e4m3 copies, cached on the Linear that owns the weight
+                    q8 = decode_fp8_copies(self, x.shape[0], tuple(
+                        (m, "_w_fp8", wi, "swiglu" if m is mlp.gate_up_proj else None) for m, wi in zip(mods, w)))
+                return decode_layer_fused(self, x, cos, sin, kcache, vcache, t, key_mask, *w, fp8=q8)
         x = x + self.self_attn.decode(self.input_layernorm(x), cos, sin, kcache, vcache, t, key_mask)
         return x + self.mlp(self.post_attention_layernorm(x))
 

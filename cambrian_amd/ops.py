@@ -2294,6 +2294,108 @@ def decode_linear(x: torch.Tensor, w: torch.Tensor, *, norm_weight: Optional[tor
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# the same linears on weight-only e4m3 weights (decode_linear_fp8.hip): half the weight stream of a decode step.  Opt-in
+# (``config.decode_fp8_weights`` / CAMBRIAN_AMD_DECODE_FP8): it changes numerics — row-wise e4m3 weights are about 2.5–2.7 %
+# relative L2 error per product on Gaussian weights — and keeps a 1-byte copy of every decoder weight beside the bf16 one.
+# ------------------------------------------------------------------------------------------------
+DECODE_FP8_MAX_K = 16384       # cmb_quantize_fp8_rows holds a row in registers: K <= 256 threads x 16 x 4 pieces (fp8.hip)
+
+
+def decode_fp8_enabled(config_flag: bool = False) -> bool:
+    """Whether decode steps stream e4m3 weights: ``CAMBRIAN_AMD_DECODE_FP8`` = ``1`` / ``0`` in the environment overrides,
+    unset it is ``config_flag`` (the model's ``config.decode_fp8_weights``, absent = off)."""
+    v = os.environ.get("CAMBRIAN_AMD_DECODE_FP8")
+    if v is None or v == "":
+        return bool(config_flag)
+    return v != "0"
+
+
+def decode_linear_fp8_plan(M: int, N: int, K: int, act: Optional[str] = None, cus: int = 0) -> Tuple[int, int]:
+    """(weight rows per workgroup, workgroups) of a ``decode_linear_fp8`` call: a pure function of (M, N, K, act, CU
+    count); ``cus`` = 0 takes the current device's count."""
+    rows, wgs = C.c_int32(0), C.c_int64(0)
+    L.check(L.load().cmb_decode_linear_fp8_plan(M, N, K, _decode_linear_act(act), cus, C.byref(rows), C.byref(wgs)),
+            "cmb_decode_linear_fp8_plan")
+    return rows.value, wgs.value
+
+
+def decode_linear_fp8_weight_supported(M: int, w: torch.Tensor, act: Optional[str] = None) -> bool:
+    """Whether the bf16 weight ``w`` [N, K] can be served by ``decode_fp8_weight`` + ``decode_linear_fp8`` for ``M`` rows of
+    x: a GPU bf16 matrix with contiguous, 16-byte aligned rows, K % 16 == 0, K within the quantiser's reach
+    (``DECODE_FP8_MAX_K``), and the kernel's shape rule."""
+    return (w.dim() == 2 and _decode_linear_rows_ok(w, w.shape[1]) and w.shape[1] <= DECODE_FP8_MAX_K
+            and bool(L.load().cmb_decode_linear_fp8_supported(M, w.shape[0], w.shape[1], _decode_linear_act(act))))
+
+
+def _decode_fp8_q_ok(q: torch.Tensor, inv_scale: torch.Tensor) -> bool:
+    return (q.is_cuda and q.dtype == torch.uint8 and q.dim() == 2 and q.stride(1) == 1 and q.stride(0) >= q.shape[1]
+            and q.stride(0) % 16 == 0 and q.data_ptr() % 16 == 0 and inv_scale.is_cuda and inv_scale.device == q.device
+            and inv_scale.dtype == torch.float32 and inv_scale.shape == (q.shape[0],) and inv_scale.is_contiguous())
+
+
+def decode_linear_fp8_supported(x: torch.Tensor, q: torch.Tensor, inv_scale: torch.Tensor, act: Optional[str] = None) -> bool:
+    """Whether ``decode_linear_fp8(x, q, inv_scale, act=act)`` takes these operands: bf16 GPU x [M <= 16, K], uint8 GPU q
+    [N, K] with contiguous 16-byte aligned rows (row stride a multiple of 16), contiguous fp32 inv_scale [N], K % 16 == 0,
+    N even for SwiGLU."""
+    return (x.dim() == 2 and q.dim() == 2 and x.shape[0] >= 1 and _decode_linear_rows_ok(x, q.shape[1])
+            and _decode_fp8_q_ok(q, inv_scale)
+            and bool(L.load().cmb_decode_linear_fp8_supported(x.shape[0], q.shape[0], q.shape[1], _decode_linear_act(act))))
+
+
+def decode_fp8_weight(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A frozen bf16 GPU weight [N, K] -> (e4m3fn bytes uint8 [N, K], fp32 dequantisation factor [N]) for
+    ``decode_linear_fp8``: every row scaled so that its largest magnitude maps to 448 (``k_quantize_fp8_rows``; a zero row
+    gets the factor 1).  K % 16 == 0 and K <= ``DECODE_FP8_MAX_K``, the quantiser's limit."""
+    L.require_gpu(w)
+    if w.requires_grad:
+        raise L.CambrianAmdError("decode_fp8_weight: the weight is trainable; quantised copies are for frozen weights")
+    if w.dim() != 2 or w.dtype != torch.bfloat16 or w.stride(1) != 1 or w.shape[0] < 1 or w.shape[1] < 16 \
+            or w.shape[1] % 16 or w.shape[1] > DECODE_FP8_MAX_K or w.stride(0) % 8 or w.data_ptr() % 16:
+        raise L.CambrianAmdError(f"decode_fp8_weight: needs a bf16 [N, K] matrix with contiguous 16-byte aligned rows, "
+                                 f"K % 16 == 0 and 16 <= K <= {DECODE_FP8_MAX_K}; got {tuple(w.shape)} {w.dtype} "
+                                 f"strides {w.stride()}")
+    return k_quantize_fp8_rows(w.detach())
+
+
+def decode_linear_fp8(x: torch.Tensor, q: torch.Tensor, inv_scale: torch.Tensor, *, norm_weight: Optional[torch.Tensor] = None,
+                      eps: float = 0.0, act: Optional[str] = None, residual: Optional[torch.Tensor] = None,
+                      out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``decode_linear`` on weight-only e4m3 weights: ``epilogue(inv_scale * (prologue(x) @ e4m3(q).T))`` for bf16 x
+    [M <= 16, K], q the uint8 e4m3fn bytes [N, K] (finite: never the NaN codes 0x7F / 0xFF) and inv_scale the fp32 row factors [N] of
+    ``decode_fp8_weight``; one
+    launch that reads one byte per weight.  ``norm_weight`` / ``eps`` / ``act`` / ``residual`` / ``out_dtype`` / ``out``
+    mean what they mean in ``decode_linear``.  Inference only: there is no backward and no CPU path."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, inv_scale, norm_weight, residual)):
+        raise L.CambrianAmdError("decode_linear_fp8 has no backward: call it under torch.no_grad()")
+    L.require_gpu(x, q, inv_scale, norm_weight, residual, out)
+    code = _decode_linear_act(act)
+    if not decode_linear_fp8_supported(x, q, inv_scale, act):
+        raise L.CambrianAmdError(f"decode_linear_fp8: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, "
+                                 f"q {tuple(q.shape)} {q.dtype} strides {q.stride()}, inv_scale {tuple(inv_scale.shape)} "
+                                 f"{inv_scale.dtype}, act {act!r}")
+    (M, K), N = x.shape, q.shape[0]
+    cols = N // 2 if code else N
+    if norm_weight is not None and (norm_weight.dtype != torch.bfloat16 or norm_weight.shape != (K,)
+                                    or not norm_weight.is_contiguous()):
+        raise L.CambrianAmdError("decode_linear_fp8: norm_weight is a contiguous bf16 [K] vector")
+    if residual is not None and (code or residual.dtype != torch.bfloat16 or residual.shape != (M, cols)
+                                 or residual.stride(1) != 1):
+        raise L.CambrianAmdError("decode_linear_fp8: residual is bf16 [M, N] with contiguous rows, and not combined with act")
+    out_dtype = out_dtype or (torch.bfloat16 if out is None else out.dtype)
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise L.CambrianAmdError(f"decode_linear_fp8: out_dtype {out_dtype} (bf16 or fp32)")
+    if out is None:
+        ld = (cols + 7) // 8 * 8
+        out = torch.empty((M, ld), dtype=out_dtype, device=x.device)[:, :cols]
+    elif not out.is_cuda or out.dtype != out_dtype or out.shape != (M, cols) or out.stride(1) != 1:
+        raise L.CambrianAmdError(f"decode_linear_fp8: out must be a {out_dtype} GPU tensor [{M}, {cols}] with contiguous rows")
+    L.call("cmb_decode_linear_fp8", x.data_ptr(), x.stride(0), M, L.ptr(norm_weight), float(eps), q.data_ptr(), q.stride(0),
+           inv_scale.data_ptr(), N, K, code, L.ptr(residual), 0 if residual is None else residual.stride(0), out.data_ptr(),
+           out.stride(0), int(out_dtype == torch.float32), device=x.device)
+    return out
+
+
 # ================================================================================================
 # optimizer: global gradient norm and the one-pass AdamW step (optim.hip) over lists of tensors
 # ================================================================================================

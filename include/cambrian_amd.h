@@ -67,7 +67,8 @@ const char* cmb_version(void);
  * the deterministic column sums = 11, cmb_decode_attn and its plan / workspace queries = 12,
  * cmb_resample_bilinear_bwd = 13).  cmb_resample_accum and its descriptor, and later the optimizer entry points
  * (cmb_optim_chunks, cmb_grad_sqnorm, cmb_grad_sqnorm_workspace, cmb_adamw_step), and after them the decode-step linear
- * (cmb_decode_linear, cmb_decode_linear_supported, cmb_decode_linear_plan) were ADDED under revision 13: no existing
+ * (cmb_decode_linear, cmb_decode_linear_supported, cmb_decode_linear_plan) and its 1-byte-weight form
+ * (cmb_decode_linear_fp8, cmb_decode_linear_fp8_supported, cmb_decode_linear_fp8_plan) were ADDED under revision 13: no existing
  * signature or layout changed, which is the rule for a bump, so a binding written against 13 still calls everything it
  * knows correctly.  Bindings must compare it
  * with the revision they
@@ -738,6 +739,24 @@ int cmb_decode_linear(const void* x, int64_t x_ld, int32_t M, const void* norm_w
                       int64_t o_ld, int32_t out_f32, void* stream);
 int cmb_decode_linear_supported(int32_t M, int64_t N, int64_t K, int32_t act);
 int cmb_decode_linear_plan(int32_t M, int64_t N, int64_t K, int32_t act, int32_t cus, int32_t* rows_out, int64_t* wgs_out);
+/* cmb_decode_linear on weight-only e4m3 weights, half the weight stream of a decode step:
+ *   out = epilogue(rstd? * w_inv_scale[n] * sum_k prologue(x)[m, k] * e4m3(Wq[n, k]))
+ * Wq: OCP e4m3fn bytes [N, K] with row stride w_ld BYTES, w_inv_scale: fp32 [N] — what cmb_quantize_fp8_rows writes (a
+ * row's largest magnitude maps to 448, inv_scale = amax / 448, 1.0 for a zero row).  Every byte of Wq[N, K] must be FINITE
+ * (not 0x7F / 0xFF, the NaN codes, which the quantiser never writes): fragments past a ragged K re-read bytes at k = 0 and
+ * multiply them by zero, so a NaN anywhere in a row could reach its sum.  x stays bf16: every e4m3 value is
+ * exactly a bf16, so the bytes are converted in registers and the products are those of cmb_decode_linear on the
+ * dequantised-without-scale weights; the row factor multiplies the finished fp32 sum once (together with rstd under the
+ * norm prologue; with act = 1 gate and up each take their own row's before silu(g) * u).  norm_w, act, residual, out_f32,
+ * the determinism and the statuses are cmb_decode_linear's; the shape rule differs in K % 16 == 0, K >= 16, w_ld >= K and
+ * w_ld % 16 == 0 (a lane loads 16 bytes = 16 k), Wq 16-byte aligned, w_inv_scale non-NULL and 4-byte aligned.
+ * cmb_decode_linear_fp8_plan: as cmb_decode_linear_plan, with the largest slab that leaves ONE workgroup per CU at every
+ * M (a slab carries half the bytes per row, the x fragments per k-step stay). */
+int cmb_decode_linear_fp8(const void* x, int64_t x_ld, int32_t M, const void* norm_w, float norm_eps, const void* Wq,
+                          int64_t w_ld, const void* w_inv_scale, int64_t N, int64_t K, int32_t act, const void* residual,
+                          int64_t r_ld, void* out, int64_t o_ld, int32_t out_f32, void* stream);
+int cmb_decode_linear_fp8_supported(int32_t M, int64_t N, int64_t K, int32_t act);
+int cmb_decode_linear_fp8_plan(int32_t M, int64_t N, int64_t K, int32_t act, int32_t cus, int32_t* rows_out, int64_t* wgs_out);
 /* Backward of h = silu(g) * u (Llama MLP gate; forward is cmb_act_mul with CMB_ACT_SILU):
  * dg = dh * u * silu'(g), du = dh * silu(g); all [rows, D] with row strides. */
 int cmb_swiglu_bwd(int dtype, const void* dh, int64_t lddh, const void* g, int64_t ldg, const void* u, int64_t ldu,

@@ -5,6 +5,15 @@ adds), same box, same run.  The off arm is the yardstick; the table this writes 
 
     python tools/bench_decode_linear.py [--out profiles/decode_linear.md] [--iters 50] [--quick] [--resources FILE]
     python tools/bench_decode_linear.py --dump-resources FILE       # no GPU: hipcc's register / LDS / scratch report
+    python tools/bench_decode_linear.py --fp8 [--out profiles/decode_fp8.md] [--resources FILE]
+    python tools/bench_decode_linear.py --fp8 --dump-resources FILE
+
+``--fp8`` measures the e4m3 weight stream (``cmb_decode_linear_fp8``, ``layer.decode(..., fp8=True)``) against the bf16
+``decode_linear`` arm — today's default path, the yardstick — by the same method; the ring is at least 768 MB of the 1-byte
+weights, MB and GB/s count one byte per weight, and a row is faster when the fp8 median is below the bf16 arm's minimum
+window.  A weight the row quantiser does not reach (K > ``ops.DECODE_FP8_MAX_K``: Yi-34B's down_proj) is timed alone on
+random finite e4m3 bytes — time does not depend on the values — and the layer that holds it refuses the mode, quantises nothing and
+runs on bf16, as it does in ``generate()``; the layer table reads that off the layers and says so.
 
 For Llama-3-8B, Yi-34B (Llama blocks) and Phi-3-mini (Phi-3 block) in bf16, context 2048, batch 1 / 4 / 16, each arm runs in
 a fresh child process (one per geometry and arm, the arms alternating) and times with HIP events after a warm-up of every
@@ -49,19 +58,21 @@ def linear_shapes(g: dict) -> dict:
     return {"qkv": ((nh + 2 * nkv) * hd, H), "o": (H, nh * hd), "gate_up": (2 * inter, H), "down": (H, inter)}
 
 
-def weight_bytes(g: dict) -> dict:
-    return {k: n * kk * 2 for k, (n, kk) in linear_shapes(g).items()}
+def weight_bytes(g: dict, elem: int = 2) -> dict:
+    return {k: n * kk * elem for k, (n, kk) in linear_shapes(g).items()}
 
 
-def child(geom: str, arm: str, iters: int, warmup: int, quick: bool) -> None:
+def child(geom: str, arm: str, iters: int, warmup: int, quick: bool, ring_fp8: bool = False) -> None:
     import torch
     import torch.nn.functional as F
     from cambrian_amd import ops
     from cambrian_amd.model.language_model import cambrian_llama as CL, cambrian_phi3 as CP
     if not torch.cuda.is_available():
         raise SystemExit("bench_decode_linear: no GPU visible")
-    on = arm == "on"
+    fp8 = arm == "fp8"
+    on = arm == "on" or fp8
     assert ops.decode_linear_enabled(1) == on and ops.decode_linear_enabled(16) == on and ops.decode_attention_enabled()
+    assert ops.decode_fp8_enabled() == fp8
     dev, dt = torch.device("cuda:0"), torch.bfloat16
     g = dict(GEOMS[geom])
     lm = g.pop("lm")
@@ -69,8 +80,9 @@ def child(geom: str, arm: str, iters: int, warmup: int, quick: bool) -> None:
     cfg = mod.CambrianConfig(vocab_size=64, num_hidden_layers=1, rms_norm_eps=1e-5, rope_theta=500000.0,
                              max_position_embeddings=16384, **g)
     torch.manual_seed(0)
-    wb = weight_bytes(g)
-    ring = max(4, -(-RING_BYTES // sum(wb.values())))
+    wb = weight_bytes(g, 1 if fp8 else 2)                    # the bytes a call streams
+    ring_wb = weight_bytes(g, 1) if ring_fp8 else wb         # an fp8 run sizes BOTH arms' rings by the 1-byte weights
+    ring = max(4, -(-RING_BYTES // sum(ring_wb.values())))
     cls = CP.Phi3DecoderLayer if lm == "phi3" else CL.LlamaDecoderLayer
     layers = [cls(cfg, dev, dt).requires_grad_(False) for _ in range(ring)]
     att = layers[0].self_attn
@@ -78,8 +90,19 @@ def child(geom: str, arm: str, iters: int, warmup: int, quick: bool) -> None:
     H = g["hidden_size"]
     eps = 1e-5
     shapes = linear_shapes(g)
-    rings = {k: max(4, -(-RING_BYTES // wb[k])) for k in LINEARS}
-    weights = {k: [torch.randn(shapes[k], device=dev, dtype=dt) * shapes[k][1] ** -0.5 for _ in range(rings[k])] for k in LINEARS}
+    rings = {k: max(4, -(-RING_BYTES // ring_wb[k])) for k in LINEARS}
+
+    def weight(k):
+        w = torch.randn(shapes[k], device=dev, dtype=dt) * shapes[k][1] ** -0.5
+        if not fp8:
+            return w
+        if ops.decode_linear_fp8_weight_supported(1, w, "swiglu" if k == "gate_up" else None):
+            return ops.decode_fp8_weight(w)
+        q = torch.randint(0, 256, shapes[k], device=dev, dtype=torch.uint8)       # beyond the quantiser's reach: random bytes,
+        q[(q & 0x7F) == 0x7F] = 0                                                 # none of them the two NaN codes
+        return q, torch.full((shapes[k][0],), 2.0 ** -8 * shapes[k][1] ** -0.5, device=dev)
+
+    weights = {k: [weight(k) for _ in range(rings[k])] for k in LINEARS}
     nw = torch.ones(H, device=dev, dtype=dt)
 
     def timed(fn, n):
@@ -106,13 +129,15 @@ def child(geom: str, arm: str, iters: int, warmup: int, quick: bool) -> None:
         cos, sin = ops.rope_table(torch.full((B, 1), CTX, device=dev), hd, 500000.0)
 
         def layer_call(i):
-            layers[i % ring].decode(x, cos, sin, kc, vc, t, mask)
+            layers[i % ring].decode(x, cos, sin, kc, vc, t, mask, fp8=fp8)
 
         def lin_call(name):
             ws, n, xin = weights[name], rings[name], xs[name]
             if on:
                 kw = {"qkv": dict(norm_weight=nw, eps=eps), "o": dict(residual=x2),
                       "gate_up": dict(norm_weight=nw, eps=eps, act="swiglu"), "down": dict(residual=x2)}[name]
+                if fp8:
+                    return lambda i: ops.decode_linear_fp8(xin, *ws[i % n], **kw)
                 return lambda i: ops.decode_linear(xin, ws[i % n], **kw)
             if name == "qkv":
                 return lambda i: F.linear(ops.rmsnorm(xin, nw, eps), ws[i % n])
@@ -131,31 +156,36 @@ def child(geom: str, arm: str, iters: int, warmup: int, quick: bool) -> None:
                 for i in range(max(warmup, 4)):
                     calls[k](i)
             torch.cuda.synchronize()
+            # whether the layers took the mode is read off the layers: the copies they cached, none when a weight was refused
+            rec["layer_fp8"] = any(k.endswith("_fp8") for m in layers[0].modules() for k in m.__dict__)
+            assert rec["layer_fp8"] == all(any(k.endswith("_fp8") for m in ly.modules() for k in m.__dict__) for ly in layers)
             rec["layer_us"] = timed(layer_call, iters)
             for k in LINEARS:
                 rec[k + "_us"] = timed(calls[k], iters)
         print("BENCH_DECODE_LINEAR " + json.dumps(rec), flush=True)
 
 
-def resource_usage() -> list:
-    """hipcc's kernel-resource-usage remarks for decode_linear.hip (no GPU needed): one dict per instantiation"""
-    src = os.path.join(ROOT, "cambrian_amd", "csrc", "decode_linear.hip")
+def resource_usage(fp8: bool = False) -> list:
+    """hipcc's kernel-resource-usage remarks for decode_linear.hip (``fp8``: decode_linear_fp8.hip with the Makefile's flag
+    for that file; no GPU needed): one dict per instantiation"""
+    src = os.path.join(ROOT, "cambrian_amd", "csrc", "decode_linear_fp8.hip" if fp8 else "decode_linear.hip")
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    p = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Rpass-analysis=kernel-resource-usage",
-                        "-c", src, "-o", os.devnull], capture_output=True, text=True, cwd=os.path.dirname(src))
+    p = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Rpass-analysis=kernel-resource-usage"]
+                       + (["-fno-slp-vectorize"] if fp8 else []) + ["-c", src, "-o", os.devnull],
+                       capture_output=True, text=True, cwd=os.path.dirname(src))
     if p.returncode != 0:
         raise SystemExit(p.stderr)
     out, cur = [], None
     for ln in p.stderr.splitlines():
         m = re.search(r"Function Name: (\S+)", ln)
         if m:
-            cur = dict(name=m.group(1)) if "decode_linear_kernel" in m.group(1) else None
+            cur = dict(name=m.group(1)) if ("decode_linear_fp8_kernel" if fp8 else "decode_linear_kernel") in m.group(1) else None
             if cur is not None:
                 out.append(cur)
             continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", ln)
+        m = re.search(r"remark:\s+.*?(VGPRs Spill|SGPRs Spill|VGPRs|AGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", ln)
         if m and cur is not None:
-            cur[m.group(1).split(" ")[0]] = int(m.group(2))
+            cur[m.group(1) if m.group(1).endswith("Spill") else m.group(1).split(" ")[0]] = int(m.group(2))
     for r in out:
         m = re.search(r"ILi(\d)ELb([01])E", r["name"])
         r["tiles"], r["norm"] = int(m.group(1)), bool(int(m.group(2)))
@@ -164,7 +194,8 @@ def resource_usage() -> list:
 
 def main() -> None:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "decode_linear.md"))
+    ap.add_argument("--out")
+    ap.add_argument("--fp8", action="store_true", help="the e4m3 weight stream against the bf16 decode_linear arm -> profiles/decode_fp8.md")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--quick", action="store_true", help="first batch only (rehearsal)")
@@ -172,22 +203,24 @@ def main() -> None:
     ap.add_argument("--dump-resources", metavar="FILE")
     ap.add_argument("--child", nargs=2, metavar=("GEOM", "ARM"))
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "decode_fp8.md" if a.fp8 else "decode_linear.md")
     if a.dump_resources:
         with open(a.dump_resources, "w") as fh:
-            json.dump(resource_usage(), fh, indent=1)
+            json.dump(resource_usage(a.fp8), fh, indent=1)
         return
     if a.iters < 30:
         ap.error("--iters: at least 30")
     if a.child:
-        child(a.child[0], a.child[1], a.iters, a.warmup, a.quick)
+        child(a.child[0], a.child[1], a.iters, a.warmup, a.quick, a.fp8)
         return
     recs = {}
     for geom in GEOMS:
-        for arm in ("on", "off"):
-            env = dict(os.environ, CAMBRIAN_AMD_DECODE_LINEAR="1" if arm == "on" else "0")
+        for arm in (("fp8", "on") if a.fp8 else ("on", "off")):
+            env = dict(os.environ, CAMBRIAN_AMD_DECODE_LINEAR="0" if arm == "off" else "1",
+                       CAMBRIAN_AMD_DECODE_FP8="1" if arm == "fp8" else "0")
             env.pop("CAMBRIAN_AMD_DECODE_ATTN", None)
             cmd = [sys.executable, os.path.abspath(__file__), "--child", geom, arm, "--iters", str(a.iters),
-                   "--warmup", str(a.warmup)] + (["--quick"] if a.quick else [])
+                   "--warmup", str(a.warmup)] + (["--quick"] if a.quick else []) + (["--fp8"] if a.fp8 else [])
             p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
             if p.returncode != 0:                   # a child that failed ends the run: nothing else is started on the GPU
                 sys.stderr.write(p.stdout + p.stderr)
@@ -201,10 +234,14 @@ def main() -> None:
         with open(a.resources) as fh:
             res = json.load(fh)
     else:
-        res = resource_usage()
+        res = resource_usage(a.fp8)
 
     def f(t3):
         return f"{t3[0]:.1f} ({t3[1]:.1f} - {t3[2]:.1f})"
+
+    if a.fp8:
+        write_fp8(a, recs, res, f)
+        return
 
     lines = ["# Decode step: `cmb_decode_linear` (five launches per layer) against the stock sequence", "",
              f"Command: `python tools/bench_decode_linear.py --iters {a.iters} --warmup {a.warmup}`" + (" `--quick`" if a.quick else ""),
@@ -266,6 +303,78 @@ def main() -> None:
     for r in sorted(res, key=lambda r: (r["norm"], r["tiles"])):
         lines.append(f"| {8 * r['tiles']} | {'yes' if r['norm'] else 'no'} | {r.get('VGPRs')} | {r.get('AGPRs')} | {r.get('TotalSGPRs')} | "
                      f"{r.get('LDS')} | {r.get('ScratchSize')} | {r.get('Occupancy')} |")
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
+def write_fp8(a, recs, res, f) -> None:
+    """profiles/decode_fp8.md: the e4m3 stream (arm ``fp8``) against the bf16 ``decode_linear`` arm (``on``, the yardstick)"""
+    from cambrian_amd import ops
+    lines = ["# Decode step: `cmb_decode_linear_fp8` (e4m3 weights, one byte per weight) against the bf16 `cmb_decode_linear`", "",
+             f"Command: `python tools/bench_decode_linear.py --fp8 --iters {a.iters} --warmup {a.warmup}`" + (" `--quick`" if a.quick else ""),
+             f"on an MI355X, bf16 activations, context {CTX}, one decoder layer with random frozen weights; HIP "
+             f"events, median of 3 windows of {a.iters} calls (min - max in brackets), each arm in its own process, arms alternating.  "
+             "`fp8` = `CAMBRIAN_AMD_DECODE_FP8=1` (`layer.decode(..., fp8=True)`, `ops.decode_linear_fp8`), `bf16` = the default path "
+             "(`ops.decode_linear`: the yardstick).  Every call takes the next of a ring of weight sets of at least 768 MB of the "
+             "1-byte weights, in both arms.  MB = the bytes the arm streams (1 or 2 per weight); GB/s = fp8 MB / fp8 time, the share "
+             f"is of the ~{HBM_TBPS} TB/s an MI355X achieves from HBM.  A row is **faster** when the fp8 arm's median is below the "
+             "bf16 arm's minimum window.", "",
+             "## One `layer.decode` call", "",
+             "| model | B | fp8 MB | fp8 us | bf16 us | bf16 / fp8 | fp8 GB/s | of HBM | verdict |", "|---|---|---|---|---|---|---|---|---|"]
+    slow = []
+    for geom in GEOMS:
+        for B in BATCHES:
+            o, z = recs.get((geom, B, "fp8")), recs.get((geom, B, "on"))
+            if o is None or z is None:
+                continue
+            if not o["layer_fp8"]:
+                lines.append(f"| {geom} | {B} | - | {f(o['layer_us'])} | {f(z['layer_us'])} | - | - | - | not taken: the layer refused a weight (K > "
+                             f"{ops.DECODE_FP8_MAX_K}, the row quantiser's reach, or K % 16), made no copy and ran on bf16 in both arms |")
+                slow.append(f"{geom} B {B} layer (mode not taken)")
+                continue
+            mb = sum(o["bytes"].values())
+            gbs = mb / (o["layer_us"][0] * 1e-6) / 1e9
+            fast = o["layer_us"][0] < z["layer_us"][1]
+            if not fast:
+                slow.append(f"{geom} B {B} layer")
+            lines.append(f"| {geom} | {B} | {mb / 1e6:.1f} | {f(o['layer_us'])} | {f(z['layer_us'])} | "
+                         f"{z['layer_us'][0] / o['layer_us'][0]:.2f} | {gbs:.0f} | {gbs / (HBM_TBPS * 1e3) * 100:.0f} % | "
+                         f"{'faster' if fast else 'not faster'} |")
+    lines += ["", "## The four linears alone (one `ops.decode_linear_fp8` call against one `ops.decode_linear` call)", "",
+              "Small linears sit on the host's launch floor (the timed loop issues every call from Python, as `generate()` does): "
+              "where a linear's time stays put while its MB change, the floor is what is timed and the GB/s column is not a figure "
+              "of the kernel.", "",
+              "| model | B | linear | N x K | fp8 MB | fp8 us | bf16 us | bf16 / fp8 | fp8 GB/s | of HBM | verdict |",
+              "|---|---|---|---|---|---|---|---|---|---|---|"]
+    for geom in GEOMS:
+        shapes = linear_shapes({k: v for k, v in GEOMS[geom].items() if k != "lm"})
+        for B in BATCHES:
+            o, z = recs.get((geom, B, "fp8")), recs.get((geom, B, "on"))
+            if o is None or z is None:
+                continue
+            for k in LINEARS:
+                mb = o["bytes"][k]
+                gbs = mb / (o[k + "_us"][0] * 1e-6) / 1e9
+                fast = o[k + "_us"][0] < z[k + "_us"][1]
+                if not fast:
+                    slow.append(f"{geom} B {B} {k}")
+                lines.append(f"| {geom} | {B} | {k} | {shapes[k][0]} x {shapes[k][1]} | {mb / 1e6:.1f} | {f(o[k + '_us'])} | "
+                             f"{f(z[k + '_us'])} | {z[k + '_us'][0] / o[k + '_us'][0]:.2f} | {gbs:.0f} | "
+                             f"{gbs / (HBM_TBPS * 1e3) * 100:.0f} % | {'faster' if fast else 'not faster'} |")
+    done = [f"{g} {k}: {'faster' if (g + ' B 1 ' + k) not in slow else 'NOT faster'}" for g in ("llama3-8b", "yi-34b")
+            for k in ("gate_up", "down") if (g, 1, "fp8") in recs]
+    lines += ["", "## Verdict", "",
+              "The rows the mode exists for (B = 1, time grows with bytes) — " + "; ".join(done) + ".",
+              "Not faster (fp8 median not below the bf16 minimum): " + ("; ".join(slow) if slow else "nowhere") + ".",
+              "The mode stays opt-in whatever this table says: it changes numerics.", "",
+              "## Kernel resource usage (`hipcc -Rpass-analysis=kernel-resource-usage -fno-slp-vectorize`, gfx950)", "",
+              "| slab rows | norm prologue | VGPRs | AGPRs | SGPRs | VGPR spills | SGPR spills | LDS bytes | scratch bytes / lane | waves / SIMD |",
+              "|---|---|---|---|---|---|---|---|---|---|"]
+    for r in sorted(res, key=lambda r: (r["norm"], r["tiles"])):
+        lines.append(f"| {8 * r['tiles']} | {'yes' if r['norm'] else 'no'} | {r.get('VGPRs')} | {r.get('AGPRs')} | {r.get('TotalSGPRs')} | "
+                     f"{r.get('VGPRs Spill')} | {r.get('SGPRs Spill')} | {r.get('LDS')} | {r.get('ScratchSize')} | {r.get('Occupancy')} |")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
