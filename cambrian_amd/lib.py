@@ -176,6 +176,31 @@ class ResampleAccumDesc(C.Structure):
     ]
 
 
+class DecodeLayer(C.Structure):
+    """cmb_decode_layer (include/cambrian_amd.h): one decoder layer's operands of cmb_decode_step, in host memory."""
+    _fields_ = [
+        ("w_qkv", C.c_void_p), ("ld_qkv", C.c_int64), ("w_qkv_scale", C.c_void_p),
+        ("w_o", C.c_void_p), ("ld_o", C.c_int64), ("w_o_scale", C.c_void_p),
+        ("w_gate_up", C.c_void_p), ("ld_gate_up", C.c_int64), ("w_gate_up_scale", C.c_void_p),
+        ("w_down", C.c_void_p), ("ld_down", C.c_int64), ("w_down_scale", C.c_void_p),
+        ("norm1", C.c_void_p), ("norm2", C.c_void_p),
+        ("kcache", C.c_void_p), ("vcache", C.c_void_p),
+    ]
+
+
+class DecodeStepDesc(C.Structure):
+    """cmb_decode_step_desc (include/cambrian_amd.h): what every step of one generate() call shares."""
+    _fields_ = [
+        ("B", C.c_int32), ("layers", C.c_int32), ("H", C.c_int32), ("I", C.c_int32), ("nh", C.c_int32), ("nkv", C.c_int32),
+        ("hd", C.c_int32), ("fp8", C.c_int32),
+        ("V", C.c_int64),
+        ("eps", C.c_float), ("scale", C.c_float),
+        ("c_sb", C.c_int64), ("c_sh", C.c_int64), ("c_st", C.c_int64),
+        ("final_norm", C.c_void_p),
+        ("head", C.c_void_p), ("ld_head", C.c_int64), ("head_scale", C.c_void_p),
+    ]
+
+
 # symbol -> (restype, argtypes); every symbol of include/cambrian_amd.h must be listed here
 # (tests/test_abi.py cross-checks this table against the header).
 _i32, _i64, _f, _p = C.c_int32, C.c_int64, C.c_float, C.c_void_p
@@ -259,6 +284,11 @@ SIGNATURES = {
     "cmb_decode_linear_fp8": (C.c_int, [_p, _i64, _i32, _p, _f, _p, _i64, _p, _i64, _i64, _i32, _p, _i64, _p, _i64, _i32, _p]),
     "cmb_decode_linear_fp8_supported": (C.c_int, [_i32, _i64, _i64, _i32]),
     "cmb_decode_linear_fp8_plan": (C.c_int, [_i32, _i64, _i64, _i32, _i32, C.POINTER(_i32), C.POINTER(_i64)]),
+    "cmb_decode_step": (C.c_int, [C.POINTER(DecodeStepDesc), C.POINTER(DecodeLayer), _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _p,
+                                  _i64, _p]),
+    "cmb_decode_step_ws": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32, _i64]),
+    "cmb_decode_next": (C.c_int, [_p, _i64, _i32, _i64, _i64, _p, _p, _i64, _i64, _p, _p, _p, _i64, _i64, _p, _i64, _i64, _i64, _p,
+                                  _i64, _i32, _f, _p, _p, _p]),
     "cmb_swiglu_bwd": (C.c_int, [C.c_int, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p]),
     "cmb_resize_coeffs": (C.c_int, [_i32, _i32, _p, _p]),
     "cmb_image_preprocess": (C.c_int, [_p, _p, _i32, _p, _p, _p, _p, _i32, _p, _p, _p]),

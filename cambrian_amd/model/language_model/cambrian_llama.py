@@ -31,6 +31,7 @@ except Exception:  # pragma: no cover - transformers is part of the image
     LlamaConfig = object
     CausalLMOutputWithPast = None
 
+from ... import lib as _lib
 from ... import ops
 from ...constants import IGNORE_INDEX
 from ..cambrian_arch import CambrianMetaForCausalLM, CambrianMetaModel, SvaContext
@@ -368,6 +369,28 @@ class LlamaDecoderLayer(nn.Module):
         x, h = ops.add_rmsnorm(x, a, n2.weight, n2.variance_epsilon)  # x + a and norm(x + a) in one pass
         return self.mlp(h, residual=x)
 
+    def decode_operands(self, x, fp8=False):
+        """(the four weights, their e4m3 copies or None) when ``decode`` runs a step of x [B, 1, H] as five launches, else
+        None.  ``fp8``: ask for the e4m3 copies; None in their place when one weight is refused.  These are ``decode``'s own
+        conditions, restated for ``DecodeStepPlan`` (asked once per ``generate()`` call) so that the per-launch loop, the
+        yardstick of the one-call step, stays line for line what it was."""
+        a, mlp = self.self_attn, self.mlp
+        if x.dtype == torch.bfloat16 and x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS and ops.decode_linear_enabled(x.shape[0]) \
+                and use_decode_kernel(x, a.nh, a.nkv, a.hd):
+            # the packed copies are the prefill's (_fused_frozen_weight: frozen bias-free projections only)
+            w = (_fused_frozen_weight(a, "_w_qkv", (a.q_proj, a.k_proj, a.v_proj)),
+                 a.o_proj.weight if _frozen_plain(a.o_proj) else None,
+                 _fused_frozen_weight(mlp, "_w_gate_up", (mlp.gate_proj, mlp.up_proj)),
+                 mlp.down_proj.weight if _frozen_plain(mlp.down_proj) else None)
+            if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm)):
+                q8 = None
+                if fp8:
+                    q8 = decode_fp8_copies(self, x.shape[0], ((a, "_w_qkv_fp8", w[0], None), (a.o_proj, "_w_fp8", w[1], None),
+                                                              (mlp, "_w_gate_up_fp8", w[2], "swiglu"),
+                                                              (mlp.down_proj, "_w_fp8", w[3], None)))
+                return w, q8
+        return None
+
     def decode(self, x, cos, sin, kcache, vcache, t, key_mask, fp8=False):
         """``fp8``: stream e4m3 copies of the weights where the five-launch step is taken (``ops.decode_fp8_enabled``,
         resolved once by ``generate``)."""
@@ -674,6 +697,20 @@ def filter_logits_top_k_top_p(logits: torch.Tensor, top_k=None, top_p=None) -> t
     return logits
 
 
+def _decode_logits_operands(self, x: torch.Tensor, fp8: bool = False):
+    """(lm_head weight, its e4m3 copy or None) when ``_decode_logits`` takes its one-launch arm, else None: that function's
+    condition restated for ``DecodeStepPlan``, so that the per-launch loop stays what it was."""
+    model, head = self.model, self.lm_head
+    a = model.layers[0].self_attn if len(model.layers) else None        # a decoder without layers keeps the stock line
+    B = x.shape[0]
+    if a is not None and use_decode_kernel(x, a.nh, a.nkv, a.hd) and x.dtype == torch.bfloat16 and B <= ops.DECODE_LINEAR_MAX_ROWS \
+            and ops.decode_linear_enabled(B) and _frozen_plain(head) and not model.norm.weight.requires_grad \
+            and model.norm.weight.dtype == torch.bfloat16 and ops.decode_linear_supported(x[:, 0], head.weight):
+        q8 = decode_fp8_copies(head, B, ((head, "_w_fp8", head.weight, None),)) if fp8 else None
+        return head.weight, (None if q8 is None else q8[0])
+    return None
+
+
 def _decode_logits(self, x: torch.Tensor, fp8: bool = False) -> torch.Tensor:
     """fp32 logits of a decode step from the last layer's x [B, 1, H]: final norm + lm_head in one ``ops.decode_linear``
     launch under the conditions of the layers' five-launch step, else the norm kernel, the stock GEMM and a cast.
@@ -691,6 +728,79 @@ def _decode_logits(self, x: torch.Tensor, fp8: bool = False) -> torch.Tensor:
         return ops.decode_linear(x[:, 0], head.weight, norm_weight=model.norm.weight, eps=model.norm.variance_epsilon,
                                  out_dtype=torch.float32)
     return head(model.norm(x)[:, 0]).float()
+
+
+class DecodeStepPlan:
+    """What the decode steps of ONE ``generate()`` call share when they are issued as one library call per token
+    (``ops.decode_step``): the layer table and the step descriptor in host memory, the objects that own every pointer in
+    them, the workspace and the logits buffer.  ``build`` returns None unless the whole model qualifies — every layer under
+    the five-launch conditions, the lm_head under ``_decode_logits``' condition, with ``fp8`` the e4m3 copies of every weight
+    — and the call then runs on the per-launch loop, unchanged."""
+
+    @classmethod
+    def build(cls, lm, B: int, caches, t_max: int, fp8: bool):
+        model = lm.model
+        if not len(model.layers) or len(caches) != len(model.layers) or not 1 <= B <= ops.DECODE_LINEAR_MAX_ROWS:
+            return None
+        dev = lm.lm_head.weight.device
+        if model.llm_dtype != torch.bfloat16 or dev.type != "cuda":
+            return None
+        cfg = lm.config
+        a0 = model.layers[0].self_attn
+        H, nh, nkv, hd = cfg.hidden_size, a0.nh, a0.nkv, a0.hd
+        x = torch.empty(B, 1, H, dtype=torch.bfloat16, device=dev)       # what the predicates look at; never read
+        head = _decode_logits_operands(lm, x, fp8)
+        if head is None or (fp8 and head[1] is None):
+            return None
+        eps = float(model.norm.variance_epsilon)
+        kc0 = caches[0][0]
+        keep, rows, inter = [x, head, model.norm.weight, caches], [], None
+        for layer, (kc, vc) in zip(model.layers, caches):
+            a = layer.self_attn
+            n1, n2 = layer.input_layernorm, layer.post_attention_layernorm
+            if not hasattr(layer, "decode_operands") or (a.nh, a.nkv, a.hd) != (nh, nkv, hd) \
+                    or float(n1.variance_epsilon) != eps or float(n2.variance_epsilon) != eps:
+                return None
+            found = layer.decode_operands(x, fp8)
+            if found is None or (fp8 and found[1] is None):
+                return None
+            w, q8 = found
+            if w[2].shape[0] % 2 or (inter is not None and w[2].shape[0] // 2 != inter) or w[0].shape != ((nh + 2 * nkv) * hd, H) \
+                    or w[1].shape != (H, nh * hd) or w[3].shape != (H, w[2].shape[0] // 2) or w[2].shape[1] != H:
+                return None
+            inter = w[2].shape[0] // 2
+            if kc.dtype != torch.bfloat16 or vc.dtype != kc.dtype or kc.shape != (B, nkv, kc0.shape[2], hd) \
+                    or vc.shape != kc.shape or kc.stride() != kc0.stride() or vc.stride() != kc0.stride() or kc.stride(3) != 1:
+                return None
+            row = _lib.DecodeLayer()
+            mats = q8 if fp8 else [(wi, None) for wi in w]
+            for name, (m, sc) in zip(("qkv", "o", "gate_up", "down"), mats):
+                setattr(row, "w_" + name, m.data_ptr())
+                setattr(row, "ld_" + name, m.stride(0))
+                setattr(row, "w_" + name + "_scale", _lib.ptr(sc))
+            row.norm1, row.norm2 = n1.weight.data_ptr(), n2.weight.data_ptr()
+            row.kcache, row.vcache = kc.data_ptr(), vc.data_ptr()
+            rows.append(row)
+            keep.append((found, n1.weight, n2.weight))
+        if t_max >= kc0.shape[2]:
+            return None
+        self = cls()
+        hw, hs = head[1] if fp8 else (head[0], None)
+        V = head[0].shape[0]
+        self.desc = _lib.DecodeStepDesc(B=B, layers=len(rows), H=H, I=inter, nh=nh, nkv=nkv, hd=hd, fp8=int(bool(fp8)), V=V, eps=eps,
+                                     scale=1.0 / math.sqrt(hd), c_sb=kc0.stride(0), c_sh=kc0.stride(1), c_st=kc0.stride(2),
+                                     final_norm=model.norm.weight.data_ptr(), head=hw.data_ptr(), ld_head=hw.stride(0),
+                                     head_scale=_lib.ptr(hs))
+        self.table = (_lib.DecodeLayer * len(rows))(*rows)
+        self.keep = keep
+        self.ws = ops.decode_step_workspace(dev, ops.decode_step_ws_floats(B, H, inter, nh, nkv, hd, t_max))
+        self.logits = torch.empty(B, (V + 7) // 8 * 8, dtype=torch.float32, device=dev)[:, :V]
+        self.B, self.H, self.hd, self.t_max = B, H, hd, t_max
+        return self
+
+    def step(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, t: int, key_valid: torch.Tensor) -> torch.Tensor:
+        """fp32 logits [B, V] (the plan's buffer, overwritten by the next step) of the token whose embeddings are x [B, H]."""
+        return ops.decode_step(self.desc, self.table, x, cos, sin, t, key_valid, self.ws, self.logits)
 
 
 def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: int = 16, do_sample: bool = False,
@@ -755,6 +865,14 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         theta = float(getattr(self.config, "rope_theta", 10000.0))
         fp8 = ops.decode_fp8_enabled(getattr(self.config, "decode_fp8_weights", False))   # e4m3 weight stream, opt-in
+        plan = None                                                                       # one library call per token, opt-in
+        if max_new_tokens > 1 and ops.decode_step_enabled(getattr(self.config, "decode_step_fused", False)):
+            plan = DecodeStepPlan.build(self, B, caches, Lmax - 1, fp8)
+        if plan is not None and not (do_sample and temperature > 0):
+            emb = model.embed_tokens.weight
+            if emb.dtype == torch.bfloat16 and emb.stride(1) == 1 and emb.stride(0) % 8 == 0 and emb.data_ptr() % 16 == 0 \
+                    and emb.shape[0] >= logits.shape[1] and (eos_token_id is None or 0 <= int(eos_token_id) < emb.shape[0]):
+                return _greedy_fused(plan, emb, logits, key_mask, n_tok, L, max_new_tokens, eos_token_id, hd, theta)
         for step in range(max_new_tokens):
             if do_sample and temperature > 0:
                 warped = filter_logits_top_k_top_p(logits / temperature, top_k, top_p)
@@ -771,10 +889,42 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
             key_mask[:, t] = True
             cos, sin = ops.rope_table((n_tok + step)[:, None], hd, theta)
             x = model.embed_tokens(nxt)[:, None, :].to(model.llm_dtype)
+            if plan is not None:                 # sampling: torch's warpers above, the layers and the logits in one call
+                logits = plan.step(x[:, 0], cos, sin, t, key_mask)
+                continue
             for layer, (kc, vc) in zip(model.layers, caches):
                 x = layer.decode(x, cos, sin, kc, vc, t, key_mask, fp8=fp8)      # [B, Lmax]: the step reads columns 0..t
             logits = _decode_logits(self, x, fp8)
         return torch.stack(out_ids, 1)
+
+
+def _greedy_fused(plan, emb, logits, key_mask, n_tok, L0: int, max_new_tokens: int, eos_token_id, hd: int, theta: float):
+    """The greedy loop as two library calls per token and no ATen call: ``ops.decode_next`` (selection, eos rule, position,
+    key mask, embedding row, RoPE table) then ``ops.decode_step`` (every layer and the lm_head).  The first token comes from
+    the prefill ``logits`` through the same selection.  With an eos id the host reads ``done`` only every
+    ``ops.DECODE_STEP_POLL`` steps, so the loop may run up to that many tokens past the point where every row is done;
+    ``ops.trim_after_all_done`` cuts the result back to the column where the per-token loop stops."""
+    B = logits.shape[0]
+    dev = logits.device
+    eos = -1 if eos_token_id is None else int(eos_token_id)
+    out = torch.zeros(B, max_new_tokens, dtype=torch.int64, device=dev)
+    done = torch.zeros(B, dtype=torch.bool, device=dev) if eos >= 0 else None
+    pos = torch.empty(B, dtype=torch.int64, device=dev)
+    x = torch.empty(B, plan.H, dtype=torch.bfloat16, device=dev)
+    cos = torch.empty(B, hd // 2, dtype=torch.float32, device=dev)
+    sin = torch.empty_like(cos)
+    n_tok = n_tok.contiguous()
+    n = 0
+    for step in range(max_new_tokens):
+        ops.decode_next(logits, eos, done, out, step, n_tok, pos, key_mask, L0 + step, emb, x, hd, theta, cos, sin)
+        n = step + 1
+        if n == max_new_tokens or (eos >= 0 and n % ops.DECODE_STEP_POLL == 0 and bool(done.all())):
+            break
+        logits = plan.step(x, cos, sin, L0 + step, key_mask)
+    ids = out[:, :n]
+    if eos >= 0:
+        ids = ops.trim_after_all_done(ids, eos)
+    return ids.contiguous()
 
 
 CambrianLlamaForCausalLM.generate = _generate

@@ -144,6 +144,22 @@ class Phi3DecoderLayer(nn.Module):
         x = x + self.self_attn.decode(self.input_layernorm(x), cos, sin, kcache, vcache, t, key_mask)
         return x + self.mlp(self.post_attention_layernorm(x))
 
+    def decode_operands(self, x, fp8=False):
+        """(the four weights, their e4m3 copies or None) when ``decode`` runs a step of x as five launches, else None:
+        ``decode``'s conditions restated for ``DecodeStepPlan`` (see LlamaDecoderLayer.decode_operands)."""
+        a, mlp = self.self_attn, self.mlp
+        if x.dtype == torch.bfloat16 and x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS and ops.decode_linear_enabled(x.shape[0]) \
+                and use_decode_kernel(x, a.nh, a.nkv, a.hd):
+            mods = (a.qkv_proj, a.o_proj, mlp.gate_up_proj, mlp.down_proj)
+            w = tuple(m.weight if _frozen_plain(m) else None for m in mods)
+            if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm)):
+                q8 = None
+                if fp8:
+                    q8 = decode_fp8_copies(self, x.shape[0], tuple(
+                        (m, "_w_fp8", wi, "swiglu" if m is mlp.gate_up_proj else None) for m, wi in zip(mods, w)))
+                return w, q8
+        return None
+
 
 class CambrianPhi3Model(CambrianLlamaModel):
     """``CambrianMetaModel`` + Phi-3 backbone (cambrian_phi3.py:38-43)."""

@@ -2396,6 +2396,81 @@ def decode_linear_fp8(x: torch.Tensor, q: torch.Tensor, inv_scale: torch.Tensor,
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# the whole decode step as one library call (decode_step.hip) and the greedy selection between two steps as another
+# (decode_next.hip).  Opt-in (``config.decode_step_fused`` / CAMBRIAN_AMD_DECODE_STEP), off by default: the kernels and
+# their arguments are those of the five-launch path, what changes is who issues them.  The wrappers are thin on purpose
+# (the point is the host's time per token): the caller — ``cambrian_llama`` — establishes every condition once per
+# ``generate()`` call, and the library checks every argument rule again before it launches anything.
+# ------------------------------------------------------------------------------------------------
+DECODE_STEP_POLL = 8           # with an eos id the host reads ``done`` at most every this many steps
+_DECODE_STEP_WS: dict = {}     # device -> fp32 workspace of cmb_decode_step, grown on demand and reused (like _DECODE_WS)
+
+
+def decode_step_enabled(config_flag: bool = False) -> bool:
+    """Whether decode steps of ``generate()`` are issued as one library call per token: ``CAMBRIAN_AMD_DECODE_STEP`` =
+    ``1`` / ``0`` in the environment overrides, unset it is ``config_flag`` (the model's ``config.decode_step_fused``,
+    absent = off)."""
+    v = os.environ.get("CAMBRIAN_AMD_DECODE_STEP")
+    if v is None or v == "":
+        return bool(config_flag)
+    return v != "0"
+
+
+def decode_step_ws_floats(B: int, H: int, I: int, nh: int, nkv: int, hd: int, t_max: int) -> int:
+    """fp32 elements of the workspace ``decode_step`` needs for steps up to cache slot ``t_max``."""
+    need = int(L.load().cmb_decode_step_ws(B, H, I, nh, nkv, hd, t_max))
+    if need < 0:
+        L.check(need, "cmb_decode_step_ws")
+    return need
+
+
+def decode_step_workspace(device, floats: int) -> torch.Tensor:
+    """The device's shared workspace, at least ``floats`` long."""
+    ws = _DECODE_STEP_WS.get(device)
+    if ws is None or ws.numel() < floats:
+        ws = _DECODE_STEP_WS[device] = torch.empty(max(int(floats), 4), dtype=torch.float32, device=device)
+    return ws
+
+
+def decode_step(desc, layers, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, t: int, key_valid: torch.Tensor,
+                ws: torch.Tensor, logits: torch.Tensor) -> torch.Tensor:
+    """One token through every decoder layer and the lm_head: ``desc`` (``lib.DecodeStepDesc``) and ``layers`` (a ctypes
+    array of ``lib.DecodeLayer``) describe the model, x bf16 [B, H], cos / sin the fp32 tables of ``rope_table``, ``t`` the
+    cache slot, key_valid bool / uint8 [B, >= t+1], ``ws`` from ``decode_step_workspace``; fp32 logits [B, V] are written
+    into ``logits`` (row stride a multiple of 8) and returned.  Inference only."""
+    L.call("cmb_decode_step", C.byref(desc), layers, x.data_ptr(), x.stride(0), cos.data_ptr(), sin.data_ptr(), t,
+           key_valid.data_ptr(), key_valid.stride(0), ws.data_ptr(), ws.numel(), logits.data_ptr(), logits.stride(0),
+           device=x.device)
+    return logits
+
+
+def decode_next(logits: torch.Tensor, eos: int, done: Optional[torch.Tensor], out_ids: torch.Tensor, step: int,
+                n_tok: torch.Tensor, pos: torch.Tensor, key_valid: torch.Tensor, t: int, embed: torch.Tensor, x: torch.Tensor,
+                hd: int, rope_base: float, cos: torch.Tensor, sin: torch.Tensor) -> None:
+    """Greedy selection and the next step's inputs in one launch (+ the RoPE-table launch): per row ``nxt = argmax(logits)``
+    (fp32 [B, V], any row stride; torch.argmax's tie and NaN rules), with ``eos`` >= 0 (-1: none) ``nxt = done ? eos : nxt;
+    done |= nxt == eos``; writes ``out_ids[:, step] = nxt`` (int64), ``pos = n_tok + step`` (int64 [B]), ``key_valid[:, t] =
+    1``, ``x = embed[nxt]`` (bf16 rows) and cos / sin = ``rope_table(pos)``.  Every tensor is the caller's, on one GPU."""
+    B, V = logits.shape
+    L.call("cmb_decode_next", logits.data_ptr(), logits.stride(0), B, V, eos, L.ptr(done), out_ids.data_ptr(), out_ids.stride(0),
+           step, n_tok.data_ptr(), pos.data_ptr(), key_valid.data_ptr(), key_valid.stride(0), t, embed.data_ptr(),
+           embed.stride(0), embed.shape[0], embed.shape[1], x.data_ptr(), x.stride(0), hd, rope_base, cos.data_ptr(),
+           sin.data_ptr(), device=logits.device)
+
+
+def trim_after_all_done(ids: torch.Tensor, eos_token_id: int) -> torch.Tensor:
+    """``ids`` [B, n] of a greedy loop that ran past the point where every row had produced ``eos_token_id`` (it polls
+    ``done`` only every ``DECODE_STEP_POLL`` steps): the columns up to and including the first one at which every row is done
+    — a row is done from its first eos on — which is where a loop that tests ``done.all()`` after every token stops.  All
+    of ``ids`` when no such column exists."""
+    if ids.shape[1] == 0:
+        return ids
+    all_done = ((ids == eos_token_id).long().cumsum(dim=1) > 0).all(dim=0)
+    hit = torch.nonzero(all_done)
+    return ids if hit.numel() == 0 else ids[:, :int(hit[0, 0]) + 1]
+
+
 # ================================================================================================
 # optimizer: global gradient norm and the one-pass AdamW step (optim.hip) over lists of tensors
 # ================================================================================================

@@ -68,7 +68,8 @@ const char* cmb_version(void);
  * cmb_resample_bilinear_bwd = 13).  cmb_resample_accum and its descriptor, and later the optimizer entry points
  * (cmb_optim_chunks, cmb_grad_sqnorm, cmb_grad_sqnorm_workspace, cmb_adamw_step), and after them the decode-step linear
  * (cmb_decode_linear, cmb_decode_linear_supported, cmb_decode_linear_plan) and its 1-byte-weight form
- * (cmb_decode_linear_fp8, cmb_decode_linear_fp8_supported, cmb_decode_linear_fp8_plan) were ADDED under revision 13: no existing
+ * (cmb_decode_linear_fp8, cmb_decode_linear_fp8_supported, cmb_decode_linear_fp8_plan), and then the one-call decode step
+ * (cmb_decode_step, cmb_decode_step_ws, cmb_decode_next and the two descriptors) were ADDED under revision 13: no existing
  * signature or layout changed, which is the rule for a bump, so a binding written against 13 still calls everything it
  * knows correctly.  Bindings must compare it
  * with the revision they
@@ -757,6 +758,58 @@ int cmb_decode_linear_fp8(const void* x, int64_t x_ld, int32_t M, const void* no
                           int64_t r_ld, void* out, int64_t o_ld, int32_t out_f32, void* stream);
 int cmb_decode_linear_fp8_supported(int32_t M, int64_t N, int64_t K, int32_t act);
 int cmb_decode_linear_fp8_plan(int32_t M, int64_t N, int64_t K, int32_t act, int32_t cus, int32_t* rows_out, int64_t* wgs_out);
+/* One token's pass through the whole decoder in ONE call (generate(); the decode-step loop over HF LlamaDecoderLayer /
+ * Phi3DecoderLayer and the lm_head): per layer norm + QKV linear, cmb_decode_attn (with its combine launch when the plan
+ * splits), o_proj + skip, norm + gate / up + SwiGLU, down_proj + skip; then final norm + lm_head into fp32 logits.  It calls
+ * cmb_decode_linear / cmb_decode_linear_fp8 / cmb_decode_attn with the arguments the five-launch path passes, 5 layers + 1
+ * launches (+ 1 per layer when the attention splits) on `stream`, ordered by the stream alone: no new GEMM or attention kernel,
+ * no grid-wide barrier, no device-side flag, so logits and caches carry the bits of the separate calls.
+ * cmb_decode_layer, one per layer, in HOST memory: the four weights [N, K] with their row strides (bf16: elements; fp8: bytes
+ * of e4m3fn with w_*_scale the fp32 row factors of cmb_quantize_fp8_rows, else NULL), both RMSNorm weights (bf16 [H]) and the
+ * layer's K / V caches [B, nkv, Lmax, hd].  w_qkv is [(nh + 2 nkv) hd, H] (q | k | v heads), w_o [H, nh hd], w_gate_up
+ * [2 I, H] ([gate; up], cmb_decode_linear's act = 1), w_down [H, I].
+ * cmb_decode_step_desc: geometry, eps (every norm), the attention scale, the caches' element strides (shared by all layers),
+ * the final norm and the lm_head [V, H]; fp8 != 0: every weight of every layer and the head is e4m3 with row factors.
+ * Per call: x bf16 [B, H] (row stride x_ld, outside ws), cos_t / sin_t fp32 [B, hd/2], cache slot t, key_valid bytes
+ * [B, >= t+1] (row stride kv_ld), ws fp32 [>= cmb_decode_step_ws(...) at this t] (csrc/decode_step_layout.h), logits fp32
+ * [B, V] with row stride logits_ld (a multiple of 8).  bf16 only.
+ * Every rule is checked before any launch: CMB_ERR_BAD_ARG for a NULL pointer, layers < 1, B outside 1 .. 16, a geometry or
+ * stride the launchers refuse, x inside ws; CMB_ERR_ALIGNMENT for a pointer that is not 16-byte aligned (row factors: 4) or a
+ * cache stride that is no multiple of 8 elements; CMB_ERR_WORKSPACE for ws_floats below the need.
+ * cmb_decode_step_ws: floats of ws for steps up to slot t_max (non-decreasing in t_max), or a negative status. */
+typedef struct cmb_decode_layer {
+  const void* w_qkv; int64_t ld_qkv; const float* w_qkv_scale;
+  const void* w_o; int64_t ld_o; const float* w_o_scale;
+  const void* w_gate_up; int64_t ld_gate_up; const float* w_gate_up_scale;
+  const void* w_down; int64_t ld_down; const float* w_down_scale;
+  const void* norm1; const void* norm2;
+  void* kcache; void* vcache;
+} cmb_decode_layer;
+typedef struct cmb_decode_step_desc {
+  int32_t B, layers, H, I, nh, nkv, hd, fp8;
+  int64_t V;
+  float eps, scale;
+  int64_t c_sb, c_sh, c_st;
+  const void* final_norm;
+  const void* head; int64_t ld_head; const float* head_scale;
+} cmb_decode_step_desc;
+int cmb_decode_step(const cmb_decode_step_desc* d, const cmb_decode_layer* layers, const void* x, int64_t x_ld,
+                    const float* cos_t, const float* sin_t, int64_t t, const uint8_t* key_valid, int64_t kv_ld, float* ws,
+                    int64_t ws_floats, float* logits, int64_t logits_ld, void* stream);
+int64_t cmb_decode_step_ws(int32_t B, int32_t H, int32_t I, int32_t nh, int32_t nkv, int32_t hd, int64_t t_max);
+/* Greedy token selection and the next step's inputs in one launch (+ the cmb_rope_table launch), one workgroup per row b:
+ *   nxt = argmax(logits[b, 0..V))       fp32 logits, row stride logits_ld; ties: the lowest index; a NaN is greater than
+ *                                       every number and the first NaN wins (torch.argmax's rules); -0 == +0
+ *   eos >= 0:  nxt = done[b] ? eos : nxt;  done[b] |= (nxt == eos)            (eos = -1: none, done may be NULL)
+ *   out_ids[b * out_ld + step] = nxt;  pos[b] = n_tok[b] + step;  key_valid[b * kv_ld + t] = 1;
+ *   x[b, 0..H) = embed[nxt, 0..H)       bf16 rows copied in 16-byte pieces (H % 8 == 0, strides multiples of 8)
+ * then cos_t / sin_t [B, hd/2] = cmb_rope_table(pos, B, hd, rope_base).  No atomics, the same bits on every run.
+ * CMB_ERR_BAD_ARG: a NULL pointer, B outside 1 .. 16, V < 1 or > 2^31 - 1, V > embed_rows, eos outside -1 .. embed_rows - 1,
+ * step, t < 0, step >= out_ld, t >= kv_ld, H, hd or a stride out of rule; CMB_ERR_ALIGNMENT: embed or x not 16-byte aligned. */
+int cmb_decode_next(const float* logits, int64_t logits_ld, int32_t B, int64_t V, int64_t eos, uint8_t* done,
+                    int64_t* out_ids, int64_t out_ld, int64_t step, const int64_t* n_tok, int64_t* pos, uint8_t* key_valid,
+                    int64_t kv_ld, int64_t t, const void* embed, int64_t embed_ld, int64_t embed_rows, int64_t H, void* x,
+                    int64_t x_ld, int32_t hd, float rope_base, float* cos_t, float* sin_t, void* stream);
 /* Backward of h = silu(g) * u (Llama MLP gate; forward is cmb_act_mul with CMB_ACT_SILU):
  * dg = dh * u * silu'(g), du = dh * silu(g); all [rows, D] with row strides. */
 int cmb_swiglu_bwd(int dtype, const void* dh, int64_t lddh, const void* g, int64_t ldg, const void* u, int64_t ldu,

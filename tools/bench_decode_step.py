@@ -1,0 +1,254 @@
+"""Decode steps of ``generate()``: one library call per token (``CAMBRIAN_AMD_DECODE_STEP=1``: ``cmb_decode_next`` +
+``cmb_decode_step``) against the per-launch loop (``=0``, the default: the yardstick), same box, same run.
+
+    python tools/bench_decode_step.py [--out profiles/decode_step.md] [--new 64] [--quick] [--parent-tree DIR]
+                                      [--yardstick-repeats N]
+    python tools/bench_decode_step.py --from-log FILE               # no GPU: the table again from a run's output
+    python tools/bench_decode_step.py --dump-resources FILE         # no GPU: hipcc's register / LDS / scratch report
+
+Llama-3-8B geometry at full depth (32 layers, vocabulary 128256) with random frozen weights, text-only prompt of 2048
+tokens, batch 1 / 4 / 16, bf16 weights and e4m3 weights (``CAMBRIAN_AMD_DECODE_FP8=1``), greedy without an eos id and with an
+eos id that never fires (a token the greedy run does not produce; the child checks that the tokens stay the same).  Each
+arm runs in a fresh child process, the arms alternating.  What is timed is the host's wall clock ``generate()`` with the device synchronised — the host's time per token is the subject — as
+    ms per decoded token = (T(1 + new tokens) - T(1 token)) / new
+where T(1 token) is the prefill and the first selection alone (median of 3), so the prefill is not in the figure.  Three
+windows per number (median, min - max).  A row is **faster** when the on arm's median is below the off arm's fastest window.
+``--parent-tree DIR``: a checkout of the parent commit with its own library built; its loop (there is no switch there) is
+timed by the same child as one more arm, to show that this tree's off arm is the parent's; ``--yardstick-repeats N`` then
+runs the off arm and the parent N more times each at batch 1, alternating, each in a fresh process: how far one arm moves
+from process to process, which the three windows of a single process do not show.  A run without a GPU fails; nothing is
+estimated."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import re
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BATCHES = [1, 4, 16]
+CTX = 2048
+TAG = "BENCH_DECODE_STEP "
+YTAG = "BENCH_DECODE_STEP_YARDSTICK "
+
+
+def child(tree: str, arm: str, new: int, quick: bool) -> None:
+    sys.path.insert(0, tree)
+    import torch
+    from cambrian_amd import ops
+    from cambrian_amd.model.language_model import cambrian_llama as CL
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_decode_step: no GPU visible")
+    assert os.path.dirname(os.path.dirname(os.path.abspath(ops.__file__))) == os.path.abspath(tree)
+    prec, switch = arm.split("-")                       # bf16 | fp8, on | off | parent
+    assert ops.decode_fp8_enabled() == (prec == "fp8")
+    if switch != "parent":
+        assert ops.decode_step_enabled() == (switch == "on")
+    dev, dt = torch.device("cuda:0"), torch.bfloat16
+    cfg = CL.llama3_8b_config()
+    torch.manual_seed(0)
+    model = CL.CambrianLlamaForCausalLM(cfg, device=dev, llm_dtype=dt)
+    with torch.no_grad():
+        for p in model.parameters():
+            if p.dim() >= 2:
+                p.normal_(0.0, 0.02)
+    model.requires_grad_(False).eval()
+    calls = {"step": 0}
+    if hasattr(ops, "decode_step"):
+        real = ops.decode_step
+
+        def counted(*a, **kw):
+            calls["step"] += 1
+            return real(*a, **kw)
+
+        ops.decode_step = counted
+
+    def gen(ids, n, eos):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = model.generate(ids, max_new_tokens=n, eos_token_id=eos)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    for B in (BATCHES[:1] if quick else BATCHES):
+        g = torch.Generator().manual_seed(B)
+        ids = torch.randint(0, cfg.vocab_size, (B, CTX), generator=g).to(dev)
+        calls["step"] = 0
+        _, free = gen(ids, 1 + new, None)               # warm-up of every shape; and the tokens the greedy run produces
+        assert free.shape == (B, 1 + new)
+        assert calls["step"] == (new if switch == "on" else 0), f"{arm}: {calls['step']} step calls"
+        eos = next(v for v in range(cfg.vocab_size) if not bool((free == v).any()))      # never fires
+        base = statistics.median(gen(ids, 1, None)[0] for _ in range(3))
+        rec = dict(arm=arm, B=B, ctx=CTX, new=new, prefill_ms=base, tokens=free[0, :8].tolist())
+        for name, e in (("greedy", None), ("greedy_eos", eos)):
+            win = []
+            for _ in range(3):
+                ms, out = gen(ids, 1 + new, e)
+                assert torch.equal(out, free)
+                win.append((ms - base) / new)
+            rec[name] = (statistics.median(win), min(win), max(win))
+        print(TAG + json.dumps(rec), flush=True)
+        del ids
+
+
+def resource_usage() -> list:
+    """hipcc's kernel-resource-usage remarks for decode_next.hip (no GPU needed)"""
+    src = os.path.join(ROOT, "cambrian_amd", "csrc", "decode_next.hip")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    p = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Rpass-analysis=kernel-resource-usage",
+                        "-c", src, "-o", os.devnull], capture_output=True, text=True, cwd=os.path.dirname(src))
+    if p.returncode != 0:
+        raise SystemExit(p.stderr)
+    out, cur = [], None
+    for ln in p.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", ln)
+        if m:
+            cur = dict(name=m.group(1)) if "decode_next_kernel" in m.group(1) else None
+            if cur is not None:
+                out.append(cur)
+            continue
+        m = re.search(r"remark:\s+.*?(VGPRs Spill|SGPRs Spill|VGPRs|AGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", ln)
+        if m and cur is not None:
+            cur[m.group(1) if m.group(1).endswith("Spill") else m.group(1).split(" ")[0]] = int(m.group(2))
+    return out
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "decode_step.md"))
+    ap.add_argument("--new", type=int, default=64, help="decoded tokens per window")
+    ap.add_argument("--quick", action="store_true", help="batch 1 only (rehearsal)")
+    ap.add_argument("--parent-tree", help="checkout of the parent commit, library built: one more arm")
+    ap.add_argument("--yardstick-repeats", type=int, default=0, help="with --parent-tree: extra off / parent runs at batch 1")
+    ap.add_argument("--from-log", help="a run's output: write the table again without running anything")
+    ap.add_argument("--resources", help="JSON written by --dump-resources; without it hipcc is run now")
+    ap.add_argument("--dump-resources", metavar="FILE")
+    ap.add_argument("--child", nargs=2, metavar=("TREE", "ARM"))
+    a = ap.parse_args()
+    if a.dump_resources:
+        with open(a.dump_resources, "w") as fh:
+            json.dump(resource_usage(), fh, indent=1)
+        return
+    if a.new < 16:
+        ap.error("--new: at least 16")
+    if a.child:
+        child(a.child[0], a.child[1], a.new, a.quick)
+        return
+    arms = [("bf16-on", ROOT), ("bf16-off", ROOT)] + ([("bf16-parent", a.parent_tree)] if a.parent_tree else []) \
+        + [("fp8-on", ROOT), ("fp8-off", ROOT)]
+    recs, extra = {}, []
+
+    def run(arm, tree, quick):
+        prec, switch = arm.split("-")
+        env = dict(os.environ, CAMBRIAN_AMD_DECODE_FP8="1" if prec == "fp8" else "0",
+                   CAMBRIAN_AMD_DECODE_STEP="1" if switch == "on" else "0")
+        for k in ("CAMBRIAN_AMD_DECODE_ATTN", "CAMBRIAN_AMD_DECODE_LINEAR", "CAMBRIAN_AMD_LIB", "PYTHONPATH"):
+            env.pop(k, None)
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", os.path.abspath(tree), arm, "--new", str(a.new)] \
+            + (["--quick"] if quick else [])
+        p = subprocess.run(cmd, env=env, cwd=os.path.abspath(tree), capture_output=True, text=True, timeout=420)
+        if p.returncode != 0:                       # a child that failed ends the run: nothing else is started on the GPU
+            sys.stderr.write(p.stdout + p.stderr)
+            raise SystemExit(f"bench_decode_step: child {arm} exited with {p.returncode}")
+        return [json.loads(ln[len(TAG):]) for ln in p.stdout.splitlines() if ln.startswith(TAG)]
+
+    if a.from_log:
+        with open(a.from_log) as fh:
+            for ln in fh:
+                if ln.startswith(YTAG):
+                    extra.append(json.loads(ln[len(YTAG):]))
+                elif ln.startswith(TAG):
+                    r = json.loads(ln[len(TAG):])
+                    recs[r["arm"], r["B"]] = r
+        a.parent_tree = a.parent_tree or ("parent" if any(k[0] == "bf16-parent" for k in recs) else None)
+    else:
+        for arm, tree in arms:
+            for r in run(arm, tree, a.quick):
+                recs[r["arm"], r["B"]] = r
+                print(TAG + json.dumps(r), flush=True)
+        for _ in range(a.yardstick_repeats if a.parent_tree else 0):
+            for arm, tree in (("bf16-off", ROOT), ("bf16-parent", a.parent_tree)):
+                for r in run(arm, tree, True):
+                    extra.append(r)
+                    print(YTAG + json.dumps(r), flush=True)
+    if a.resources:
+        with open(a.resources) as fh:
+            res = json.load(fh)
+    else:
+        res = resource_usage()
+
+    def f(t3):
+        return f"{t3[0]:.3f} ({t3[1]:.3f} - {t3[2]:.3f})"
+
+    lines = ["# Decode steps of `generate()`: one library call per token against the per-launch loop", "",
+             f"Command: `python tools/bench_decode_step.py --new {a.new}`" + (" `--quick`" if a.quick else "")
+             + (" `--parent-tree <checkout of the parent commit>`" if a.parent_tree else "")
+             + (f" `--yardstick-repeats {len(extra) // 2}`" if extra else ""),
+             f"on an MI355X: Llama-3-8B geometry at full depth (32 layers, vocabulary 128256), random frozen weights, a text-only "
+             f"prompt of {CTX} tokens, greedy.  ms per decoded token = (wall clock of `generate()` for 1 + {a.new} tokens - that "
+             "for 1 token, device synchronised) / " + f"{a.new}: the prefill is not in the figure, the host's time per token is.  "
+             "Median of 3 windows (min - max in brackets), each arm in its own process, arms alternating.  `on` = "
+             "`CAMBRIAN_AMD_DECODE_STEP=1` (`cmb_decode_next` + `cmb_decode_step`, two library calls per token), `off` = `0` (the "
+             "per-launch loop, unchanged by this switch: the yardstick).  `eos` = an eos id that never fires: the off arm then "
+             "reads `done` back every token, the on arm every 8.  A row is **faster** when the on arm's median is below the off "
+             "arm's fastest window.", "",
+             "| weights | B | loop | on ms / token | off ms / token | off / on | verdict |", "|---|---|---|---|---|---|---|"]
+    slow = []
+    for prec in ("bf16", "fp8"):
+        for B in BATCHES:
+            o, z = recs.get((prec + "-on", B)), recs.get((prec + "-off", B))
+            if o is None or z is None:
+                continue
+            assert o["tokens"] == z["tokens"], "the arms decoded different tokens"
+            for name, label in (("greedy", "greedy"), ("greedy_eos", "greedy, eos")):
+                fast = o[name][0] < z[name][1]
+                if not fast:
+                    slow.append(f"{prec} B {B} {label}")
+                lines.append(f"| {prec} | {B} | {label} | {f(o[name])} | {f(z[name])} | {z[name][0] / o[name][0]:.2f} | "
+                             f"{'faster' if fast else 'not faster'} |")
+    lines += ["", "Not faster: " + ("; ".join(slow) if slow else "nowhere") + ".",
+              "The switch stays off by default whatever this table says.", ""]
+    if a.parent_tree:
+        lines += ["## The yardstick: this tree's off arm against the parent commit's loop", "",
+                  "The parent commit (its own sources and its own build of the library) timed by the same child process as one "
+                  "more arm.  `moved` = the distance of the two medians, `spread` = the wider of the two arms' windows (max - "
+                  "min).", "",
+                  "| B | loop | off ms / token | parent ms / token | moved | spread | moved / parent |", "|---|---|---|---|---|---|---|"]
+        for B in BATCHES:
+            z, p = recs.get(("bf16-off", B)), recs.get(("bf16-parent", B))
+            if z is None or p is None:
+                continue
+            for name, label in (("greedy", "greedy"), ("greedy_eos", "greedy, eos")):
+                moved = abs(z[name][0] - p[name][0])
+                spread = max(z[name][2] - z[name][1], p[name][2] - p[name][1])
+                lines.append(f"| {B} | {label} | {f(z[name])} | {f(p[name])} | {moved:.3f} | {spread:.3f} | {moved / p[name][0] * 100:.2f} % |")
+        lines.append("")
+        if extra:
+            lines += [f"Batch 1 again, {len(extra) // 2} more fresh processes per arm, alternating (median of 3 windows each): the windows of "
+                      "one process are narrower than the distance between two processes of the same arm, so that distance, not "
+                      "the windows' spread, is the resolution of the comparison above.", "",
+                      "| arm | greedy ms / token, per process | greedy, eos ms / token, per process |", "|---|---|---|"]
+            for arm in ("bf16-off", "bf16-parent"):
+                rs = [r for r in extra if r["arm"] == arm]
+                lines.append(f"| {arm[5:]} | " + ", ".join(f"{r['greedy'][0]:.3f}" for r in rs) + " | "
+                             + ", ".join(f"{r['greedy_eos'][0]:.3f}" for r in rs) + " |")
+            lines.append("")
+    lines += ["## Kernel resource usage of `decode_next_kernel` (`hipcc -Rpass-analysis=kernel-resource-usage`, gfx950)", "",
+              "| VGPRs | AGPRs | SGPRs | VGPR spills | SGPR spills | LDS bytes | scratch bytes / lane | waves / SIMD |",
+              "|---|---|---|---|---|---|---|---|"]
+    for r in res:
+        lines.append(f"| {r.get('VGPRs')} | {r.get('AGPRs')} | {r.get('TotalSGPRs')} | {r.get('VGPRs Spill')} | {r.get('SGPRs Spill')} | "
+                     f"{r.get('LDS')} | {r.get('ScratchSize')} | {r.get('Occupancy')} |")
+    lines.append("(`cmb_decode_step` launches no kernel of its own.)")
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
+if __name__ == "__main__":
+    main()
