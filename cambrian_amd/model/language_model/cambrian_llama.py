@@ -868,10 +868,14 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
         plan = None                                                                       # one library call per token, opt-in
         if max_new_tokens > 1 and ops.decode_step_enabled(getattr(self.config, "decode_step_fused", False)):
             plan = DecodeStepPlan.build(self, B, caches, Lmax - 1, fp8)
-        if plan is not None and not (do_sample and temperature > 0):
+        sampled = bool(do_sample and temperature > 0)
+        if plan is not None and (not sampled or ops.decode_sample_enabled(getattr(self.config, "decode_sample_device", False))):
             emb = model.embed_tokens.weight
             if emb.dtype == torch.bfloat16 and emb.stride(1) == 1 and emb.stride(0) % 8 == 0 and emb.data_ptr() % 16 == 0 \
                     and emb.shape[0] >= logits.shape[1] and (eos_token_id is None or 0 <= int(eos_token_id) < emb.shape[0]):
+                if sampled:
+                    return _sample_fused(plan, emb, logits, key_mask, n_tok, L, max_new_tokens, eos_token_id, hd, theta,
+                                         temperature, top_k, top_p)
                 return _greedy_fused(plan, emb, logits, key_mask, n_tok, L, max_new_tokens, eos_token_id, hd, theta)
         for step in range(max_new_tokens):
             if do_sample and temperature > 0:
@@ -917,6 +921,43 @@ def _greedy_fused(plan, emb, logits, key_mask, n_tok, L0: int, max_new_tokens: i
     n = 0
     for step in range(max_new_tokens):
         ops.decode_next(logits, eos, done, out, step, n_tok, pos, key_mask, L0 + step, emb, x, hd, theta, cos, sin)
+        n = step + 1
+        if n == max_new_tokens or (eos >= 0 and n % ops.DECODE_STEP_POLL == 0 and bool(done.all())):
+            break
+        logits = plan.step(x, cos, sin, L0 + step, key_mask)
+    ids = out[:, :n]
+    if eos >= 0:
+        ids = ops.trim_after_all_done(ids, eos)
+    return ids.contiguous()
+
+
+def _sample_fused(plan, emb, logits, key_mask, n_tok, L0: int, max_new_tokens: int, eos_token_id, hd: int, theta: float,
+                  temperature: float, top_k, top_p):
+    """``_greedy_fused`` with ``ops.decode_sample`` in the place of ``ops.decode_next``: temperature, top-k, top-p and the draw
+    on the device, so sampled decoding too is two library calls per token and no ATen call.  ``top_k`` None / 0 and ``top_p``
+    None / >= 1 mean off; ``top_p <= 0`` raises what ``filter_logits_top_k_top_p`` raises.  The seed is one int64 drawn once
+    per call ON the device from torch's generator (``torch.manual_seed`` governs it, the host never waits for it); the draws of
+    a call are counted by (element, row, step) under that seed, so they are not torch.multinomial's stream."""
+    k = 0 if top_k is None else max(int(top_k), 0)
+    p = 1.0 if top_p is None or float(top_p) >= 1.0 else float(top_p)
+    if not 0.0 < p:
+        raise ValueError(f"`top_p` has to be a float > 0 and <= 1, but is {top_p}")
+    B = logits.shape[0]
+    dev = logits.device
+    inv_t = float(torch.tensor(1.0 / float(temperature), dtype=torch.float32))        # float32(1 / T), formed on the host
+    seed = torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64, device=dev)
+    eos = -1 if eos_token_id is None else int(eos_token_id)
+    out = torch.zeros(B, max_new_tokens, dtype=torch.int64, device=dev)
+    done = torch.zeros(B, dtype=torch.bool, device=dev) if eos >= 0 else None
+    pos = torch.empty(B, dtype=torch.int64, device=dev)
+    x = torch.empty(B, plan.H, dtype=torch.bfloat16, device=dev)
+    cos = torch.empty(B, hd // 2, dtype=torch.float32, device=dev)
+    sin = torch.empty_like(cos)
+    n_tok = n_tok.contiguous()
+    n = 0
+    for step in range(max_new_tokens):
+        ops.decode_sample(logits, inv_t, k, p, seed, eos, done, out, step, n_tok, pos, key_mask, L0 + step, emb, x, hd, theta,
+                          cos, sin)
         n = step + 1
         if n == max_new_tokens or (eos >= 0 and n % ops.DECODE_STEP_POLL == 0 and bool(done.all())):
             break

@@ -2398,7 +2398,8 @@ def decode_linear_fp8(x: torch.Tensor, q: torch.Tensor, inv_scale: torch.Tensor,
 
 # ------------------------------------------------------------------------------------------------
 # the whole decode step as one library call (decode_step.hip) and the greedy selection between two steps as another
-# (decode_next.hip).  Opt-in (``config.decode_step_fused`` / CAMBRIAN_AMD_DECODE_STEP), off by default: the kernels and
+# (decode_next.hip; decode_sample.hip for sampled decoding, behind a switch of its own: ``config.decode_sample_device`` /
+# CAMBRIAN_AMD_DECODE_SAMPLE).  Opt-in (``config.decode_step_fused`` / CAMBRIAN_AMD_DECODE_STEP), off by default: the kernels and
 # their arguments are those of the five-launch path, what changes is who issues them.  The wrappers are thin on purpose
 # (the point is the host's time per token): the caller — ``cambrian_llama`` — establishes every condition once per
 # ``generate()`` call, and the library checks every argument rule again before it launches anything.
@@ -2457,6 +2458,34 @@ def decode_next(logits: torch.Tensor, eos: int, done: Optional[torch.Tensor], ou
            step, n_tok.data_ptr(), pos.data_ptr(), key_valid.data_ptr(), key_valid.stride(0), t, embed.data_ptr(),
            embed.stride(0), embed.shape[0], embed.shape[1], x.data_ptr(), x.stride(0), hd, rope_base, cos.data_ptr(),
            sin.data_ptr(), device=logits.device)
+
+
+def decode_sample_enabled(config_flag: bool = False) -> bool:
+    """Whether sampled decoding of ``generate()`` selects its tokens on the device (``decode_sample``) where the one-call decode
+    step runs: ``CAMBRIAN_AMD_DECODE_SAMPLE`` = ``1`` / ``0`` in the environment overrides, unset it is ``config_flag`` (the
+    model's ``config.decode_sample_device``, absent = off)."""
+    v = os.environ.get("CAMBRIAN_AMD_DECODE_SAMPLE")
+    if v is None or v == "":
+        return bool(config_flag)
+    return v != "0"
+
+
+def decode_sample(logits: torch.Tensor, inv_temperature: float, top_k: int, top_p: float, seed: torch.Tensor, eos: int,
+                  done: Optional[torch.Tensor], out_ids: torch.Tensor, step: int, n_tok: torch.Tensor, pos: torch.Tensor,
+                  key_valid: torch.Tensor, t: int, embed: torch.Tensor, x: torch.Tensor, hd: int, rope_base: float,
+                  cos: torch.Tensor, sin: torch.Tensor, thr: Optional[torch.Tensor] = None,
+                  n_keep: Optional[torch.Tensor] = None) -> None:
+    """``decode_next`` with the argmax replaced by a filtered random draw, in one launch (+ the RoPE-table launch): per row
+    ``z = logits * inv_temperature``, top-k (``top_k`` 0 = off; ties at the k-th value kept), top-p over what top-k kept
+    (``top_p`` 1 = off; equal values kept or dropped together), then Gumbel-max with Philox4x32-10 noise keyed by ``seed`` (one
+    int64 in DEVICE memory) and counted by (element, row, ``step``).  A row whose maximum is not finite takes its argmax.
+    ``thr`` fp32 [B] / ``n_keep`` int32 [B]: optional outputs, the threshold and how many elements passed it.  Everything else
+    as ``decode_next``; the semantics are spelled out at ``cmb_decode_sample`` in include/cambrian_amd.h."""
+    B, V = logits.shape
+    L.call("cmb_decode_sample", logits.data_ptr(), logits.stride(0), B, V, inv_temperature, top_k, top_p, seed.data_ptr(), eos,
+           L.ptr(done), out_ids.data_ptr(), out_ids.stride(0), step, n_tok.data_ptr(), pos.data_ptr(), key_valid.data_ptr(),
+           key_valid.stride(0), t, embed.data_ptr(), embed.stride(0), embed.shape[0], embed.shape[1], x.data_ptr(), x.stride(0),
+           hd, rope_base, cos.data_ptr(), sin.data_ptr(), L.ptr(thr), L.ptr(n_keep), device=logits.device)
 
 
 def trim_after_all_done(ids: torch.Tensor, eos_token_id: int) -> torch.Tensor:

@@ -69,7 +69,8 @@ const char* cmb_version(void);
  * (cmb_optim_chunks, cmb_grad_sqnorm, cmb_grad_sqnorm_workspace, cmb_adamw_step), and after them the decode-step linear
  * (cmb_decode_linear, cmb_decode_linear_supported, cmb_decode_linear_plan) and its 1-byte-weight form
  * (cmb_decode_linear_fp8, cmb_decode_linear_fp8_supported, cmb_decode_linear_fp8_plan), and then the one-call decode step
- * (cmb_decode_step, cmb_decode_step_ws, cmb_decode_next and the two descriptors) were ADDED under revision 13: no existing
+ * (cmb_decode_step, cmb_decode_step_ws, cmb_decode_next and the two descriptors), and then the sampled selection
+ * (cmb_decode_sample) were ADDED under revision 13: no existing
  * signature or layout changed, which is the rule for a bump, so a binding written against 13 still calls everything it
  * knows correctly.  Bindings must compare it
  * with the revision they
@@ -810,6 +811,29 @@ int cmb_decode_next(const float* logits, int64_t logits_ld, int32_t B, int64_t V
                     int64_t* out_ids, int64_t out_ld, int64_t step, const int64_t* n_tok, int64_t* pos, uint8_t* key_valid,
                     int64_t kv_ld, int64_t t, const void* embed, int64_t embed_ld, int64_t embed_rows, int64_t H, void* x,
                     int64_t x_ld, int32_t hd, float rope_base, float* cos_t, float* sin_t, void* stream);
+/* Sampled token selection: cmb_decode_next with the argmax replaced by temperature -> top-k -> top-p -> a random draw, one
+ * workgroup per row b, one launch (+ the cmb_rope_table launch).  With z_i = logits[b, i] * inv_temperature (one fp32 multiply):
+ *   - the row's maximum (cmb_decode_next's order) is not finite — a NaN, +inf, every logit -inf, or z_max overflows:
+ *     nxt = cmb_decode_next's argmax, thr[b] = NaN, n_keep[b] = 0, nothing below applies;
+ *   - top_k > 0: keep i iff z_i >= the min(top_k, V)-th largest z (ties at that value are all kept);  0 = off
+ *   - top_p < 1: over what top-k kept, w_i = exp(z_i - z_max) counted in units of 2^-40, Z = sum w; a value v is kept iff the
+ *     mass of the kept elements with z <= v exceeds (1 - top_p) * Z; the maximum is always kept; equal values are kept or
+ *     dropped together (HF's TopPLogitsWarper splits such ties by its sort order);  1 = off
+ *   - both filters are one threshold, keep iff z_i >= thr (-inf with both off);
+ *   - nxt = the kept i with the largest s_i = z_i + g_i (fp32), the lowest index among equals, where g = -log(-log u),
+ *     u = ((word >> 8) + 0.5) * 2^-24 and word = output (i & 3) of Philox4x32-10 with counter (i >> 2, b, step, 0) and key
+ *     (*seed & 0xFFFFFFFF, *seed >> 32).  `seed` is read on the device.  A row's id depends on (*seed, b, step) and the row
+ *     alone, not on B;
+ * then the eos rule, out_ids, pos, key_valid, x, cos_t / sin_t exactly as cmb_decode_next.  thr [B] and n_keep [B] (the
+ * threshold and how many elements passed it) are optional outputs, NULL = not written.  Integer LDS atomics only: the same bits
+ * on every run.  Argument rules and statuses of cmb_decode_next, checked in its order, and: CMB_ERR_BAD_ARG for seed NULL,
+ * inv_temperature not finite or <= 0, top_p outside (0, 1], top_k < 0; CMB_ERR_ALIGNMENT for seed not 8-byte, thr or n_keep
+ * not 4-byte aligned. */
+int cmb_decode_sample(const float* logits, int64_t logits_ld, int32_t B, int64_t V, float inv_temperature, int64_t top_k,
+                      float top_p, const uint64_t* seed, int64_t eos, uint8_t* done, int64_t* out_ids, int64_t out_ld,
+                      int64_t step, const int64_t* n_tok, int64_t* pos, uint8_t* key_valid, int64_t kv_ld, int64_t t,
+                      const void* embed, int64_t embed_ld, int64_t embed_rows, int64_t H, void* x, int64_t x_ld, int32_t hd,
+                      float rope_base, float* cos_t, float* sin_t, float* thr, int32_t* n_keep, void* stream);
 /* Backward of h = silu(g) * u (Llama MLP gate; forward is cmb_act_mul with CMB_ACT_SILU):
  * dg = dh * u * silu'(g), du = dh * silu(g); all [rows, D] with row strides. */
 int cmb_swiglu_bwd(int dtype, const void* dh, int64_t lddh, const void* g, int64_t ldg, const void* u, int64_t ldu,
