@@ -25,8 +25,6 @@
 // the result has the same bits on every run and does not depend on B.  Then decode_next's tail.
 #include "decode_select.h"
 
-#define DS_BINS 2048
-
 namespace {
 
 struct DsParams {
@@ -35,52 +33,6 @@ struct DsParams {
   const uint64_t* seed;
   float* thr; int32_t* n_keep;
 };
-
-struct DsFound {
-  uint32_t bin;
-  unsigned long long before, total;
-};
-
-// The bin of h[0 .. DS_BINS) at which the running sum reaches `target` (1 <= target <= total), and the sum before that bin;
-// REV: the running sum starts at the last bin.  top_p >= 0: the target is the nucleus target of the total.  Thread t owns two
-// bins that follow each other in scan order; an inclusive scan by shuffles inside a wave, the wave totals through LDS.
-// The caller has a barrier between the last atomic on h and this call.
-template <typename T, bool REV>
-__device__ __forceinline__ DsFound ds_find(const T* h, unsigned long long target, float top_p, int tid, unsigned long long* wsum,
-                                           unsigned long long* found) {
-  const int lane = tid & 63, wave = tid >> 6;
-  const int i0 = REV ? DS_BINS - 1 - 2 * tid : 2 * tid, i1 = REV ? i0 - 1 : i0 + 1;
-  const unsigned long long a = h[i0], s = a + h[i1];
-  unsigned long long inc = s;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned long long up = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += up;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  unsigned long long off = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < DN_WAVES; ++w) {
-    const unsigned long long ws = wsum[w];
-    if (w < wave) off += ws;
-    total += ws;
-  }
-  if (top_p >= 0.f) target = cmb_ds_nucleus_target(top_p, total) + 1;
-  inc += off;
-  const unsigned long long exc = inc - s;
-  if (exc < target && target <= inc) {
-    const bool first = exc + a >= target;
-    found[0] = (unsigned long long)(first ? i0 : i1);
-    found[1] = first ? exc : exc + a;
-  }
-  __syncthreads();
-  DsFound r;
-  r.bin = (uint32_t)found[0];
-  r.before = found[1];
-  r.total = total;
-  return r;
-}
 
 __global__ void __launch_bounds__(DN_THREADS) decode_sample_kernel(DsParams q) {
   __shared__ unsigned long long hist[DS_BINS];      // the count passes use its first half as uint32 bins

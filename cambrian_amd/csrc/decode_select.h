@@ -64,6 +64,55 @@ __device__ __forceinline__ unsigned long long dn_block_max(unsigned long long be
   return m;
 }
 
+// ---- the radix select both filtered selections share (decode_sample.hip: top-k / top-p, decode_beam.hip: a row's K largest) ----
+#define DS_BINS 2048
+
+struct DsFound {
+  uint32_t bin;
+  unsigned long long before, total;
+};
+
+// The bin of h[0 .. DS_BINS) at which the running sum reaches `target` (1 <= target <= total), and the sum before that bin;
+// REV: the running sum starts at the last bin.  top_p >= 0: the target is the nucleus target of the total.  Thread t owns two
+// bins that follow each other in scan order; an inclusive scan by shuffles inside a wave, the wave totals through LDS.
+// The caller has a barrier between the last atomic on h and this call.
+template <typename T, bool REV>
+__device__ __forceinline__ DsFound ds_find(const T* h, unsigned long long target, float top_p, int tid, unsigned long long* wsum,
+                                           unsigned long long* found) {
+  const int lane = tid & 63, wave = tid >> 6;
+  const int i0 = REV ? DS_BINS - 1 - 2 * tid : 2 * tid, i1 = REV ? i0 - 1 : i0 + 1;
+  const unsigned long long a = h[i0], s = a + h[i1];
+  unsigned long long inc = s;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long up = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += up;
+  }
+  if (lane == 63) wsum[wave] = inc;
+  __syncthreads();
+  unsigned long long off = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < DN_WAVES; ++w) {
+    const unsigned long long ws = wsum[w];
+    if (w < wave) off += ws;
+    total += ws;
+  }
+  if (top_p >= 0.f) target = cmb_ds_nucleus_target(top_p, total) + 1;
+  inc += off;
+  const unsigned long long exc = inc - s;
+  if (exc < target && target <= inc) {
+    const bool first = exc + a >= target;
+    found[0] = (unsigned long long)(first ? i0 : i1);
+    found[1] = first ? exc : exc + a;
+  }
+  __syncthreads();
+  DsFound r;
+  r.bin = (uint32_t)found[0];
+  r.before = found[1];
+  r.total = total;
+  return r;
+}
+
 // thread 0 applies the eos rule to the id it was given and writes the id, the position and the key-mask byte; the whole
 // workgroup copies the embedding row in 16-byte pieces.  `chosen`: one int64 of LDS.
 __device__ __forceinline__ void dn_tail(const DnParams& p, int b, int tid, int64_t nxt, int64_t* chosen) {

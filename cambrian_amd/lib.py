@@ -291,6 +291,11 @@ SIGNATURES = {
                                   _i64, _i32, _f, _p, _p, _p]),
     "cmb_decode_sample": (C.c_int, [_p, _i64, _i32, _i64, _f, _i64, _f, _p, _i64, _p, _p, _i64, _i64, _p, _p, _p, _i64, _i64, _p,
                                     _i64, _i64, _i64, _p, _i64, _i32, _f, _p, _p, _p, _p, _p]),
+    "cmb_decode_beam_state_bytes": (_i64, [_i32, _i32, _i64]),
+    "cmb_decode_beam": (C.c_int, [_p, _i64, _i32, _i32, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _p, _i64, _i64,
+                                  _i64, _p, _i64, _i32, _f, _p, _p, C.POINTER(DecodeStepDesc), C.POINTER(DecodeLayer), _i64, _p,
+                                  _p]),
+    "cmb_decode_beam_reorder": (C.c_int, [C.POINTER(DecodeStepDesc), C.POINTER(DecodeLayer), _p, _i32, _i64, _i64, _p]),
     "cmb_swiglu_bwd": (C.c_int, [C.c_int, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p]),
     "cmb_resize_coeffs": (C.c_int, [_i32, _i32, _p, _p]),
     "cmb_image_preprocess": (C.c_int, [_p, _p, _i32, _p, _p, _p, _p, _i32, _p, _p, _p]),

@@ -35,6 +35,7 @@ from ... import lib as _lib
 from ... import ops
 from ...constants import IGNORE_INDEX
 from ..cambrian_arch import CambrianMetaForCausalLM, CambrianMetaModel, SvaContext
+from .beam import BeamState, beam_done, beam_fill, beam_result, beam_update
 
 
 class CambrianConfig(LlamaConfig):
@@ -812,13 +813,22 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
     SVA hook, K/V of every layer kept; decode steps = one token against the cache, no hook (cambrian_llama.py:174).
     Greedy, or sampling with temperature -> top-k -> nucleus top-p as HF's logits warpers define them; returns the NEW
     token ids [B, <= max_new_tokens] (like HF generate() called with inputs_embeds).  The reference inherits the loop from HF
-    GenerationMixin; what this loop does not implement RAISES instead of being dropped: beam search (``num_beams > 1``),
-    ``inputs_embeds`` (the reference raises too, cambrian_llama.py:447-448) and any keyword it does not know."""
+    GenerationMixin; what this loop does not implement RAISES instead of being dropped: beam search (``num_beams > 1``) unless
+    it is switched on (``config.decode_beam_search`` / CAMBRIAN_AMD_DECODE_BEAM=1: ``_beam_search``, HF's beam search without
+    sampling, length penalty 1, no early stopping, one returned sequence), ``inputs_embeds`` (the reference raises too,
+    cambrian_llama.py:447-448) and any keyword it does not know."""
     if "inputs_embeds" in kwargs:
         raise NotImplementedError("`inputs_embeds` is not supported")          # cambrian_llama.py:447-448
-    if num_beams is not None and int(num_beams) > 1:
-        raise NotImplementedError(f"generate(num_beams={num_beams}): beam search is not implemented in cambrian_amd "
-                                  "(greedy / temperature / top-k / top-p sampling only); pass num_beams=1")
+    beams = 1 if num_beams is None else int(num_beams)
+    if beams > 1:
+        if not ops.decode_beam_enabled(getattr(getattr(self, "config", None), "decode_beam_search", False)):
+            raise NotImplementedError(f"generate(num_beams={num_beams}): beam search is not implemented in cambrian_amd "
+                                      "(greedy / temperature / top-k / top-p sampling only); pass num_beams=1, or switch beam "
+                                      "search on (config.decode_beam_search / CAMBRIAN_AMD_DECODE_BEAM=1)")
+        if do_sample:
+            raise NotImplementedError(f"generate(num_beams={num_beams}, do_sample=True): beam sampling is not implemented")
+        if int(max_new_tokens) < 1:
+            raise ValueError(f"generate(num_beams={num_beams}): max_new_tokens has to be >= 1, but is {max_new_tokens}")
     if "max_length" in kwargs and kwargs["max_length"] is not None:
         raise NotImplementedError("generate(max_length=...): use max_new_tokens")
     kwargs.pop("max_length", None)
@@ -851,6 +861,9 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
             last = torch.full_like(last, L - 1)                                      # left padding: the last column
         logits = self.lm_head(hidden[torch.arange(B, device=dev), last]).float()
         nh_kv, hd = model.layers[0].self_attn.nkv, model.layers[0].self_attn.hd
+        if beams > 1:
+            return _beam_search(self, logits, kv_out, valid, L, int(max_new_tokens), eos_token_id, kwargs.get("pad_token_id"),
+                                beams)
         Lmax = L + max_new_tokens
         caches = []
         for k, v in kv_out:
@@ -966,6 +979,90 @@ def _sample_fused(plan, emb, logits, key_mask, n_tok, L0: int, max_new_tokens: i
     if eos >= 0:
         ids = ops.trim_after_all_done(ids, eos)
     return ids.contiguous()
+
+
+def _beam_search(self, logits, kv_out, valid, L: int, max_new_tokens: int, eos_token_id, pad_token_id, nb: int):
+    """Beam search after the prefill (``logits`` fp32 [B, V], ``kv_out`` every layer's K / V of the B prompts): the ``nb`` beams
+    of a prompt are ``nb`` rows of a decode step, so the caches take ``nb`` times the memory of greedy decoding and the
+    prompt's columns are copied into every beam's row.  Where the one-call plan is available the loop is ``_beam_fused``;
+    else selection is ``beam.beam_update`` (plain torch) around ``layer.decode`` / ``plan.step``, and each step moves the
+    generated columns of every cache from the parents' rows with an ``index_select``."""
+    model = self.model
+    B, V = logits.shape
+    dev = logits.device
+    R = B * nb
+    nh_kv, hd = model.layers[0].self_attn.nkv, model.layers[0].self_attn.hd
+    Lmax = L + max_new_tokens
+    caches = []
+    for k, v in kv_out:
+        kc = torch.zeros(R, nh_kv, Lmax, hd, dtype=k.dtype, device=dev)
+        vc = torch.zeros_like(kc)
+        kc.view(B, nb, nh_kv, Lmax, hd)[:, :, :, :L] = k[:, None]
+        vc.view(B, nb, nh_kv, Lmax, hd)[:, :, :, :L] = v[:, None]
+        caches.append((kc, vc))
+    key_mask = torch.zeros(R, Lmax, dtype=torch.bool, device=dev)
+    key_mask[:, :L] = valid.repeat_interleave(nb, dim=0)
+    n_tok = valid.long().sum(1).repeat_interleave(nb).contiguous()
+    logits = logits.repeat_interleave(nb, dim=0)
+    theta = float(getattr(self.config, "rope_theta", 10000.0))
+    fp8 = ops.decode_fp8_enabled(getattr(self.config, "decode_fp8_weights", False))
+    fill = beam_fill(pad_token_id, eos_token_id)
+    plan = None
+    if max_new_tokens > 1 and ops.decode_step_enabled(getattr(self.config, "decode_step_fused", False)):
+        plan = DecodeStepPlan.build(self, R, caches, Lmax - 1, fp8)
+    if plan is not None and R <= ops.DECODE_BEAM_MAX and V >= 2 and V * nb < 2 ** 31:
+        emb = model.embed_tokens.weight
+        if emb.dtype == torch.bfloat16 and emb.stride(1) == 1 and emb.stride(0) % 8 == 0 and emb.data_ptr() % 16 == 0 \
+                and emb.shape[0] >= V and (eos_token_id is None or 0 <= int(eos_token_id) < emb.shape[0]):
+            return _beam_fused(plan, emb, logits, key_mask, n_tok, L, max_new_tokens, eos_token_id, fill, nb, hd, theta)
+    state = BeamState(B, nb, max_new_tokens, dev)
+    first = (torch.arange(B, device=dev) * nb)[:, None]
+    for step in range(max_new_tokens):
+        parent, tok = beam_update(state, logits, step, eos_token_id, step + 1 == max_new_tokens)
+        if step + 1 == max_new_tokens or beam_done(state):
+            break
+        t = L + step
+        if step:
+            rows = (parent + first).reshape(-1)
+            for kc, vc in caches:
+                kc[:, :, L:t] = kc[:, :, L:t].index_select(0, rows)
+                vc[:, :, L:t] = vc[:, :, L:t].index_select(0, rows)
+        key_mask[:, t] = True
+        cos, sin = ops.rope_table((n_tok + step)[:, None], hd, theta)
+        x = model.embed_tokens(tok.reshape(-1))[:, None, :].to(model.llm_dtype)
+        if plan is not None:
+            logits = plan.step(x[:, 0], cos, sin, t, key_mask)
+            continue
+        for layer, (kc, vc) in zip(model.layers, caches):
+            x = layer.decode(x, cos, sin, kc, vc, t, key_mask, fp8=fp8)
+        logits = _decode_logits(self, x, fp8)
+    return beam_result(state, fill)
+
+
+def _beam_fused(plan, emb, logits, key_mask, n_tok, L0: int, max_new_tokens: int, eos_token_id, fill: int, nb: int, hd: int,
+                theta: float):
+    """Beam search as two library calls per token and no ATen call: ``ops.decode_beam`` (selection across the beams, the
+    hypotheses, the early-stop flag, the K / V of the generated columns moved to each beam's row, position, key mask,
+    embedding rows, RoPE table) then ``ops.decode_step``.  With an eos id the host reads the ``unfinished`` byte every
+    ``ops.DECODE_STEP_POLL`` steps; steps past the stopping point cannot change the kept hypotheses (a new one scores 1e9
+    lower once the flag is satisfied).  Without an eos id nothing is read before the last step."""
+    R = logits.shape[0]
+    dev = logits.device
+    eos = -1 if eos_token_id is None else int(eos_token_id)
+    state = ops.DecodeBeamState(R // nb, nb, max_new_tokens, dev)
+    pos = torch.empty(R, dtype=torch.int64, device=dev)
+    x = torch.empty(R, plan.H, dtype=torch.bfloat16, device=dev)
+    cos = torch.empty(R, hd // 2, dtype=torch.float32, device=dev)
+    sin = torch.empty_like(cos)
+    n = 0
+    for step in range(max_new_tokens):
+        ops.decode_beam(logits, nb, eos, state, step, n_tok, pos, key_mask, L0 + step, emb, x, hd, theta, cos, sin, plan.desc,
+                        plan.table, L0)
+        n = step + 1
+        if n == max_new_tokens or (eos >= 0 and n % ops.DECODE_STEP_POLL == 0 and not bool(state.unfinished.item())):
+            break
+        logits = plan.step(x, cos, sin, L0 + step, key_mask)
+    return beam_result(state.view(n), fill)
 
 
 CambrianLlamaForCausalLM.generate = _generate

@@ -2488,6 +2488,84 @@ def decode_sample(logits: torch.Tensor, inv_temperature: float, top_k: int, top_
            hd, rope_base, cos.data_ptr(), sin.data_ptr(), L.ptr(thr), L.ptr(n_keep), device=logits.device)
 
 
+def decode_beam_enabled(config_flag: bool = False) -> bool:
+    """Whether ``generate(num_beams > 1)`` runs beam search (on the device, ``decode_beam``, where the one-call decode step
+    runs; else on the per-launch loop around model/language_model/beam.py) instead of raising: ``CAMBRIAN_AMD_DECODE_BEAM`` =
+    ``1`` / ``0`` in the environment overrides, unset it is ``config_flag`` (the model's ``config.decode_beam_search``, absent =
+    off).  Any other value raises: a typo must not silently pick a side."""
+    v = os.environ.get("CAMBRIAN_AMD_DECODE_BEAM")
+    if v is None or v == "":
+        return bool(config_flag)
+    if v not in ("0", "1"):
+        raise ValueError(f"CAMBRIAN_AMD_DECODE_BEAM={v!r}: the switch takes 1 or 0")
+    return v == "1"
+
+
+DECODE_BEAM_MAX = 16           # CMB_BEAM_MAX of csrc/decode_beam_core.h: beams of one prompt, and rows of a fused decode step
+
+
+class DecodeBeamState:
+    """The state block of ``decode_beam`` (``cmb_decode_beam`` in include/cambrian_amd.h documents the layout): one zeroed
+    uint8 tensor ``buf`` per ``generate()`` call, every section a view into it, plus the ``unfinished`` byte.  ``view(n)`` gives
+    the state after ``n`` steps in the shape of ``beam.BeamState`` ([prompts, num_beams, ...]) for ``beam.beam_result``."""
+
+    def __init__(self, prompts: int, num_beams: int, max_new: int, device):
+        need = int(L.load().cmb_decode_beam_state_bytes(prompts, num_beams, max_new))
+        if need < 0:
+            L.check(need, "cmb_decode_beam_state_bytes")
+        self.prompts, self.num_beams, self.max_new = prompts, num_beams, max_new
+        self.buf = torch.zeros(need + 16, dtype=torch.uint8, device=device)     # the last 16 bytes: the `unfinished` byte
+        R, K, f32, i32, u8 = prompts * num_beams, 2 * num_beams, torch.float32, torch.int32, torch.uint8
+        at = 0
+        for name, dtype, shape in (("run_score", f32, (R,)), ("fin_score", f32, (R,)), ("fin_len", i32, (R,)), ("parent", i32, (R,)),
+                                   ("tok", i32, (R,)), ("cand_lp", f32, (R, K)), ("cand_tok", i32, (R, K)), ("fin_ok", u8, (R,)),
+                                   ("unsat", u8, (prompts,)), ("all_hit", u8, (prompts,)),
+                                   ("run_ids2", torch.int64, (2, R, max_new)), ("fin_ids", torch.int64, (R, max_new))):
+            n = math.prod(shape) * torch.empty(0, dtype=dtype).element_size()      # cmb_beam_make_layout's order and rounding
+            setattr(self, name, self.buf[at:at + n].view(dtype).view(shape))
+            at += (n + 15) // 16 * 16
+        if at != need:
+            raise L.CambrianAmdError(f"decode_beam: the state block's layout ({at} bytes) is not the library's ({need})")
+        self.bytes = need
+        self.unfinished = self.buf[need:need + 1]
+
+    def view(self, steps: int):
+        from .model.language_model.beam import BeamState
+        P, nb, M = self.prompts, self.num_beams, self.max_new
+        st = BeamState.__new__(BeamState)
+        st.run_ids = self.run_ids2[steps & 1].view(P, nb, M)
+        st.run_score, st.fin_score = self.run_score.view(P, nb), self.fin_score.view(P, nb)
+        st.fin_ids, st.fin_len = self.fin_ids.view(P, nb, M), self.fin_len.view(P, nb)
+        st.fin_ok, st.unsat, st.all_hit = self.fin_ok.view(P, nb).bool(), self.unsat.bool(), self.all_hit.bool()
+        return st
+
+
+def decode_beam(logits: torch.Tensor, num_beams: int, eos: int, state: DecodeBeamState, step: int, n_tok: torch.Tensor,
+                pos: torch.Tensor, key_valid: torch.Tensor, t: int, embed: torch.Tensor, x: torch.Tensor, hd: int,
+                rope_base: float, cos: torch.Tensor, sin: torch.Tensor, desc=None, layers=None, L0: int = 0) -> None:
+    """One step of beam search and the next decode step's inputs in one library call: ``logits`` fp32 [prompts * num_beams, V]
+    of the running beams (row ``prompt * num_beams + slot``), ``state`` the call's ``DecodeBeamState``, ``step`` 0-based with
+    ``state.max_new`` steps at most (the last one finishes every candidate), ``eos`` -1 = none.  Updates ``state`` as
+    ``beam.beam_update`` does, writes ``pos``, ``key_valid[:, t]``, ``x = embed[token]``, cos / sin as ``decode_next``, and with
+    ``desc`` / ``layers`` (a ``DecodeStepPlan``'s) moves every layer's K / V of the generated columns ``L0 .. t - 1`` from each
+    beam's parent row to its own, in place.  ``state.unfinished`` (a device byte) says whether the search goes on."""
+    R, V = logits.shape
+    L.call("cmb_decode_beam", logits.data_ptr(), logits.stride(0), R, num_beams, V, eos, state.buf.data_ptr(), state.bytes, step,
+           state.max_new, n_tok.data_ptr(), pos.data_ptr(), key_valid.data_ptr(), key_valid.stride(0), t, embed.data_ptr(),
+           embed.stride(0), embed.shape[0], embed.shape[1], x.data_ptr(), x.stride(0), hd, rope_base, cos.data_ptr(),
+           sin.data_ptr(), None if desc is None else C.byref(desc), layers, L0, state.unfinished.data_ptr(), device=logits.device)
+
+
+def decode_beam_reorder(desc, layers, parent: torch.Tensor, num_beams: int, L0: int, t: int) -> None:
+    """The cache half of ``decode_beam`` on its own: in every layer's K / V cache of ``desc`` / ``layers`` and for the columns
+    ``L0 <= c < t``, row ``prompt * num_beams + i`` takes the values of row ``prompt * num_beams + parent[...]`` (int32 GPU
+    [rows]), in place; nothing else is written."""
+    L.require_gpu(parent)
+    if parent.dtype != torch.int32 or parent.shape != (desc.B,) or not parent.is_contiguous():
+        raise L.CambrianAmdError(f"decode_beam_reorder: parent is a contiguous int32 [{desc.B}] tensor")
+    L.call("cmb_decode_beam_reorder", C.byref(desc), layers, parent.data_ptr(), num_beams, L0, t, device=parent.device)
+
+
 def trim_after_all_done(ids: torch.Tensor, eos_token_id: int) -> torch.Tensor:
     """``ids`` [B, n] of a greedy loop that ran past the point where every row had produced ``eos_token_id`` (it polls
     ``done`` only every ``DECODE_STEP_POLL`` steps): the columns up to and including the first one at which every row is done

@@ -70,7 +70,8 @@ const char* cmb_version(void);
  * (cmb_decode_linear, cmb_decode_linear_supported, cmb_decode_linear_plan) and its 1-byte-weight form
  * (cmb_decode_linear_fp8, cmb_decode_linear_fp8_supported, cmb_decode_linear_fp8_plan), and then the one-call decode step
  * (cmb_decode_step, cmb_decode_step_ws, cmb_decode_next and the two descriptors), and then the sampled selection
- * (cmb_decode_sample) were ADDED under revision 13: no existing
+ * (cmb_decode_sample), and then beam search (cmb_decode_beam, cmb_decode_beam_state_bytes, cmb_decode_beam_reorder) were
+ * ADDED under revision 13: no existing
  * signature or layout changed, which is the rule for a bump, so a binding written against 13 still calls everything it
  * knows correctly.  Bindings must compare it
  * with the revision they
@@ -834,6 +835,50 @@ int cmb_decode_sample(const float* logits, int64_t logits_ld, int32_t B, int64_t
                       int64_t step, const int64_t* n_tok, int64_t* pos, uint8_t* key_valid, int64_t kv_ld, int64_t t,
                       const void* embed, int64_t embed_ld, int64_t embed_rows, int64_t H, void* x, int64_t x_ld, int32_t hd,
                       float rope_base, float* cos_t, float* sin_t, float* thr, int32_t* n_keep, void* stream);
+/* Beam search between two decode steps: cmb_decode_next's place in the loop when rows = prompts * num_beams rows of a decode step
+ * are the beams of `prompts` prompts (row r = prompt * num_beams + slot).  HF GenerationMixin._beam_search with do_sample = False,
+ * length_penalty = 1, early_stopping = False, equal scores ordered by the lowest index; restated in torch in
+ * cambrian_amd/model/language_model/beam.py, the per-prompt step is cmb_beam_step of csrc/decode_beam_core.h.  Per prompt, with
+ * K = 2 num_beams and step s (0-based; the last step is s + 1 == max_new):
+ *   score[beam, tok] = run_score[beam] + log_softmax(logits[beam])[tok]   fp32; the log-sum-exp from fixed-point masses
+ *   the K largest under (score descending, beam * V + tok ascending); a candidate hits when tok == eos (eos = -1: none) or on
+ *   the last step; the running beams are the top num_beams of score - 1e9 * hit; candidates ranked < num_beams that hit become
+ *   hypotheses of score / (s + 1) (1e9 lower once the early-stop flag is satisfied), merged behind the kept ones, the top
+ *   num_beams kept; unsat &= any(run_score[0] / (s + 1) > (fin_ok ? min(fin_score) : -1e9)).
+ * A row contributes its min(K, V) largest LOGITS (equal logits by the lowest index): the prompt's top K scores are among them
+ * unless two different logits at a row's cut round to the same score.  A NaN or +inf logit is outside the contract (CMB_OK,
+ * every index in range).
+ * state: ONE block of cmb_decode_beam_state_bytes(prompts, num_beams, max_new) bytes, 16-byte aligned, allocated and
+ * zero-initialised by the caller once per generate() call and passed to every step; step 0 reads none of it.  Sections in this
+ * order, each starting at a multiple of 16 bytes (csrc/decode_beam_core.h: cmb_beam_make_layout), R = rows, M = max_new:
+ *   float run_score[R]; float fin_score[R]; int32 fin_len[R]; int32 parent[R]; int32 tok[R]; float cand_lp[R][K];
+ *   int32 cand_tok[R][K]; uint8 fin_ok[R]; uint8 unsat[prompts]; uint8 all_hit[prompts]; int64 run_ids[2][R][M];
+ *   int64 fin_ids[R][M]
+ * run_score / run_ids: the running beams, best first; after step s the sequences are in half (s + 1) & 1, s + 1 tokens each.
+ * fin_*: the kept hypotheses, best first; fin_len counts the generated tokens, the eos included.  parent / tok: the slot each
+ * running beam continued in this step and the token it appended.
+ * Then, per row: pos = n_tok + step, key_valid[r * kv_ld + t] = 1, x[r] = embed[tok] (cmb_decode_next's tail), and with d / layers
+ * (cmb_decode_step's descriptors, both or neither NULL; d->B == rows) cmb_decode_beam_reorder on columns L0 .. t - 1; `unfinished`
+ * (one DEVICE byte) = any(unsat) && !all(all_hit): whether the search goes on; cos_t / sin_t = cmb_rope_table(pos).
+ * Three launches + the RoPE-table launch, integer LDS atomics only: the same bits on every run, a prompt's result independent of
+ * the other prompts.  Checked before any launch, in this order: CMB_ERR_BAD_ARG for state / unfinished NULL or only one of
+ * d / layers, then cmb_decode_next's rules in its order with rows for B and max_new for out_ld, then num_beams outside 2 .. 16,
+ * rows % num_beams, V < 2, V * num_beams >= 2^31; CMB_ERR_WORKSPACE for state_bytes below the need; CMB_ERR_BAD_ARG for a cache
+ * description out of rule (below); CMB_ERR_ALIGNMENT as cmb_decode_next, state not 16-byte aligned, then the caches'.
+ * cmb_decode_beam_reorder: in every layer's K and V cache [rows, nkv, Lmax, hd] (d: B = rows, nkv, hd, c_sb / c_sh / c_st; layers:
+ * kcache / vcache; nothing else is read) and for every generated column L0 <= c < t, row prompt * num_beams + i takes the values
+ * of row prompt * num_beams + parent[that row], in place; parent: int32 [rows] in DEVICE memory, a value outside
+ * 0 .. num_beams - 1 leaves its row as it is.  No other byte is written.  CMB_ERR_BAD_ARG: a NULL pointer, B outside 1 .. 16 or no
+ * multiple of num_beams, layers < 1, nkv < 1, hd < 8 or hd % 8, a negative stride, c_st < hd, L0 outside 0 .. t;
+ * CMB_ERR_ALIGNMENT: a cache stride that is no multiple of 8 elements, a cache pointer not 16-byte aligned. */
+int64_t cmb_decode_beam_state_bytes(int32_t prompts, int32_t num_beams, int64_t max_new);
+int cmb_decode_beam(const float* logits, int64_t logits_ld, int32_t rows, int32_t num_beams, int64_t V, int64_t eos, void* state,
+                    int64_t state_bytes, int64_t step, int64_t max_new, const int64_t* n_tok, int64_t* pos, uint8_t* key_valid,
+                    int64_t kv_ld, int64_t t, const void* embed, int64_t embed_ld, int64_t embed_rows, int64_t H, void* x,
+                    int64_t x_ld, int32_t hd, float rope_base, float* cos_t, float* sin_t, const cmb_decode_step_desc* d,
+                    const cmb_decode_layer* layers, int64_t L0, uint8_t* unfinished, void* stream);
+int cmb_decode_beam_reorder(const cmb_decode_step_desc* d, const cmb_decode_layer* layers, const int32_t* parent,
+                            int32_t num_beams, int64_t L0, int64_t t, void* stream);
 /* Backward of h = silu(g) * u (Llama MLP gate; forward is cmb_act_mul with CMB_ACT_SILU):
  * dg = dh * u * silu'(g), du = dh * silu(g); all [rows, D] with row strides. */
 int cmb_swiglu_bwd(int dtype, const void* dh, int64_t lddh, const void* g, int64_t ldg, const void* u, int64_t ldu,
