@@ -1,7 +1,7 @@
 // decode_step.hip — one token's pass through the whole decoder issued from ONE host call (cmb_decode_step): the launches of
 // the five-launch decode layer (cambrian_llama.py decode_layer_fused: norm + QKV linear, cmb_decode_attn, o_proj + skip,
 // norm + gate / up + SwiGLU, down_proj + skip) for every layer, then final norm + lm_head into fp32 logits.  There is no
-// kernel in this file: it calls cmb_decode_linear / cmb_decode_linear_fp8 / cmb_decode_attn with the arguments the Python
+// kernel in this file: it calls cmb_decode_linear / _fp8 / _fp4 / cmb_decode_attn with the arguments the Python
 // path passes, on one stream, so logits and caches carry the same bits; what it removes is the host work between launches
 // (per launch: the binding's predicates, two or three ctypes queries and a tensor allocation, for 32 layers).
 // Ordering comes from the stream alone.  Buffers: decode_step_layout.h.
@@ -20,6 +20,9 @@ inline int64_t ds_attn_floats(int64_t B, int32_t nh, int32_t nkv, int32_t hd, in
 inline bool ds_geometry_ok(int32_t B, int32_t H, int32_t I, int32_t nh, int32_t nkv, int32_t hd, int fp8) {
   if (B < 1 || B > DSL_MAX_B || H < 1 || I < 1 || nh < 1 || nkv < 1 || hd < 1) return false;
   const int64_t nq = (int64_t)nh * hd, nqkv = ((int64_t)nh + 2 * (int64_t)nkv) * hd;
+  if (fp8 == 2)
+    return cmb_decode_linear_fp4_supported(B, nqkv, H, 0) && cmb_decode_linear_fp4_supported(B, H, nq, 0) &&
+           cmb_decode_linear_fp4_supported(B, 2 * (int64_t)I, H, 1) && cmb_decode_linear_fp4_supported(B, H, I, 0);
   if (fp8)
     return cmb_decode_linear_fp8_supported(B, nqkv, H, 0) && cmb_decode_linear_fp8_supported(B, H, nq, 0) &&
            cmb_decode_linear_fp8_supported(B, 2 * (int64_t)I, H, 1) && cmb_decode_linear_fp8_supported(B, H, I, 0);
@@ -30,22 +33,26 @@ inline bool ds_geometry_ok(int32_t B, int32_t H, int32_t I, int32_t nh, int32_t 
 struct DsLinear {
   const void* w;
   int64_t ld;
-  const float* scale;
+  const void* scale;       // e4m3: fp32 row factors; MXFP4: e8m0 bytes, rows K / 32 apart
 };
 
 inline int ds_linear(int fp8, const void* x, int64_t x_ld, int32_t M, const void* norm_w, float eps, const DsLinear& w,
                      int64_t N, int64_t K, int32_t act, const void* res, int64_t r_ld, void* out, int64_t o_ld,
                      int32_t out_f32, void* stream) {
+  if (fp8 == 2)
+    return cmb_decode_linear_fp4(x, x_ld, M, norm_w, eps, w.w, w.ld, w.scale, K / 32, N, K, act, res, r_ld, out, o_ld, out_f32,
+                                 stream);
   if (fp8)
     return cmb_decode_linear_fp8(x, x_ld, M, norm_w, eps, w.w, w.ld, w.scale, N, K, act, res, r_ld, out, o_ld, out_f32, stream);
   return cmb_decode_linear(x, x_ld, M, norm_w, eps, w.w, w.ld, N, K, act, res, r_ld, out, o_ld, out_f32, stream);
 }
 
-// a weight's pointer rules: [N, K] with row stride ld (elements, or bytes of e4m3); 0 = fine, else the status
+// a weight's pointer rules: [N, K] with row stride ld (elements, bytes of e4m3, or bytes of two e2m1 each); 0 = fine, else
+// the status
 inline int ds_weight_status(int fp8, const DsLinear& w, int64_t K) {
   if (!w.w || (fp8 && !w.scale)) return CMB_ERR_BAD_ARG;
-  if (w.ld < K || w.ld % (fp8 ? 16 : 8)) return CMB_ERR_BAD_ARG;
-  if (!cmb_aligned16(w.w) || (fp8 && !aligned4(w.scale))) return CMB_ERR_ALIGNMENT;
+  if (w.ld < (fp8 == 2 ? K / 2 : K) || w.ld % (fp8 ? 16 : 8)) return CMB_ERR_BAD_ARG;
+  if (!cmb_aligned16(w.w) || (fp8 == 1 && !aligned4(w.scale))) return CMB_ERR_ALIGNMENT;
   return CMB_OK;
 }
 
@@ -64,10 +71,12 @@ extern "C" int cmb_decode_step(const cmb_decode_step_desc* d, const cmb_decode_l
   // ---- every rule before any launch ----
   if (!d || !layers || !x || !cos_t || !sin_t || !key_valid || !ws || !logits) return CMB_ERR_BAD_ARG;
   if (d->layers < 1 || d->B < 1 || d->B > DSL_MAX_B) return CMB_ERR_BAD_ARG;
-  const int fp8 = d->fp8 != 0;
+  if (d->fp8 < 0 || d->fp8 > 2) return CMB_ERR_BAD_ARG;
+  const int fp8 = d->fp8;          // 0: bf16, 1: e4m3 with row factors, 2: MXFP4 with e8m0 block scales
   const int32_t B = d->B, H = d->H, I = d->I, nh = d->nh, nkv = d->nkv, hd = d->hd;
   if (!ds_geometry_ok(B, H, I, nh, nkv, hd, fp8)) return CMB_ERR_BAD_ARG;
-  if (d->V < 1 || !(fp8 ? cmb_decode_linear_fp8_supported(B, d->V, H, 0) : cmb_decode_linear_supported(B, d->V, H, 0)))
+  if (d->V < 1 || !(fp8 == 2 ? cmb_decode_linear_fp4_supported(B, d->V, H, 0)
+                             : fp8 ? cmb_decode_linear_fp8_supported(B, d->V, H, 0) : cmb_decode_linear_supported(B, d->V, H, 0)))
     return CMB_ERR_BAD_ARG;
   if (!(d->eps >= 0.f) || t < 0 || kv_ld < t + 1 || nkv > 65535) return CMB_ERR_BAD_ARG;
   if (x_ld < H || x_ld % 8 || logits_ld < d->V || logits_ld % 8) return CMB_ERR_BAD_ARG;

@@ -256,15 +256,49 @@ def decode_fp8_copies(holder: nn.Module, B: int, entries):
     return [c[1] for c in cached]
 
 
-def decode_layer_fused(layer, x, cos, sin, kcache, vcache, t, key_mask, w_qkv, w_o, w_gate_up, w_down, fp8=None):
+def decode_fp4_copies(holder: nn.Module, B: int, entries):
+    """``decode_fp8_copies`` for the MXFP4 mode: the (e2m1 nibbles, e8m0 block scales) pair per linear that
+    ``ops.decode_linear_fp4`` streams, or None when the kernel does not take ONE of the weights (K % 32 != 0) — the step then
+    runs on the bf16 weights exactly as without the mode and nothing is quantised or kept.  The rules are that function's:
+    every weight that needs a new copy is put to ``ops.decode_linear_fp4_weight_supported`` before any is quantised, a refusal
+    is remembered on ``holder`` against the same tags, copies are cached on the owning module under ``key + "_fp4"``-style keys
+    of their own (the e4m3 copies live under other keys and are not touched) with _frozen_transposed's tag, and rebuilt when the
+    weight moves or changes."""
+    tags = tuple(_decode_fp8_tag(w) for _, _, w, _ in entries)
+    if holder.__dict__.get("_decode_fp4_refused") == tags:
+        return None
+    cached = [owner.__dict__.get(key) for owner, key, _, _ in entries]
+    miss = [i for i, (c, tag) in enumerate(zip(cached, tags)) if c is None or c[0] != tag]
+    if miss:
+        if not all(ops.decode_linear_fp4_weight_supported(B, entries[i][2], entries[i][3]) for i in miss):
+            holder.__dict__["_decode_fp4_refused"] = tags
+            for owner, key, _, _ in entries:
+                owner.__dict__.pop(key, None)
+            return None
+        holder.__dict__.pop("_decode_fp4_refused", None)
+        for i in miss:
+            owner, key, w, _ = entries[i]
+            cached[i] = owner.__dict__[key] = (tags[i], ops.decode_fp4_weight(w), w)
+    return [c[1] for c in cached]
+
+
+def decode_layer_fused(layer, x, cos, sin, kcache, vcache, t, key_mask, w_qkv, w_o, w_gate_up, w_down, fp8=None, fp4=None):
     """The five launches of a decode step: norm + QKV projection, attention on the cache, o_proj + skip connection,
     norm + gate / up projection + SwiGLU, down_proj + skip connection.  ``fp8``: the four (bytes, factors) pairs of
-    ``decode_fp8_copies`` — the linears then stream those instead of the bf16 weights."""
+    ``decode_fp8_copies`` — the linears then stream those instead of the bf16 weights.  ``fp4``: the four (nibbles, scales)
+    pairs of ``decode_fp4_copies``, likewise (at most one of the two)."""
     attn = layer.self_attn
     B = x.shape[0]
     nq, nk = attn.nh * attn.hd, attn.nkv * attn.hd
     n1, n2 = layer.input_layernorm, layer.post_attention_layernorm
     x2 = x.reshape(B, -1)
+    if fp4 is not None:
+        q_qkv, q_o, q_gate_up, q_down = fp4
+        row = ops.decode_linear_fp4(x2, *q_qkv, norm_weight=n1.weight, eps=n1.variance_epsilon)
+        o = ops.decode_attention(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t, key_mask)
+        x2 = ops.decode_linear_fp4(o, *q_o, residual=x2)
+        inner = ops.decode_linear_fp4(x2, *q_gate_up, norm_weight=n2.weight, eps=n2.variance_epsilon, act="swiglu")
+        return ops.decode_linear_fp4(inner, *q_down, residual=x2).reshape(B, 1, -1)
     if fp8 is not None:
         q_qkv, q_o, q_gate_up, q_down = fp8
         row = ops.decode_linear_fp8(x2, *q_qkv, norm_weight=n1.weight, eps=n1.variance_epsilon)
@@ -370,9 +404,15 @@ class LlamaDecoderLayer(nn.Module):
         x, h = ops.add_rmsnorm(x, a, n2.weight, n2.variance_epsilon)  # x + a and norm(x + a) in one pass
         return self.mlp(h, residual=x)
 
-    def decode_operands(self, x, fp8=False):
+    def _decode_fp4(self, B, w):
+        a, mlp = self.self_attn, self.mlp
+        return decode_fp4_copies(self, B, ((a, "_w_qkv_fp4", w[0], None), (a.o_proj, "_w_fp4", w[1], None),
+                                           (mlp, "_w_gate_up_fp4", w[2], "swiglu"), (mlp.down_proj, "_w_fp4", w[3], None)))
+
+    def decode_operands(self, x, fp8=False, fp4=False):
         """(the four weights, their e4m3 copies or None) when ``decode`` runs a step of x [B, 1, H] as five launches, else
-        None.  ``fp8``: ask for the e4m3 copies; None in their place when one weight is refused.  These are ``decode``'s own
+        None.  ``fp8``: ask for the e4m3 copies; None in their place when one weight is refused.  ``fp4``: the same with the
+        MXFP4 copies in that place.  These are ``decode``'s own
         conditions, restated for ``DecodeStepPlan`` (asked once per ``generate()`` call) so that the per-launch loop, the
         yardstick of the one-call step, stays line for line what it was."""
         a, mlp = self.self_attn, self.mlp
@@ -384,6 +424,8 @@ class LlamaDecoderLayer(nn.Module):
                  _fused_frozen_weight(mlp, "_w_gate_up", (mlp.gate_proj, mlp.up_proj)),
                  mlp.down_proj.weight if _frozen_plain(mlp.down_proj) else None)
             if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm)):
+                if fp4:
+                    return w, self._decode_fp4(x.shape[0], w)
                 q8 = None
                 if fp8:
                     q8 = decode_fp8_copies(self, x.shape[0], ((a, "_w_qkv_fp8", w[0], None), (a.o_proj, "_w_fp8", w[1], None),
@@ -392,9 +434,10 @@ class LlamaDecoderLayer(nn.Module):
                 return w, q8
         return None
 
-    def decode(self, x, cos, sin, kcache, vcache, t, key_mask, fp8=False):
+    def decode(self, x, cos, sin, kcache, vcache, t, key_mask, fp8=False, fp4=False):
         """``fp8``: stream e4m3 copies of the weights where the five-launch step is taken (``ops.decode_fp8_enabled``,
-        resolved once by ``generate``)."""
+        resolved once by ``generate``).  ``fp4``: MXFP4 copies instead (``ops.decode_fp4_enabled``); ``generate`` never sets
+        both (``ops.decode_weight_format``), and ``fp4`` wins here if a caller does."""
         a, mlp = self.self_attn, self.mlp
         if x.dtype == torch.bfloat16 and x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS and ops.decode_linear_enabled(x.shape[0]) \
                 and use_decode_kernel(x, a.nh, a.nkv, a.hd):
@@ -404,6 +447,9 @@ class LlamaDecoderLayer(nn.Module):
                  _fused_frozen_weight(mlp, "_w_gate_up", (mlp.gate_proj, mlp.up_proj)),
                  mlp.down_proj.weight if _frozen_plain(mlp.down_proj) else None)
             if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm)):
+                if fp4:
+                    return decode_layer_fused(self, x, cos, sin, kcache, vcache, t, key_mask, *w,
+                                              fp4=self._decode_fp4(x.shape[0], w))
                 q8 = None
                 if fp8:
                     q8 = decode_fp8_copies(self, x.shape[0], ((a, "_w_qkv_fp8", w[0], None), (a.o_proj, "_w_fp8", w[1], None),
@@ -698,8 +744,8 @@ def filter_logits_top_k_top_p(logits: torch.Tensor, top_k=None, top_p=None) -> t
     return logits
 
 
-def _decode_logits_operands(self, x: torch.Tensor, fp8: bool = False):
-    """(lm_head weight, its e4m3 copy or None) when ``_decode_logits`` takes its one-launch arm, else None: that function's
+def _decode_logits_operands(self, x: torch.Tensor, fp8: bool = False, fp4: bool = False):
+    """(lm_head weight, its e4m3 — with ``fp4`` its MXFP4 — copy or None) when ``_decode_logits`` takes its one-launch arm, else None: that function's
     condition restated for ``DecodeStepPlan``, so that the per-launch loop stays what it was."""
     model, head = self.model, self.lm_head
     a = model.layers[0].self_attn if len(model.layers) else None        # a decoder without layers keeps the stock line
@@ -707,22 +753,30 @@ def _decode_logits_operands(self, x: torch.Tensor, fp8: bool = False):
     if a is not None and use_decode_kernel(x, a.nh, a.nkv, a.hd) and x.dtype == torch.bfloat16 and B <= ops.DECODE_LINEAR_MAX_ROWS \
             and ops.decode_linear_enabled(B) and _frozen_plain(head) and not model.norm.weight.requires_grad \
             and model.norm.weight.dtype == torch.bfloat16 and ops.decode_linear_supported(x[:, 0], head.weight):
-        q8 = decode_fp8_copies(head, B, ((head, "_w_fp8", head.weight, None),)) if fp8 else None
+        if fp4:
+            q8 = decode_fp4_copies(head, B, ((head, "_w_fp4", head.weight, None),))
+        else:
+            q8 = decode_fp8_copies(head, B, ((head, "_w_fp8", head.weight, None),)) if fp8 else None
         return head.weight, (None if q8 is None else q8[0])
     return None
 
 
-def _decode_logits(self, x: torch.Tensor, fp8: bool = False) -> torch.Tensor:
+def _decode_logits(self, x: torch.Tensor, fp8: bool = False, fp4: bool = False) -> torch.Tensor:
     """fp32 logits of a decode step from the last layer's x [B, 1, H]: final norm + lm_head in one ``ops.decode_linear``
     launch under the conditions of the layers' five-launch step, else the norm kernel, the stock GEMM and a cast.
-    ``fp8``: that launch streams the lm_head's e4m3 copy (``ops.decode_linear_fp8``) where the kernel takes it."""
+    ``fp8``: that launch streams the lm_head's e4m3 copy (``ops.decode_linear_fp8``) where the kernel takes it; ``fp4``: its
+    MXFP4 copy (``ops.decode_linear_fp4``)."""
     model, head = self.model, self.lm_head
     a = model.layers[0].self_attn if len(model.layers) else None        # a decoder without layers keeps the stock line
     B = x.shape[0]
     if a is not None and use_decode_kernel(x, a.nh, a.nkv, a.hd) and x.dtype == torch.bfloat16 and B <= ops.DECODE_LINEAR_MAX_ROWS \
             and ops.decode_linear_enabled(B) and _frozen_plain(head) and not model.norm.weight.requires_grad \
             and model.norm.weight.dtype == torch.bfloat16 and ops.decode_linear_supported(x[:, 0], head.weight):
-        q8 = decode_fp8_copies(head, B, ((head, "_w_fp8", head.weight, None),)) if fp8 else None
+        q4 = decode_fp4_copies(head, B, ((head, "_w_fp4", head.weight, None),)) if fp4 else None
+        if q4 is not None:
+            return ops.decode_linear_fp4(x[:, 0], *q4[0], norm_weight=model.norm.weight, eps=model.norm.variance_epsilon,
+                                         out_dtype=torch.float32)
+        q8 = decode_fp8_copies(head, B, ((head, "_w_fp8", head.weight, None),)) if fp8 and not fp4 else None
         if q8 is not None:
             return ops.decode_linear_fp8(x[:, 0], *q8[0], norm_weight=model.norm.weight, eps=model.norm.variance_epsilon,
                                          out_dtype=torch.float32)
@@ -735,11 +789,11 @@ class DecodeStepPlan:
     """What the decode steps of ONE ``generate()`` call share when they are issued as one library call per token
     (``ops.decode_step``): the layer table and the step descriptor in host memory, the objects that own every pointer in
     them, the workspace and the logits buffer.  ``build`` returns None unless the whole model qualifies — every layer under
-    the five-launch conditions, the lm_head under ``_decode_logits``' condition, with ``fp8`` the e4m3 copies of every weight
-    — and the call then runs on the per-launch loop, unchanged."""
+    the five-launch conditions, the lm_head under ``_decode_logits``' condition, with ``fp8`` the e4m3 copies (with ``fp4`` the
+    MXFP4 copies, ``cmb_decode_step_desc.fp8`` = 2) of every weight — and the call then runs on the per-launch loop, unchanged."""
 
     @classmethod
-    def build(cls, lm, B: int, caches, t_max: int, fp8: bool):
+    def build(cls, lm, B: int, caches, t_max: int, fp8: bool, fp4: bool = False):
         model = lm.model
         if not len(model.layers) or len(caches) != len(model.layers) or not 1 <= B <= ops.DECODE_LINEAR_MAX_ROWS:
             return None
@@ -750,8 +804,9 @@ class DecodeStepPlan:
         a0 = model.layers[0].self_attn
         H, nh, nkv, hd = cfg.hidden_size, a0.nh, a0.nkv, a0.hd
         x = torch.empty(B, 1, H, dtype=torch.bfloat16, device=dev)       # what the predicates look at; never read
-        head = _decode_logits_operands(lm, x, fp8)
-        if head is None or (fp8 and head[1] is None):
+        quant = bool(fp8 or fp4)
+        head = _decode_logits_operands(lm, x, fp8, fp4)
+        if head is None or (quant and head[1] is None):
             return None
         eps = float(model.norm.variance_epsilon)
         kc0 = caches[0][0]
@@ -762,8 +817,8 @@ class DecodeStepPlan:
             if not hasattr(layer, "decode_operands") or (a.nh, a.nkv, a.hd) != (nh, nkv, hd) \
                     or float(n1.variance_epsilon) != eps or float(n2.variance_epsilon) != eps:
                 return None
-            found = layer.decode_operands(x, fp8)
-            if found is None or (fp8 and found[1] is None):
+            found = layer.decode_operands(x, fp8, fp4) if fp4 else layer.decode_operands(x, fp8)
+            if found is None or (quant and found[1] is None):
                 return None
             w, q8 = found
             if w[2].shape[0] % 2 or (inter is not None and w[2].shape[0] // 2 != inter) or w[0].shape != ((nh + 2 * nkv) * hd, H) \
@@ -774,7 +829,9 @@ class DecodeStepPlan:
                     or vc.shape != kc.shape or kc.stride() != kc0.stride() or vc.stride() != kc0.stride() or kc.stride(3) != 1:
                 return None
             row = _lib.DecodeLayer()
-            mats = q8 if fp8 else [(wi, None) for wi in w]
+            mats = q8 if quant else [(wi, None) for wi in w]
+            if fp4 and any(sc.stride(0) != sc.shape[1] for _, sc in mats):      # the step takes scale rows K / 32 apart
+                return None
             for name, (m, sc) in zip(("qkv", "o", "gate_up", "down"), mats):
                 setattr(row, "w_" + name, m.data_ptr())
                 setattr(row, "ld_" + name, m.stride(0))
@@ -786,9 +843,11 @@ class DecodeStepPlan:
         if t_max >= kc0.shape[2]:
             return None
         self = cls()
-        hw, hs = head[1] if fp8 else (head[0], None)
+        hw, hs = head[1] if quant else (head[0], None)
+        if fp4 and hs.stride(0) != hs.shape[1]:
+            return None
         V = head[0].shape[0]
-        self.desc = _lib.DecodeStepDesc(B=B, layers=len(rows), H=H, I=inter, nh=nh, nkv=nkv, hd=hd, fp8=int(bool(fp8)), V=V, eps=eps,
+        self.desc = _lib.DecodeStepDesc(B=B, layers=len(rows), H=H, I=inter, nh=nh, nkv=nkv, hd=hd, fp8=2 if fp4 else int(bool(fp8)), V=V, eps=eps,
                                      scale=1.0 / math.sqrt(hd), c_sb=kc0.stride(0), c_sh=kc0.stride(1), c_st=kc0.stride(2),
                                      final_norm=model.norm.weight.data_ptr(), head=hw.data_ptr(), ld_head=hw.stride(0),
                                      head_scale=_lib.ptr(hs))
@@ -877,10 +936,12 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
         out_ids = []
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         theta = float(getattr(self.config, "rope_theta", 10000.0))
-        fp8 = ops.decode_fp8_enabled(getattr(self.config, "decode_fp8_weights", False))   # e4m3 weight stream, opt-in
+        fmt = ops.decode_weight_format(self.config)            # e4m3 or MXFP4 weight stream, opt-in; both on raises
+        fp8, fp4 = fmt == "fp8", fmt == "fp4"
+        low = {"fp4": True} if fp4 else {}                      # (the fp8 mode's calls stay what they were)
         plan = None                                                                       # one library call per token, opt-in
         if max_new_tokens > 1 and ops.decode_step_enabled(getattr(self.config, "decode_step_fused", False)):
-            plan = DecodeStepPlan.build(self, B, caches, Lmax - 1, fp8)
+            plan = DecodeStepPlan.build(self, B, caches, Lmax - 1, fp8, **low)
         sampled = bool(do_sample and temperature > 0)
         if plan is not None and (not sampled or ops.decode_sample_enabled(getattr(self.config, "decode_sample_device", False))):
             emb = model.embed_tokens.weight
@@ -910,8 +971,8 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
                 logits = plan.step(x[:, 0], cos, sin, t, key_mask)
                 continue
             for layer, (kc, vc) in zip(model.layers, caches):
-                x = layer.decode(x, cos, sin, kc, vc, t, key_mask, fp8=fp8)      # [B, Lmax]: the step reads columns 0..t
-            logits = _decode_logits(self, x, fp8)
+                x = layer.decode(x, cos, sin, kc, vc, t, key_mask, fp8=fp8, **low)      # [B, Lmax]: the step reads columns 0..t
+            logits = _decode_logits(self, x, fp8, **low)
         return torch.stack(out_ids, 1)
 
 
@@ -1005,11 +1066,13 @@ def _beam_search(self, logits, kv_out, valid, L: int, max_new_tokens: int, eos_t
     n_tok = valid.long().sum(1).repeat_interleave(nb).contiguous()
     logits = logits.repeat_interleave(nb, dim=0)
     theta = float(getattr(self.config, "rope_theta", 10000.0))
-    fp8 = ops.decode_fp8_enabled(getattr(self.config, "decode_fp8_weights", False))
+    fmt = ops.decode_weight_format(self.config)
+    fp8, fp4 = fmt == "fp8", fmt == "fp4"
+    low = {"fp4": True} if fp4 else {}
     fill = beam_fill(pad_token_id, eos_token_id)
     plan = None
     if max_new_tokens > 1 and ops.decode_step_enabled(getattr(self.config, "decode_step_fused", False)):
-        plan = DecodeStepPlan.build(self, R, caches, Lmax - 1, fp8)
+        plan = DecodeStepPlan.build(self, R, caches, Lmax - 1, fp8, **low)
     if plan is not None and R <= ops.DECODE_BEAM_MAX and V >= 2 and V * nb < 2 ** 31:
         emb = model.embed_tokens.weight
         if emb.dtype == torch.bfloat16 and emb.stride(1) == 1 and emb.stride(0) % 8 == 0 and emb.data_ptr() % 16 == 0 \
@@ -1034,8 +1097,8 @@ def _beam_search(self, logits, kv_out, valid, L: int, max_new_tokens: int, eos_t
             logits = plan.step(x[:, 0], cos, sin, t, key_mask)
             continue
         for layer, (kc, vc) in zip(model.layers, caches):
-            x = layer.decode(x, cos, sin, kc, vc, t, key_mask, fp8=fp8)
-        logits = _decode_logits(self, x, fp8)
+            x = layer.decode(x, cos, sin, kc, vc, t, key_mask, fp8=fp8, **low)
+        logits = _decode_logits(self, x, fp8, **low)
     return beam_result(state, fill)
 
 

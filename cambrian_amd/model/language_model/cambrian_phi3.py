@@ -33,7 +33,7 @@ except Exception:  # pragma: no cover
 from ... import lib as L
 from ... import ops
 from .cambrian_llama import (CambrianLlamaForCausalLM, CambrianLlamaModel, HipRMSNorm, _down_proj, _frozen_plain, _lin,
-                             decode_fp8_copies, decode_layer_fused, decode_linear_weights, use_decode_kernel)
+                             decode_fp4_copies, decode_fp8_copies, decode_layer_fused, decode_linear_weights, use_decode_kernel)
 
 
 class CambrianConfig(Phi3Config):
@@ -128,7 +128,7 @@ class Phi3DecoderLayer(nn.Module):
         x, h = ops.add_rmsnorm(x, a, n2.weight, n2.variance_epsilon)              # :903-911 residual + norm, one pass
         return self.mlp(h, residual=x)
 
-    def decode(self, x, cos, sin, kcache, vcache, t, key_mask, fp8=False):
+    def decode(self, x, cos, sin, kcache, vcache, t, key_mask, fp8=False, fp4=False):
         a, mlp = self.self_attn, self.mlp
         if x.dtype == torch.bfloat16 and x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS and ops.decode_linear_enabled(x.shape[0]) \
                 and use_decode_kernel(x, a.nh, a.nkv, a.hd):
@@ -136,6 +136,10 @@ class Phi3DecoderLayer(nn.Module):
             mods = (a.qkv_proj, a.o_proj, mlp.gate_up_proj, mlp.down_proj)
             w = tuple(m.weight if _frozen_plain(m) else None for m in mods)
             if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm)):
+                if fp4:      # MXFP4 copies, cached on the Linear that owns the weight under a key of their own
+                    q4 = decode_fp4_copies(self, x.shape[0], tuple(
+                        (m, "_w_fp4", wi, "swiglu" if m is mlp.gate_up_proj else None) for m, wi in zip(mods, w)))
+                    return decode_layer_fused(self, x, cos, sin, kcache, vcache, t, key_mask, *w, fp4=q4)
                 q8 = None
                 if fp8:      # e4m3 copies, cached on the Linear that owns the weight
                     q8 = decode_fp8_copies(self, x.shape[0], tuple(
@@ -144,7 +148,7 @@ class Phi3DecoderLayer(nn.Module):
         x = x + self.self_attn.decode(self.input_layernorm(x), cos, sin, kcache, vcache, t, key_mask)
         return x + self.mlp(self.post_attention_layernorm(x))
 
-    def decode_operands(self, x, fp8=False):
+    def decode_operands(self, x, fp8=False, fp4=False):
         """(the four weights, their e4m3 copies or None) when ``decode`` runs a step of x as five launches, else None:
         ``decode``'s conditions restated for ``DecodeStepPlan`` (see LlamaDecoderLayer.decode_operands)."""
         a, mlp = self.self_attn, self.mlp
@@ -153,6 +157,9 @@ class Phi3DecoderLayer(nn.Module):
             mods = (a.qkv_proj, a.o_proj, mlp.gate_up_proj, mlp.down_proj)
             w = tuple(m.weight if _frozen_plain(m) else None for m in mods)
             if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm)):
+                if fp4:
+                    return w, decode_fp4_copies(self, x.shape[0], tuple(
+                        (m, "_w_fp4", wi, "swiglu" if m is mlp.gate_up_proj else None) for m, wi in zip(mods, w)))
                 q8 = None
                 if fp8:
                     q8 = decode_fp8_copies(self, x.shape[0], tuple(

@@ -2397,6 +2397,136 @@ def decode_linear_fp8(x: torch.Tensor, q: torch.Tensor, inv_scale: torch.Tensor,
 
 
 # ------------------------------------------------------------------------------------------------
+# the same linears on MXFP4 weights (decode_linear_fp4.hip, mxfp4.hip): OCP e2m1 nibbles with one e8m0 power-of-two scale per
+# 32 elements, 4.25 bits per weight — a quarter of the bf16 stream, and 0.53 byte per decoder parameter beside the bf16 weights
+# (the e4m3 mode adds 1).  Opt-in (``config.decode_fp4_weights`` / CAMBRIAN_AMD_DECODE_FP4) and COARSE: about 11 % relative L2
+# error per weight on Gaussian weights (e4m3 rows: 2.5–2.7 %); task quality on real checkpoints is unmeasured.  Block scales
+# need no row in registers, so K has no upper reach (Yi-34B's down_proj, K = 20480, is taken).  Not bitsandbytes' NF4:
+# ``load_4bit`` stays refused.
+# ------------------------------------------------------------------------------------------------
+DECODE_FP4_BLOCK = 32
+
+
+def decode_fp4_enabled(config_flag: bool = False) -> bool:
+    """Whether decode steps stream MXFP4 weights: ``CAMBRIAN_AMD_DECODE_FP4`` = ``1`` / ``0`` in the environment overrides,
+    unset it is ``config_flag`` (the model's ``config.decode_fp4_weights``, absent = off)."""
+    v = os.environ.get("CAMBRIAN_AMD_DECODE_FP4")
+    if v is None or v == "":
+        return bool(config_flag)
+    return v != "0"
+
+
+def decode_weight_format(config) -> Optional[str]:
+    """The reduced weight format of the decode steps as the two switches resolve it: None (bf16), ``"fp8"`` (e4m3 rows,
+    ``config.decode_fp8_weights`` / CAMBRIAN_AMD_DECODE_FP8) or ``"fp4"`` (MXFP4, ``config.decode_fp4_weights`` /
+    CAMBRIAN_AMD_DECODE_FP4).  Both on is an error, not a silent pick."""
+    fp8 = decode_fp8_enabled(getattr(config, "decode_fp8_weights", False))
+    fp4 = decode_fp4_enabled(getattr(config, "decode_fp4_weights", False))
+    if fp8 and fp4:
+        raise L.CambrianAmdError("decode steps can stream one reduced weight format: both the e4m3 mode (config.decode_fp8_weights / "
+                                 "CAMBRIAN_AMD_DECODE_FP8) and the MXFP4 mode (config.decode_fp4_weights / CAMBRIAN_AMD_DECODE_FP4) "
+                                 "are switched on; switch one off")
+    return "fp8" if fp8 else ("fp4" if fp4 else None)
+
+
+def decode_linear_fp4_plan(M: int, N: int, K: int, act: Optional[str] = None, cus: int = 0) -> Tuple[int, int]:
+    """(weight rows per workgroup, workgroups) of a ``decode_linear_fp4`` call: a pure function of (M, N, K, act, CU
+    count); ``cus`` = 0 takes the current device's count."""
+    rows, wgs = C.c_int32(0), C.c_int64(0)
+    L.check(L.load().cmb_decode_linear_fp4_plan(M, N, K, _decode_linear_act(act), cus, C.byref(rows), C.byref(wgs)),
+            "cmb_decode_linear_fp4_plan")
+    return rows.value, wgs.value
+
+
+def decode_linear_fp4_weight_supported(M: int, w: torch.Tensor, act: Optional[str] = None) -> bool:
+    """Whether the bf16 weight ``w`` [N, K] can be served by ``decode_fp4_weight`` + ``decode_linear_fp4`` for ``M`` rows of
+    x: a GPU bf16 matrix with contiguous, 16-byte aligned rows, K % 32 == 0 (any such K), and the kernel's shape rule."""
+    return (w.dim() == 2 and _decode_linear_rows_ok(w, w.shape[1])
+            and bool(L.load().cmb_decode_linear_fp4_supported(M, w.shape[0], w.shape[1], _decode_linear_act(act))))
+
+
+def _decode_fp4_q_ok(q: torch.Tensor, scales: torch.Tensor) -> bool:
+    return (q.is_cuda and q.dtype == torch.uint8 and q.dim() == 2 and q.shape[1] >= 16 and q.shape[1] % 16 == 0
+            and q.stride(1) == 1 and q.stride(0) >= q.shape[1] and q.stride(0) % 16 == 0 and q.data_ptr() % 16 == 0
+            and scales.is_cuda and scales.device == q.device and scales.dtype == torch.uint8 and scales.dim() == 2
+            and scales.shape == (q.shape[0], q.shape[1] // 16) and scales.stride(1) == 1 and scales.stride(0) >= scales.shape[1])
+
+
+def decode_linear_fp4_supported(x: torch.Tensor, q: torch.Tensor, scales: torch.Tensor, act: Optional[str] = None) -> bool:
+    """Whether ``decode_linear_fp4(x, q, scales, act=act)`` takes these operands: bf16 GPU x [M <= 16, K], uint8 GPU q
+    [N, K / 2] with contiguous 16-byte aligned rows (row stride a multiple of 16), uint8 scales [N, K / 32] with contiguous
+    rows, K % 32 == 0, N even for SwiGLU."""
+    return (x.dim() == 2 and q.dim() == 2 and x.shape[0] >= 1 and _decode_linear_rows_ok(x, 2 * q.shape[1])
+            and _decode_fp4_q_ok(q, scales)
+            and bool(L.load().cmb_decode_linear_fp4_supported(x.shape[0], q.shape[0], 2 * q.shape[1], _decode_linear_act(act))))
+
+
+def k_quantize_mxfp4_rows(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """x [rows, K] bf16 | fp32 GPU tensor with contiguous rows, finite, K % 32 == 0 -> (uint8 nibbles [rows, K / 2], uint8 e8m0
+    scales [rows, K / 32]): MXFP4 under the OCP scale rule (cmb_quantize_mxfp4_rows)."""
+    L.require_gpu(x)
+    if x.dim() != 2 or x.stride(1) != 1 or x.dtype not in (torch.bfloat16, torch.float32) or x.shape[1] < DECODE_FP4_BLOCK \
+            or x.shape[1] % DECODE_FP4_BLOCK:
+        raise L.CambrianAmdError("MXFP4 quantisation needs a 2-D K-contiguous bf16 / fp32 tensor with K a multiple of 32")
+    rows, K = x.shape
+    q = torch.empty(rows, K // 2, dtype=torch.uint8, device=x.device)
+    scales = torch.empty(rows, K // DECODE_FP4_BLOCK, dtype=torch.uint8, device=x.device)
+    L.call("cmb_quantize_mxfp4_rows", L.dtype_code(x.dtype), x.data_ptr(), x.stride(0), rows, K, q.data_ptr(), K // 2,
+           scales.data_ptr(), K // DECODE_FP4_BLOCK, device=x.device, what=f"cmb_quantize_mxfp4_rows({rows}x{K})")
+    return q, scales
+
+
+def decode_fp4_weight(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A frozen bf16 GPU weight [N, K] -> (e2m1 nibbles uint8 [N, K / 2], e8m0 scales uint8 [N, K / 32]) for
+    ``decode_linear_fp4`` (``k_quantize_mxfp4_rows``).  K % 32 == 0; no upper limit on K."""
+    L.require_gpu(w)
+    if w.requires_grad:
+        raise L.CambrianAmdError("decode_fp4_weight: the weight is trainable; quantised copies are for frozen weights")
+    if w.dim() != 2 or w.dtype != torch.bfloat16 or w.stride(1) != 1 or w.shape[0] < 1 or w.shape[1] < DECODE_FP4_BLOCK \
+            or w.shape[1] % DECODE_FP4_BLOCK or w.stride(0) % 8 or w.data_ptr() % 16:
+        raise L.CambrianAmdError(f"decode_fp4_weight: needs a bf16 [N, K] matrix with contiguous 16-byte aligned rows and "
+                                 f"K % 32 == 0, K >= 32; got {tuple(w.shape)} {w.dtype} strides {w.stride()}")
+    return k_quantize_mxfp4_rows(w.detach())
+
+
+def decode_linear_fp4(x: torch.Tensor, q: torch.Tensor, scales: torch.Tensor, *, norm_weight: Optional[torch.Tensor] = None,
+                      eps: float = 0.0, act: Optional[str] = None, residual: Optional[torch.Tensor] = None,
+                      out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``decode_linear`` on MXFP4 weights: ``epilogue(prologue(x) @ (e2m1(q) * 2^(scales - 127)).T)`` for bf16 x [M <= 16, K],
+    q the packed nibbles [N, K / 2] and scales the e8m0 bytes [N, K / 32] of ``decode_fp4_weight`` (codes 1 .. 254, never 0 or
+    255); one launch that reads 4.25 bits per weight.  ``norm_weight`` / ``eps`` / ``act`` / ``residual`` / ``out_dtype`` /
+    ``out`` mean what they mean in ``decode_linear``.  Inference only: there is no backward and no CPU path."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, norm_weight, residual)):
+        raise L.CambrianAmdError("decode_linear_fp4 has no backward: call it under torch.no_grad()")
+    L.require_gpu(x, q, scales, norm_weight, residual, out)
+    code = _decode_linear_act(act)
+    if not decode_linear_fp4_supported(x, q, scales, act):
+        raise L.CambrianAmdError(f"decode_linear_fp4: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, "
+                                 f"q {tuple(q.shape)} {q.dtype} strides {q.stride()}, scales {tuple(scales.shape)} "
+                                 f"{scales.dtype} strides {scales.stride()}, act {act!r}")
+    (M, K), N = x.shape, q.shape[0]
+    cols = N // 2 if code else N
+    if norm_weight is not None and (norm_weight.dtype != torch.bfloat16 or norm_weight.shape != (K,)
+                                    or not norm_weight.is_contiguous()):
+        raise L.CambrianAmdError("decode_linear_fp4: norm_weight is a contiguous bf16 [K] vector")
+    if residual is not None and (code or residual.dtype != torch.bfloat16 or residual.shape != (M, cols)
+                                 or residual.stride(1) != 1):
+        raise L.CambrianAmdError("decode_linear_fp4: residual is bf16 [M, N] with contiguous rows, and not combined with act")
+    out_dtype = out_dtype or (torch.bfloat16 if out is None else out.dtype)
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise L.CambrianAmdError(f"decode_linear_fp4: out_dtype {out_dtype} (bf16 or fp32)")
+    if out is None:
+        ld = (cols + 7) // 8 * 8
+        out = torch.empty((M, ld), dtype=out_dtype, device=x.device)[:, :cols]
+    elif not out.is_cuda or out.dtype != out_dtype or out.shape != (M, cols) or out.stride(1) != 1:
+        raise L.CambrianAmdError(f"decode_linear_fp4: out must be a {out_dtype} GPU tensor [{M}, {cols}] with contiguous rows")
+    L.call("cmb_decode_linear_fp4", x.data_ptr(), x.stride(0), M, L.ptr(norm_weight), float(eps), q.data_ptr(), q.stride(0),
+           scales.data_ptr(), scales.stride(0), N, K, code, L.ptr(residual), 0 if residual is None else residual.stride(0),
+           out.data_ptr(), out.stride(0), int(out_dtype == torch.float32), device=x.device)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # the whole decode step as one library call (decode_step.hip) and the greedy selection between two steps as another
 # (decode_next.hip; decode_sample.hip for sampled decoding, behind a switch of its own: ``config.decode_sample_device`` /
 # CAMBRIAN_AMD_DECODE_SAMPLE).  Opt-in (``config.decode_step_fused`` / CAMBRIAN_AMD_DECODE_STEP), off by default: the kernels and

@@ -70,7 +70,9 @@ const char* cmb_version(void);
  * (cmb_decode_linear, cmb_decode_linear_supported, cmb_decode_linear_plan) and its 1-byte-weight form
  * (cmb_decode_linear_fp8, cmb_decode_linear_fp8_supported, cmb_decode_linear_fp8_plan), and then the one-call decode step
  * (cmb_decode_step, cmb_decode_step_ws, cmb_decode_next and the two descriptors), and then the sampled selection
- * (cmb_decode_sample), and then beam search (cmb_decode_beam, cmb_decode_beam_state_bytes, cmb_decode_beam_reorder) were
+ * (cmb_decode_sample), and then beam search (cmb_decode_beam, cmb_decode_beam_state_bytes, cmb_decode_beam_reorder), and then the MXFP4
+ * decode-step linear (cmb_quantize_mxfp4_rows, cmb_decode_linear_fp4, cmb_decode_linear_fp4_supported,
+ * cmb_decode_linear_fp4_plan, and the value 2 of cmb_decode_step_desc.fp8) were
  * ADDED under revision 13: no existing
  * signature or layout changed, which is the rule for a bump, so a binding written against 13 still calls everything it
  * knows correctly.  Bindings must compare it
@@ -760,6 +762,36 @@ int cmb_decode_linear_fp8(const void* x, int64_t x_ld, int32_t M, const void* no
                           int64_t r_ld, void* out, int64_t o_ld, int32_t out_f32, void* stream);
 int cmb_decode_linear_fp8_supported(int32_t M, int64_t N, int64_t K, int32_t act);
 int cmb_decode_linear_fp8_plan(int32_t M, int64_t N, int64_t K, int32_t act, int32_t cus, int32_t* rows_out, int64_t* wgs_out);
+/* MXFP4 quantisation of matrix rows (OCP microscaling: e2m1 values with one shared e8m0 scale per 32 elements, 4.25 bits per
+ * element) for cmb_decode_linear_fp4.  x [rows, K] (dtype CMB_BF16 | CMB_F32, row stride ldx elements), FINITE values only.
+ *   q      uint8 [rows, K / 2], row stride ldq bytes: byte j of a row holds element 2 j in its low nibble and element 2 j + 1
+ *          in its high nibble; a nibble is an e2m1 code, bit 3 the sign, magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6
+ *   scales uint8 [rows, K / 32], row stride lds bytes: code c means 2^(c - 127)
+ * Per block of 32: amax = max |x|; e = clamp(floor(log2 amax) - 2, -126, 127); code = e + 127 (a zero block: code 127 and
+ * zero nibbles); every x * 2^-e is rounded to the e2m1 grid, to nearest, ties to the even code, saturating at +-6 — a block
+ * whose amax lies in (6, 8) * 2^e clamps (the OCP rule).  -0 and values that round to zero are written as +0.  Codes 0 and
+ * 255 are never written.  A streaming kernel, one block of 32 per thread: any K % 32 == 0, no upper limit.  Deterministic.
+ * CMB_ERR_SHAPE: K % 32 != 0, ldx < K, ldq < K / 2, ldq % 16 != 0, lds < K / 32; CMB_ERR_ALIGNMENT: x or q not 16-byte
+ * aligned, or x rows that are not.  rows == 0 is CMB_OK. */
+int cmb_quantize_mxfp4_rows(int dtype, const void* x, int64_t ldx, int64_t rows, int64_t K, void* q, int64_t ldq, void* scales,
+                            int64_t lds, void* stream);
+/* cmb_decode_linear on MXFP4 weights, a quarter of the bf16 weight stream (4.25 bits per weight):
+ *   out = epilogue(rstd? * sum_k prologue(x)[m, k] * e2m1(Wq[n, k]) * 2^(Ws[n, k / 32] - 127))
+ * Wq / Ws: the nibbles [N, K / 2] (row stride w_ld BYTES) and e8m0 block scales [N, K / 32] (row stride s_ld bytes) in
+ * cmb_quantize_mxfp4_rows' format.  Scale codes 1 .. 254 are accepted; 0 and 255 (NaN in e8m0) must not appear anywhere in
+ * Ws[N, K / 32]: fragments past a ragged K re-read the block at k = 0 and multiply it by zero.  x stays bf16: an e2m1 value
+ * times a power of two is exactly a bf16 wherever it lies in bf16's range (codes 1 .. 252 with every nibble; 6 * 2^126 and
+ * above is infinity, as in a bf16 copy of the dequantised weight), so the nibbles are converted in registers and the
+ * products are those of cmb_decode_linear on the dequantised weights; the fp32 sum is the only rounding.  There is no
+ * per-row factor.  norm_w, act, residual, out_f32, the determinism and the statuses are cmb_decode_linear's; the shape rule
+ * differs in K % 32 == 0, K >= 32, w_ld >= K / 2 and w_ld % 16 == 0 (a lane loads 16 bytes = 32 k = one block), s_ld >= K / 32,
+ * Wq 16-byte aligned, Ws non-NULL (bytes: no alignment rule).
+ * cmb_decode_linear_fp4_plan: cmb_decode_linear_fp8_plan's rule (the largest slab that leaves one workgroup per CU). */
+int cmb_decode_linear_fp4(const void* x, int64_t x_ld, int32_t M, const void* norm_w, float norm_eps, const void* Wq,
+                          int64_t w_ld, const void* Ws, int64_t s_ld, int64_t N, int64_t K, int32_t act, const void* residual,
+                          int64_t r_ld, void* out, int64_t o_ld, int32_t out_f32, void* stream);
+int cmb_decode_linear_fp4_supported(int32_t M, int64_t N, int64_t K, int32_t act);
+int cmb_decode_linear_fp4_plan(int32_t M, int64_t N, int64_t K, int32_t act, int32_t cus, int32_t* rows_out, int64_t* wgs_out);
 /* One token's pass through the whole decoder in ONE call (generate(); the decode-step loop over HF LlamaDecoderLayer /
  * Phi3DecoderLayer and the lm_head): per layer norm + QKV linear, cmb_decode_attn (with its combine launch when the plan
  * splits), o_proj + skip, norm + gate / up + SwiGLU, down_proj + skip; then final norm + lm_head into fp32 logits.  It calls
@@ -771,7 +803,11 @@ int cmb_decode_linear_fp8_plan(int32_t M, int64_t N, int64_t K, int32_t act, int
  * layer's K / V caches [B, nkv, Lmax, hd].  w_qkv is [(nh + 2 nkv) hd, H] (q | k | v heads), w_o [H, nh hd], w_gate_up
  * [2 I, H] ([gate; up], cmb_decode_linear's act = 1), w_down [H, I].
  * cmb_decode_step_desc: geometry, eps (every norm), the attention scale, the caches' element strides (shared by all layers),
- * the final norm and the lm_head [V, H]; fp8 != 0: every weight of every layer and the head is e4m3 with row factors.
+ * the final norm and the lm_head [V, H]; fp8 == 1: every weight of every layer and the head is e4m3 with row factors;
+ * fp8 == 2: every weight is MXFP4 (cmb_quantize_mxfp4_rows' nibbles, row strides in bytes) and w_*_scale / head_scale point to
+ * its e8m0 scale BYTES with row stride K / 32 (the fields keep their const float* type for existing callers; no alignment
+ * rule applies to them in this mode) and cmb_decode_linear_fp4 runs the linears; 0: bf16.  Any other value is
+ * CMB_ERR_BAD_ARG.
  * Per call: x bf16 [B, H] (row stride x_ld, outside ws), cos_t / sin_t fp32 [B, hd/2], cache slot t, key_valid bytes
  * [B, >= t+1] (row stride kv_ld), ws fp32 [>= cmb_decode_step_ws(...) at this t] (csrc/decode_step_layout.h), logits fp32
  * [B, V] with row stride logits_ld (a multiple of 8).  bf16 only.

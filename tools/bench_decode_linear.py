@@ -7,6 +7,8 @@ adds), same box, same run.  The off arm is the yardstick; the table this writes 
     python tools/bench_decode_linear.py --dump-resources FILE       # no GPU: hipcc's register / LDS / scratch report
     python tools/bench_decode_linear.py --fp8 [--out profiles/decode_fp8.md] [--resources FILE]
     python tools/bench_decode_linear.py --fp8 --dump-resources FILE
+    python tools/bench_decode_linear.py --fp4 [--out profiles/decode_fp4.md] [--resources FILE] [--step-log FILE]
+    python tools/bench_decode_linear.py --fp4 --dump-resources FILE
 
 ``--fp8`` measures the e4m3 weight stream (``cmb_decode_linear_fp8``, ``layer.decode(..., fp8=True)``) against the bf16
 ``decode_linear`` arm — today's default path, the yardstick — by the same method; the ring is at least 768 MB of the 1-byte
@@ -14,6 +16,12 @@ weights, MB and GB/s count one byte per weight, and a row is faster when the fp8
 window.  A weight the row quantiser does not reach (K > ``ops.DECODE_FP8_MAX_K``: Yi-34B's down_proj) is timed alone on
 random finite e4m3 bytes — time does not depend on the values — and the layer that holds it refuses the mode, quantises nothing and
 runs on bf16, as it does in ``generate()``; the layer table reads that off the layers and says so.
+
+``--fp4`` measures the MXFP4 weight stream (``cmb_decode_linear_fp4``, ``layer.decode(..., fp4=True)``) against BOTH the bf16
+arm and the e4m3 arm, three arms alternating per geometry, by the same method; every ring is sized by the MXFP4 bytes (17 / 32
+byte per weight: nibbles + scales), which is what MB and GB/s count for that arm.  No weight is out of the block quantiser's
+reach, so the Yi-34B layers take the mode.  ``--step-log FILE``: the output of ``tools/bench_decode_step.py --fp4``, whose
+ms-per-token rows become the note's last table.
 
 For Llama-3-8B, Yi-34B (Llama blocks) and Phi-3-mini (Phi-3 block) in bf16, context 2048, batch 1 / 4 / 16, each arm runs in
 a fresh child process (one per geometry and arm, the arms alternating) and times with HIP events after a warm-up of every
@@ -59,20 +67,24 @@ def linear_shapes(g: dict) -> dict:
 
 
 def weight_bytes(g: dict, elem: int = 2) -> dict:
+    """``elem``: bytes per weight, or "fp4" = 17 / 32 (a nibble and 1 / 32 of a scale byte)"""
+    if elem == "fp4":
+        return {k: n * kk * 17 // 32 for k, (n, kk) in linear_shapes(g).items()}
     return {k: n * kk * elem for k, (n, kk) in linear_shapes(g).items()}
 
 
-def child(geom: str, arm: str, iters: int, warmup: int, quick: bool, ring_fp8: bool = False) -> None:
+def child(geom: str, arm: str, iters: int, warmup: int, quick: bool, ring_fp8: bool = False, ring_fp4: bool = False) -> None:
     import torch
     import torch.nn.functional as F
     from cambrian_amd import ops
     from cambrian_amd.model.language_model import cambrian_llama as CL, cambrian_phi3 as CP
     if not torch.cuda.is_available():
         raise SystemExit("bench_decode_linear: no GPU visible")
-    fp8 = arm == "fp8"
-    on = arm == "on" or fp8
+    fp8, fp4 = arm == "fp8", arm == "fp4"
+    on = arm == "on" or fp8 or fp4
     assert ops.decode_linear_enabled(1) == on and ops.decode_linear_enabled(16) == on and ops.decode_attention_enabled()
-    assert ops.decode_fp8_enabled() == fp8
+    assert ops.decode_fp8_enabled() == fp8 and ops.decode_fp4_enabled() == fp4
+    low = {"fp4": True} if fp4 else {}
     dev, dt = torch.device("cuda:0"), torch.bfloat16
     g = dict(GEOMS[geom])
     lm = g.pop("lm")
@@ -80,8 +92,9 @@ def child(geom: str, arm: str, iters: int, warmup: int, quick: bool, ring_fp8: b
     cfg = mod.CambrianConfig(vocab_size=64, num_hidden_layers=1, rms_norm_eps=1e-5, rope_theta=500000.0,
                              max_position_embeddings=16384, **g)
     torch.manual_seed(0)
-    wb = weight_bytes(g, 1 if fp8 else 2)                    # the bytes a call streams
-    ring_wb = weight_bytes(g, 1) if ring_fp8 else wb         # an fp8 run sizes BOTH arms' rings by the 1-byte weights
+    wb = weight_bytes(g, "fp4" if fp4 else (1 if fp8 else 2))        # the bytes a call streams
+    # an fp8 run sizes BOTH arms' rings by the 1-byte weights, an fp4 run all three by the MXFP4 bytes
+    ring_wb = weight_bytes(g, "fp4") if ring_fp4 else (weight_bytes(g, 1) if ring_fp8 else wb)
     ring = max(4, -(-RING_BYTES // sum(ring_wb.values())))
     cls = CP.Phi3DecoderLayer if lm == "phi3" else CL.LlamaDecoderLayer
     layers = [cls(cfg, dev, dt).requires_grad_(False) for _ in range(ring)]
@@ -94,6 +107,8 @@ def child(geom: str, arm: str, iters: int, warmup: int, quick: bool, ring_fp8: b
 
     def weight(k):
         w = torch.randn(shapes[k], device=dev, dtype=dt) * shapes[k][1] ** -0.5
+        if fp4:
+            return ops.decode_fp4_weight(w)
         if not fp8:
             return w
         if ops.decode_linear_fp8_weight_supported(1, w, "swiglu" if k == "gate_up" else None):
@@ -129,13 +144,15 @@ def child(geom: str, arm: str, iters: int, warmup: int, quick: bool, ring_fp8: b
         cos, sin = ops.rope_table(torch.full((B, 1), CTX, device=dev), hd, 500000.0)
 
         def layer_call(i):
-            layers[i % ring].decode(x, cos, sin, kc, vc, t, mask, fp8=fp8)
+            layers[i % ring].decode(x, cos, sin, kc, vc, t, mask, fp8=fp8, **low)
 
         def lin_call(name):
             ws, n, xin = weights[name], rings[name], xs[name]
             if on:
                 kw = {"qkv": dict(norm_weight=nw, eps=eps), "o": dict(residual=x2),
                       "gate_up": dict(norm_weight=nw, eps=eps, act="swiglu"), "down": dict(residual=x2)}[name]
+                if fp4:
+                    return lambda i: ops.decode_linear_fp4(xin, *ws[i % n], **kw)
                 if fp8:
                     return lambda i: ops.decode_linear_fp8(xin, *ws[i % n], **kw)
                 return lambda i: ops.decode_linear(xin, ws[i % n], **kw)
@@ -159,16 +176,20 @@ def child(geom: str, arm: str, iters: int, warmup: int, quick: bool, ring_fp8: b
             # whether the layers took the mode is read off the layers: the copies they cached, none when a weight was refused
             rec["layer_fp8"] = any(k.endswith("_fp8") for m in layers[0].modules() for k in m.__dict__)
             assert rec["layer_fp8"] == all(any(k.endswith("_fp8") for m in ly.modules() for k in m.__dict__) for ly in layers)
+            rec["layer_fp4"] = any(k.endswith("_fp4") for m in layers[0].modules() for k in m.__dict__)
+            assert rec["layer_fp4"] == all(any(k.endswith("_fp4") for m in ly.modules() for k in m.__dict__) for ly in layers)
             rec["layer_us"] = timed(layer_call, iters)
             for k in LINEARS:
                 rec[k + "_us"] = timed(calls[k], iters)
         print("BENCH_DECODE_LINEAR " + json.dumps(rec), flush=True)
 
 
-def resource_usage(fp8: bool = False) -> list:
-    """hipcc's kernel-resource-usage remarks for decode_linear.hip (``fp8``: decode_linear_fp8.hip with the Makefile's flag
-    for that file; no GPU needed): one dict per instantiation"""
-    src = os.path.join(ROOT, "cambrian_amd", "csrc", "decode_linear_fp8.hip" if fp8 else "decode_linear.hip")
+def resource_usage(fp8: bool = False, fp4: bool = False) -> list:
+    """hipcc's kernel-resource-usage remarks for decode_linear.hip (``fp8`` / ``fp4``: decode_linear_fp8.hip / _fp4.hip with the
+    Makefile's flag for that file; no GPU needed): one dict per instantiation"""
+    stem = "decode_linear_fp4" if fp4 else ("decode_linear_fp8" if fp8 else "decode_linear")
+    fp8 = fp8 or fp4                                         # the same extra flag
+    src = os.path.join(ROOT, "cambrian_amd", "csrc", stem + ".hip")
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     p = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Rpass-analysis=kernel-resource-usage"]
                        + (["-fno-slp-vectorize"] if fp8 else []) + ["-c", src, "-o", os.devnull],
@@ -179,7 +200,7 @@ def resource_usage(fp8: bool = False) -> list:
     for ln in p.stderr.splitlines():
         m = re.search(r"Function Name: (\S+)", ln)
         if m:
-            cur = dict(name=m.group(1)) if ("decode_linear_fp8_kernel" if fp8 else "decode_linear_kernel") in m.group(1) else None
+            cur = dict(name=m.group(1)) if (stem + "_kernel") in m.group(1) else None
             if cur is not None:
                 out.append(cur)
             continue
@@ -196,6 +217,9 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
     ap.add_argument("--fp8", action="store_true", help="the e4m3 weight stream against the bf16 decode_linear arm -> profiles/decode_fp8.md")
+    ap.add_argument("--fp4", action="store_true", help="the MXFP4 weight stream against the bf16 and e4m3 arms -> profiles/decode_fp4.md")
+    ap.add_argument("--step-log", help="with --fp4: output of tools/bench_decode_step.py --fp4 (ms per token on the one-call step)")
+    ap.add_argument("--from-log", help="with --fp4: a run's output; write the note again without running anything")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--quick", action="store_true", help="first batch only (rehearsal)")
@@ -203,24 +227,32 @@ def main() -> None:
     ap.add_argument("--dump-resources", metavar="FILE")
     ap.add_argument("--child", nargs=2, metavar=("GEOM", "ARM"))
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "decode_fp8.md" if a.fp8 else "decode_linear.md")
+    if a.fp4 and a.fp8:
+        ap.error("--fp4 measures the e4m3 arm too: give one of --fp8 / --fp4")
+    a.out = a.out or os.path.join(ROOT, "profiles", "decode_fp4.md" if a.fp4 else ("decode_fp8.md" if a.fp8 else "decode_linear.md"))
     if a.dump_resources:
         with open(a.dump_resources, "w") as fh:
-            json.dump(resource_usage(a.fp8), fh, indent=1)
+            json.dump(resource_usage(a.fp8, a.fp4), fh, indent=1)
         return
     if a.iters < 30:
         ap.error("--iters: at least 30")
     if a.child:
-        child(a.child[0], a.child[1], a.iters, a.warmup, a.quick, a.fp8)
+        child(a.child[0], a.child[1], a.iters, a.warmup, a.quick, a.fp8, a.fp4)
         return
     recs = {}
-    for geom in GEOMS:
-        for arm in (("fp8", "on") if a.fp8 else ("on", "off")):
+    if a.fp4 and a.from_log:
+        with open(a.from_log) as fh:
+            for ln in fh:
+                if ln.startswith("BENCH_DECODE_LINEAR "):
+                    r = json.loads(ln[len("BENCH_DECODE_LINEAR "):])
+                    recs[r["geom"], r["B"], r["arm"]] = r
+    for geom in ([] if a.fp4 and a.from_log else GEOMS):
+        for arm in (("fp4", "fp8", "on") if a.fp4 else ("fp8", "on") if a.fp8 else ("on", "off")):
             env = dict(os.environ, CAMBRIAN_AMD_DECODE_LINEAR="0" if arm == "off" else "1",
-                       CAMBRIAN_AMD_DECODE_FP8="1" if arm == "fp8" else "0")
+                       CAMBRIAN_AMD_DECODE_FP8="1" if arm == "fp8" else "0", CAMBRIAN_AMD_DECODE_FP4="1" if arm == "fp4" else "0")
             env.pop("CAMBRIAN_AMD_DECODE_ATTN", None)
             cmd = [sys.executable, os.path.abspath(__file__), "--child", geom, arm, "--iters", str(a.iters),
-                   "--warmup", str(a.warmup)] + (["--quick"] if a.quick else []) + (["--fp8"] if a.fp8 else [])
+                   "--warmup", str(a.warmup)] + (["--quick"] if a.quick else []) + (["--fp8"] if a.fp8 else []) + (["--fp4"] if a.fp4 else [])
             p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
             if p.returncode != 0:                   # a child that failed ends the run: nothing else is started on the GPU
                 sys.stderr.write(p.stdout + p.stderr)
@@ -234,13 +266,16 @@ def main() -> None:
         with open(a.resources) as fh:
             res = json.load(fh)
     else:
-        res = resource_usage(a.fp8)
+        res = resource_usage(a.fp8, a.fp4)
 
     def f(t3):
         return f"{t3[0]:.1f} ({t3[1]:.1f} - {t3[2]:.1f})"
 
     if a.fp8:
         write_fp8(a, recs, res, f)
+        return
+    if a.fp4:
+        write_fp4(a, recs, res, f)
         return
 
     lines = ["# Decode step: `cmb_decode_linear` (five launches per layer) against the stock sequence", "",
@@ -375,6 +410,82 @@ def write_fp8(a, recs, res, f) -> None:
     for r in sorted(res, key=lambda r: (r["norm"], r["tiles"])):
         lines.append(f"| {8 * r['tiles']} | {'yes' if r['norm'] else 'no'} | {r.get('VGPRs')} | {r.get('AGPRs')} | {r.get('TotalSGPRs')} | "
                      f"{r.get('VGPRs Spill')} | {r.get('SGPRs Spill')} | {r.get('LDS')} | {r.get('ScratchSize')} | {r.get('Occupancy')} |")
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
+def write_fp4(a, recs, res, f) -> None:
+    """profiles/decode_fp4.md: the MXFP4 stream (arm ``fp4``) against the bf16 ``decode_linear`` arm (``on``) and the e4m3 arm
+    (``fp8``); a verdict against each on every row"""
+    def verdict(o, z):
+        return "faster" if o[0] < z[1] else "not faster"
+
+    lines = ["# Decode step: `cmb_decode_linear_fp4` (MXFP4 weights, 4.25 bits per weight) against the bf16 and e4m3 linears", "",
+             f"Command: `python tools/bench_decode_linear.py --fp4 --iters {a.iters} --warmup {a.warmup}`" + (" `--quick`" if a.quick else ""),
+             f"on an MI355X, bf16 activations, context {CTX}, one decoder layer with random frozen weights; HIP "
+             f"events, median of 3 windows of {a.iters} calls (min - max in brackets), each arm in its own process, the three arms "
+             "alternating per geometry.  `fp4` = `CAMBRIAN_AMD_DECODE_FP4=1` (`layer.decode(..., fp4=True)`, `ops.decode_linear_fp4`), "
+             "`fp8` = `CAMBRIAN_AMD_DECODE_FP8=1` (`ops.decode_linear_fp8`), `bf16` = the default path (`ops.decode_linear`).  Every "
+             "call takes the next of a ring of weight sets of at least 768 MB of the MXFP4 bytes, in all three arms.  fp4 MB = "
+             "17 / 32 byte per weight (nibbles and scale bytes); GB/s = fp4 MB / fp4 time, the share is of the "
+             f"~{HBM_TBPS} TB/s an MI355X achieves from HBM.  A row is **faster** than an arm when the fp4 median is below that arm's "
+             "minimum window; `not faster` is said where that is what it is.", "",
+             "## One `layer.decode` call", "",
+             "| model | B | fp4 MB | fp4 us | fp8 us | bf16 us | bf16 / fp4 | fp8 / fp4 | fp4 GB/s | of HBM | vs bf16 | vs fp8 |",
+             "|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    slow = []
+    for geom in GEOMS:
+        for B in BATCHES:
+            o, e, z = recs.get((geom, B, "fp4")), recs.get((geom, B, "fp8")), recs.get((geom, B, "on"))
+            if o is None or e is None or z is None:
+                continue
+            taken = "taken" if o["layer_fp4"] else "NOT taken (the layer refused a weight and ran on bf16)"
+            e_note = "" if e["layer_fp8"] else " (the fp8 arm's layer refused a weight and ran on bf16)"
+            mb = sum(o["bytes"].values())
+            gbs = mb / (o["layer_us"][0] * 1e-6) / 1e9
+            v16, v8 = verdict(o["layer_us"], z["layer_us"]), verdict(o["layer_us"], e["layer_us"])
+            slow += [f"{geom} B {B} layer vs {n}" for n, v in (("bf16", v16), ("fp8", v8)) if v != "faster"]
+            lines.append(f"| {geom} | {B} | {mb / 1e6:.1f} | {f(o['layer_us'])} | {f(e['layer_us'])} | {f(z['layer_us'])} | "
+                         f"{z['layer_us'][0] / o['layer_us'][0]:.2f} | {e['layer_us'][0] / o['layer_us'][0]:.2f} | {gbs:.0f} | "
+                         f"{gbs / (HBM_TBPS * 1e3) * 100:.0f} % | {v16}; mode {taken} | {v8}{e_note} |")
+    lines += ["", "## The four linears alone (one `ops.decode_linear_fp4` call against one `ops.decode_linear_fp8` / `ops.decode_linear` call)", "",
+              "Small linears sit on the host's launch floor (the timed loop issues every call from Python, as `generate()` does): "
+              "where a linear's time stays put while its MB change, the floor is what is timed and the GB/s column is not a figure "
+              "of the kernel.  Yi-34B's `down` (K = 20480) is past the e4m3 row quantiser's reach: its fp8 figure is the e4m3 kernel "
+              "on random finite bytes, as in profiles/decode_fp8.md.", "",
+              "| model | B | linear | N x K | fp4 MB | fp4 us | fp8 us | bf16 us | bf16 / fp4 | fp8 / fp4 | fp4 GB/s | of HBM | vs bf16 | vs fp8 |",
+              "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for geom in GEOMS:
+        shapes = linear_shapes({k: v for k, v in GEOMS[geom].items() if k != "lm"})
+        for B in BATCHES:
+            o, e, z = recs.get((geom, B, "fp4")), recs.get((geom, B, "fp8")), recs.get((geom, B, "on"))
+            if o is None or e is None or z is None:
+                continue
+            for k in LINEARS:
+                mb = o["bytes"][k]
+                gbs = mb / (o[k + "_us"][0] * 1e-6) / 1e9
+                v16, v8 = verdict(o[k + "_us"], z[k + "_us"]), verdict(o[k + "_us"], e[k + "_us"])
+                slow += [f"{geom} B {B} {k} vs {n}" for n, v in (("bf16", v16), ("fp8", v8)) if v != "faster"]
+                lines.append(f"| {geom} | {B} | {k} | {shapes[k][0]} x {shapes[k][1]} | {mb / 1e6:.1f} | {f(o[k + '_us'])} | "
+                             f"{f(e[k + '_us'])} | {f(z[k + '_us'])} | {z[k + '_us'][0] / o[k + '_us'][0]:.2f} | "
+                             f"{e[k + '_us'][0] / o[k + '_us'][0]:.2f} | {gbs:.0f} | {gbs / (HBM_TBPS * 1e3) * 100:.0f} % | {v16} | {v8} |")
+    lines += ["", "## Verdict", "",
+              "Not faster (fp4 median not below the other arm's minimum): " + ("; ".join(slow) if slow else "nowhere") + ".",
+              "The mode stays opt-in whatever this table says: it changes numerics, and coarsely (about 11 % relative L2 error per "
+              "weight on Gaussian weights; task quality on real checkpoints is unmeasured).", ""]
+    if a.step_log:
+        from bench_decode_step import fp4_step_section
+        lines += fp4_step_section(a.step_log) + [""]
+    lines += ["## Kernel resource usage (`hipcc -Rpass-analysis=kernel-resource-usage -fno-slp-vectorize`, gfx950)", "",
+              "| slab rows | norm prologue | VGPRs | AGPRs | SGPRs | VGPR spills | SGPR spills | LDS bytes | scratch bytes / lane | waves / SIMD |",
+              "|---|---|---|---|---|---|---|---|---|---|"]
+    for r in sorted(res, key=lambda r: (r["norm"], r["tiles"])):
+        lines.append(f"| {8 * r['tiles']} | {'yes' if r['norm'] else 'no'} | {r.get('VGPRs')} | {r.get('AGPRs')} | {r.get('TotalSGPRs')} | "
+                     f"{r.get('VGPRs Spill')} | {r.get('SGPRs Spill')} | {r.get('LDS')} | {r.get('ScratchSize')} | {r.get('Occupancy')} |")
+    lines += ["", "The 32-row slab with the norm prologue is built for one workgroup per CU (`__launch_bounds__(256, 1)`): with two "
+              "it needs 116 bytes of scratch per lane; its AGPRs are register overflow, not accumulators."]
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
         fh.write("\n".join(lines) + "\n")

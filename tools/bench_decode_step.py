@@ -5,6 +5,8 @@
                                       [--yardstick-repeats N]
     python tools/bench_decode_step.py --from-log FILE               # no GPU: the table again from a run's output
     python tools/bench_decode_step.py --dump-resources FILE         # no GPU: hipcc's register / LDS / scratch report
+    python tools/bench_decode_step.py --fp4 [--new 32] [--quick]    # the one-call step on MXFP4 / e4m3 / bf16 weights; prints
+                                                                    # the records tools/bench_decode_linear.py --fp4 --step-log reads
     python tools/bench_decode_step.py --sample [--out profiles/decode_sample.md] [--new 32] [--arms bf16-on,bf16-off,...]
                                       [--parent-tree DIR] [--from-log FILE] [--resources FILE]     # see ``sample_main``
 
@@ -46,8 +48,10 @@ def child(tree: str, arm: str, new: int, quick: bool) -> None:
     if not torch.cuda.is_available():
         raise SystemExit("bench_decode_step: no GPU visible")
     assert os.path.dirname(os.path.dirname(os.path.abspath(ops.__file__))) == os.path.abspath(tree)
-    prec, switch = arm.split("-")                       # bf16 | fp8, on | off | parent
+    prec, switch = arm.split("-")                       # bf16 | fp8 | fp4, on | off | parent
     assert ops.decode_fp8_enabled() == (prec == "fp8")
+    if hasattr(ops, "decode_fp4_enabled"):
+        assert ops.decode_fp4_enabled() == (prec == "fp4")
     if switch != "parent":
         assert ops.decode_step_enabled() == (switch == "on")
     dev, dt = torch.device("cuda:0"), torch.bfloat16
@@ -95,6 +99,36 @@ def child(tree: str, arm: str, new: int, quick: bool) -> None:
             rec[name] = (statistics.median(win), min(win), max(win))
         print(TAG + json.dumps(rec), flush=True)
         del ids
+
+
+def fp4_step_section(log: str) -> list:
+    """The lines of profiles/decode_fp4.md's one-call-step table from the output of ``--fp4``"""
+    recs = {}
+    with open(log) as fh:
+        for ln in fh:
+            if ln.startswith(TAG):
+                r = json.loads(ln[len(TAG):])
+                recs[r["arm"], r["B"]] = r
+
+    def f(t3):
+        return f"{t3[0]:.3f} ({t3[1]:.3f} - {t3[2]:.3f})"
+
+    new = next(iter(recs.values()))["new"] if recs else 0
+    lines = ["## ms per decoded token on the one-call step (`CAMBRIAN_AMD_DECODE_STEP=1`), Llama-3-8B at full depth", "",
+             f"`python tools/bench_decode_step.py --fp4 --new {new}`: 32 layers, vocabulary 128256, random frozen weights, a text-only "
+             f"prompt of {CTX} tokens, greedy without an eos id; ms per decoded token = (wall clock of `generate()` for 1 + {new} "
+             f"tokens - that for 1 token, device synchronised) / {new}.  Median of 3 windows (min - max), each arm in its own "
+             "process.  All three arms issue one `cmb_decode_step` per token; what differs is the weight format it streams.  "
+             "**faster** = the fp4 median is below the other arm's fastest window.", "",
+             "| B | fp4 ms / token | fp8 ms / token | bf16 ms / token | bf16 / fp4 | fp8 / fp4 | vs bf16 | vs fp8 |", "|---|---|---|---|---|---|---|---|"]
+    for B in BATCHES:
+        o, e, z = recs.get(("fp4-on", B)), recs.get(("fp8-on", B)), recs.get(("bf16-on", B))
+        if o is None or e is None or z is None:
+            continue
+        k = "greedy"
+        lines.append(f"| {B} | {f(o[k])} | {f(e[k])} | {f(z[k])} | {z[k][0] / o[k][0]:.2f} | {e[k][0] / o[k][0]:.2f} | "
+                     f"{'faster' if o[k][0] < z[k][1] else 'not faster'} | {'faster' if o[k][0] < e[k][1] else 'not faster'} |")
+    return lines
 
 
 def resource_usage(source: str = "decode_next.hip", kernel: str = "decode_next_kernel") -> list:
@@ -374,6 +408,7 @@ def main() -> None:
     ap.add_argument("--child", nargs=2, metavar=("TREE", "ARM"))
     ap.add_argument("--sample", action="store_true", help="sampled decoding: the device sampler against torch's warpers")
     ap.add_argument("--arms", help="with --sample: a comma-separated subset of the arms to run")
+    ap.add_argument("--fp4", action="store_true", help="the one-call step on MXFP4, e4m3 and bf16 weights (records on stdout)")
     a = ap.parse_args()
     if a.dump_resources:
         with open(a.dump_resources, "w") as fh:
@@ -394,12 +429,14 @@ def main() -> None:
         return
     arms = [("bf16-on", ROOT), ("bf16-off", ROOT)] + ([("bf16-parent", a.parent_tree)] if a.parent_tree else []) \
         + [("fp8-on", ROOT), ("fp8-off", ROOT)]
+    if a.fp4:
+        arms = [("fp4-on", ROOT), ("fp8-on", ROOT), ("bf16-on", ROOT)]
     recs, extra = {}, []
 
     def run(arm, tree, quick):
         prec, switch = arm.split("-")
         env = dict(os.environ, CAMBRIAN_AMD_DECODE_FP8="1" if prec == "fp8" else "0",
-                   CAMBRIAN_AMD_DECODE_STEP="1" if switch == "on" else "0")
+                   CAMBRIAN_AMD_DECODE_FP4="1" if prec == "fp4" else "0", CAMBRIAN_AMD_DECODE_STEP="1" if switch == "on" else "0")
         for k in ("CAMBRIAN_AMD_DECODE_ATTN", "CAMBRIAN_AMD_DECODE_LINEAR", "CAMBRIAN_AMD_LIB", "PYTHONPATH"):
             env.pop(k, None)
         cmd = [sys.executable, os.path.abspath(__file__), "--child", os.path.abspath(tree), arm, "--new", str(a.new)] \
@@ -429,6 +466,8 @@ def main() -> None:
                 for r in run(arm, tree, True):
                     extra.append(r)
                     print(YTAG + json.dumps(r), flush=True)
+    if a.fp4:           # the records are on stdout; profiles/decode_fp4.md is written by tools/bench_decode_linear.py --fp4 --step-log
+        return
     if a.resources:
         with open(a.resources) as fh:
             res = json.load(fh)
