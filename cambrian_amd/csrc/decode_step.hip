@@ -5,6 +5,7 @@
 // path passes, on one stream, so logits and caches carry the same bits; what it removes is the host work between launches
 // (per launch: the binding's predicates, two or three ctypes queries and a tensor allocation, for 32 layers).
 // Ordering comes from the stream alone.  Buffers: decode_step_layout.h.
+// cmb_decode_step_kv8 is the same body with cmb_decode_attn_kv8 (e4m3 K / V caches, decode_attn_kv8.hip) as launch 1.
 #include "common.h"
 #include "decode_step_layout.h"
 
@@ -65,9 +66,14 @@ extern "C" int64_t cmb_decode_step_ws(int32_t B, int32_t H, int32_t I, int32_t n
   return dsl_make(B, H, I, nh, nkv, hd, attn).total;
 }
 
-extern "C" int cmb_decode_step(const cmb_decode_step_desc* d, const cmb_decode_layer* layers, const void* x, int64_t x_ld,
-                               const float* cos_t, const float* sin_t, int64_t t, const uint8_t* key_valid, int64_t kv_ld,
-                               float* ws, int64_t ws_floats, float* logits, int64_t logits_ld, void* stream) {
+namespace {
+
+// cmb_decode_step (kv8 == nullptr: bf16 caches, element strides) and cmb_decode_step_kv8 (kv8[l]: layer l's factor arrays;
+// the caches are e4m3 bytes and d->c_s* byte strides): one body, launch 1 of a layer is the only difference
+int ds_step(const cmb_decode_step_desc* d, const cmb_decode_layer* layers, const cmb_decode_kv8_factors* kv8, int64_t i_sb,
+            int64_t i_sh, const void* x, int64_t x_ld, const float* cos_t, const float* sin_t, int64_t t,
+            const uint8_t* key_valid, int64_t kv_ld, float* ws, int64_t ws_floats, float* logits, int64_t logits_ld,
+            void* stream) {
   // ---- every rule before any launch ----
   if (!d || !layers || !x || !cos_t || !sin_t || !key_valid || !ws || !logits) return CMB_ERR_BAD_ARG;
   if (d->layers < 1 || d->B < 1 || d->B > DSL_MAX_B) return CMB_ERR_BAD_ARG;
@@ -81,6 +87,7 @@ extern "C" int cmb_decode_step(const cmb_decode_step_desc* d, const cmb_decode_l
   if (!(d->eps >= 0.f) || t < 0 || kv_ld < t + 1 || nkv > 65535) return CMB_ERR_BAD_ARG;
   if (x_ld < H || x_ld % 8 || logits_ld < d->V || logits_ld % 8) return CMB_ERR_BAD_ARG;
   if (d->c_sb < 0 || d->c_sh < 0 || d->c_st < hd) return CMB_ERR_BAD_ARG;
+  if (kv8 && (i_sb < 0 || i_sh < 0)) return CMB_ERR_BAD_ARG;
   const int64_t attn = ds_attn_floats(B, nh, nkv, hd, t);
   if (attn < 0) return CMB_ERR_BAD_ARG;
   const int64_t nq = (int64_t)nh * hd, nk = (int64_t)nkv * hd, nqkv = nq + 2 * nk;
@@ -102,9 +109,14 @@ extern "C" int cmb_decode_step(const cmb_decode_step_desc* d, const cmb_decode_l
     }
     if (!cmb_aligned16(L.norm1) || !cmb_aligned16(L.norm2) || !cmb_aligned16(L.kcache) || !cmb_aligned16(L.vcache))
       align = CMB_ERR_ALIGNMENT;
+    if (kv8) {
+      if (!kv8[l].k_inv || !kv8[l].v_inv) return CMB_ERR_BAD_ARG;
+      if (!aligned4(kv8[l].k_inv) || !aligned4(kv8[l].v_inv)) align = CMB_ERR_ALIGNMENT;
+    }
   }
+  const int cs_mult = kv8 ? 16 : 8;      // 16 bytes either way
   if (align != CMB_OK || !cmb_aligned16(x) || !cmb_aligned16(ws) || !cmb_aligned16(logits) || !cmb_aligned16(d->final_norm) ||
-      d->c_sb % 8 || d->c_sh % 8 || d->c_st % 8)
+      d->c_sb % cs_mult || d->c_sh % cs_mult || d->c_st % cs_mult)
     return CMB_ERR_ALIGNMENT;
   const dsl_layout lay = dsl_make(B, H, I, nh, nkv, hd, attn);
   if (ws_floats < lay.total) return CMB_ERR_WORKSPACE;
@@ -139,9 +151,14 @@ extern "C" int cmb_decode_step(const cmb_decode_step_desc* d, const cmb_decode_l
     if (rc != CMB_OK) return rc;
     dsl_launch_bufs(l, 1, &xi, &ri, &oi);
     const bf16_t* row = (const bf16_t*)buf[xi];
-    rc = cmb_decode_attn(CMB_BF16, row, ld[xi], row + nq, ld[xi], row + nq + nk, ld[xi], cos_t, sin_t, L.kcache, L.vcache,
-                         d->c_sb, d->c_sh, d->c_st, B, nh, nkv, hd, t, key_valid, kv_ld, d->scale, 0, partial, attn, buf[oi],
-                         stream);
+    if (kv8)
+      rc = cmb_decode_attn_kv8(row, ld[xi], row + nq, ld[xi], row + nq + nk, ld[xi], cos_t, sin_t, L.kcache, L.vcache, d->c_sb,
+                               d->c_sh, d->c_st, kv8[l].k_inv, kv8[l].v_inv, i_sb, i_sh, B, nh, nkv, hd, t, key_valid, kv_ld,
+                               d->scale, 0, partial, attn, buf[oi], stream);
+    else
+      rc = cmb_decode_attn(CMB_BF16, row, ld[xi], row + nq, ld[xi], row + nq + nk, ld[xi], cos_t, sin_t, L.kcache, L.vcache,
+                           d->c_sb, d->c_sh, d->c_st, B, nh, nkv, hd, t, key_valid, kv_ld, d->scale, 0, partial, attn, buf[oi],
+                           stream);
     if (rc != CMB_OK) return rc;
     dsl_launch_bufs(l, 2, &xi, &ri, &oi);
     rc = ds_linear(fp8, buf[xi], ld[xi], B, nullptr, 0.f, w_o, H, nq, 0, buf[ri], ld[ri], buf[oi], ld[oi], 0, stream);
@@ -156,4 +173,21 @@ extern "C" int cmb_decode_step(const cmb_decode_step_desc* d, const cmb_decode_l
   }
   const int hi = dsl_head_in();
   return ds_linear(fp8, buf[hi], ld[hi], B, d->final_norm, d->eps, head, d->V, H, 0, nullptr, 0, logits, logits_ld, 1, stream);
+}
+
+}  // namespace
+
+extern "C" int cmb_decode_step(const cmb_decode_step_desc* d, const cmb_decode_layer* layers, const void* x, int64_t x_ld,
+                               const float* cos_t, const float* sin_t, int64_t t, const uint8_t* key_valid, int64_t kv_ld,
+                               float* ws, int64_t ws_floats, float* logits, int64_t logits_ld, void* stream) {
+  return ds_step(d, layers, nullptr, 0, 0, x, x_ld, cos_t, sin_t, t, key_valid, kv_ld, ws, ws_floats, logits, logits_ld, stream);
+}
+
+extern "C" int cmb_decode_step_kv8(const cmb_decode_step_desc* d, const cmb_decode_layer* layers,
+                                   const cmb_decode_kv8_factors* factors, int64_t i_sb, int64_t i_sh, const void* x, int64_t x_ld,
+                                   const float* cos_t, const float* sin_t, int64_t t, const uint8_t* key_valid, int64_t kv_ld,
+                                   float* ws, int64_t ws_floats, float* logits, int64_t logits_ld, void* stream) {
+  if (!factors) return CMB_ERR_BAD_ARG;
+  return ds_step(d, layers, factors, i_sb, i_sh, x, x_ld, cos_t, sin_t, t, key_valid, kv_ld, ws, ws_floats, logits, logits_ld,
+                 stream);
 }

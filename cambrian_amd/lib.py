@@ -201,6 +201,11 @@ class DecodeStepDesc(C.Structure):
     ]
 
 
+class DecodeKv8Factors(C.Structure):
+    """cmb_decode_kv8_factors (include/cambrian_amd.h): one layer's K / V factor arrays of cmb_decode_step_kv8."""
+    _fields_ = [("k_inv", C.c_void_p), ("v_inv", C.c_void_p)]
+
+
 # symbol -> (restype, argtypes); every symbol of include/cambrian_amd.h must be listed here
 # (tests/test_abi.py cross-checks this table against the header).
 _i32, _i64, _f, _p = C.c_int32, C.c_int64, C.c_float, C.c_void_p
@@ -292,6 +297,11 @@ SIGNATURES = {
     "cmb_decode_step": (C.c_int, [C.POINTER(DecodeStepDesc), C.POINTER(DecodeLayer), _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _p,
                                   _i64, _p]),
     "cmb_decode_step_ws": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32, _i64]),
+    "cmb_kv_quantize_e4m3": (C.c_int, [_p, _i64, _i64, _i64, _i64, _i32, _i64, _i32, _p, _i64, _i64, _i64, _p, _i64, _i64, _p]),
+    "cmb_decode_attn_kv8": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _i64, _i64, _i64, _i32,
+                                      _i32, _i32, _i64, _p, _i64, _f, _i32, _p, _i64, _p, _p]),
+    "cmb_decode_step_kv8": (C.c_int, [C.POINTER(DecodeStepDesc), C.POINTER(DecodeLayer), C.POINTER(DecodeKv8Factors), _i64, _i64,
+                                      _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p]),
     "cmb_decode_next": (C.c_int, [_p, _i64, _i32, _i64, _i64, _p, _p, _i64, _i64, _p, _p, _p, _i64, _i64, _p, _i64, _i64, _i64, _p,
                                   _i64, _i32, _f, _p, _p, _p]),
     "cmb_decode_sample": (C.c_int, [_p, _i64, _i32, _i64, _f, _i64, _f, _p, _i64, _p, _p, _i64, _i64, _p, _p, _p, _i64, _i64, _p,

@@ -295,19 +295,19 @@ def decode_layer_fused(layer, x, cos, sin, kcache, vcache, t, key_mask, w_qkv, w
     if fp4 is not None:
         q_qkv, q_o, q_gate_up, q_down = fp4
         row = ops.decode_linear_fp4(x2, *q_qkv, norm_weight=n1.weight, eps=n1.variance_epsilon)
-        o = ops.decode_attention(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t, key_mask)
+        o = ops.decode_attention_any(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t, key_mask)
         x2 = ops.decode_linear_fp4(o, *q_o, residual=x2)
         inner = ops.decode_linear_fp4(x2, *q_gate_up, norm_weight=n2.weight, eps=n2.variance_epsilon, act="swiglu")
         return ops.decode_linear_fp4(inner, *q_down, residual=x2).reshape(B, 1, -1)
     if fp8 is not None:
         q_qkv, q_o, q_gate_up, q_down = fp8
         row = ops.decode_linear_fp8(x2, *q_qkv, norm_weight=n1.weight, eps=n1.variance_epsilon)
-        o = ops.decode_attention(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t, key_mask)
+        o = ops.decode_attention_any(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t, key_mask)
         x2 = ops.decode_linear_fp8(o, *q_o, residual=x2)
         inner = ops.decode_linear_fp8(x2, *q_gate_up, norm_weight=n2.weight, eps=n2.variance_epsilon, act="swiglu")
         return ops.decode_linear_fp8(inner, *q_down, residual=x2).reshape(B, 1, -1)
     row = ops.decode_linear(x2, w_qkv, norm_weight=n1.weight, eps=n1.variance_epsilon)
-    o = ops.decode_attention(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t, key_mask)
+    o = ops.decode_attention_any(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t, key_mask)
     x2 = ops.decode_linear(o, w_o, residual=x2)
     inner = ops.decode_linear(x2, w_gate_up, norm_weight=n2.weight, eps=n2.variance_epsilon, act="swiglu")
     return ops.decode_linear(inner, w_down, residual=x2).reshape(B, 1, -1)
@@ -376,7 +376,7 @@ class LlamaAttention(nn.Module):
             else:
                 x2 = x.reshape(B, -1)
                 q, k, v = self.q_proj(x2), self.k_proj(x2), self.v_proj(x2)
-            o = ops.decode_attention(q, k, v, cos, sin, kcache, vcache, t, key_mask)
+            o = ops.decode_attention_any(q, k, v, cos, sin, kcache, vcache, t, key_mask)
             return self.o_proj(o.view(B, 1, nq))
         key_mask = key_mask[:, :t + 1]
         q = ops.rope(self.q_proj(x).view(B, self.nh, self.hd), cos, sin).view(B, 1, self.nh, self.hd).transpose(1, 2)
@@ -790,7 +790,8 @@ class DecodeStepPlan:
     (``ops.decode_step``): the layer table and the step descriptor in host memory, the objects that own every pointer in
     them, the workspace and the logits buffer.  ``build`` returns None unless the whole model qualifies — every layer under
     the five-launch conditions, the lm_head under ``_decode_logits``' condition, with ``fp8`` the e4m3 copies (with ``fp4`` the
-    MXFP4 copies, ``cmb_decode_step_desc.fp8`` = 2) of every weight — and the call then runs on the per-launch loop, unchanged."""
+    MXFP4 copies, ``cmb_decode_step_desc.fp8`` = 2) of every weight — and the call then runs on the per-launch loop, unchanged.
+    ``caches``: per layer (k, v), bf16 tensors or ``ops.KvCacheE4M3`` pairs (the step is then ``cmb_decode_step_kv8``)."""
 
     @classmethod
     def build(cls, lm, B: int, caches, t_max: int, fp8: bool, fp4: bool = False):
@@ -809,8 +810,12 @@ class DecodeStepPlan:
         if head is None or (quant and head[1] is None):
             return None
         eps = float(model.norm.variance_epsilon)
-        kc0 = caches[0][0]
-        keep, rows, inter = [x, head, model.norm.weight, caches], [], None
+        kv8 = isinstance(caches[0][0], ops.KvCacheE4M3)          # e4m3 caches: byte tensors + factor arrays (cmb_decode_step_kv8)
+        if kv8 and not ops.decode_attention_kv8_supported(torch.bfloat16, nh, nkv, hd):
+            return None
+        kc0 = caches[0][0].q if kv8 else caches[0][0]
+        inv0 = caches[0][0].inv if kv8 else None
+        keep, rows, inter, factors = [x, head, model.norm.weight, caches], [], None, []
         for layer, (kc, vc) in zip(model.layers, caches):
             a = layer.self_attn
             n1, n2 = layer.input_layernorm, layer.post_attention_layernorm
@@ -825,7 +830,13 @@ class DecodeStepPlan:
                     or w[1].shape != (H, nh * hd) or w[3].shape != (H, w[2].shape[0] // 2) or w[2].shape[1] != H:
                 return None
             inter = w[2].shape[0] // 2
-            if kc.dtype != torch.bfloat16 or vc.dtype != kc.dtype or kc.shape != (B, nkv, kc0.shape[2], hd) \
+            if kv8:
+                if not (isinstance(kc, ops.KvCacheE4M3) and isinstance(vc, ops.KvCacheE4M3)) \
+                        or any(c.inv.stride() != inv0.stride() for c in (kc, vc)):
+                    return None
+                factors.append(_lib.DecodeKv8Factors(kc.inv.data_ptr(), vc.inv.data_ptr()))
+                kc, vc = kc.q, vc.q
+            if kc.dtype != (torch.uint8 if kv8 else torch.bfloat16) or vc.dtype != kc.dtype or kc.shape != (B, nkv, kc0.shape[2], hd) \
                     or vc.shape != kc.shape or kc.stride() != kc0.stride() or vc.stride() != kc0.stride() or kc.stride(3) != 1:
                 return None
             row = _lib.DecodeLayer()
@@ -852,6 +863,7 @@ class DecodeStepPlan:
                                      final_norm=model.norm.weight.data_ptr(), head=hw.data_ptr(), ld_head=hw.stride(0),
                                      head_scale=_lib.ptr(hs))
         self.table = (_lib.DecodeLayer * len(rows))(*rows)
+        self.kv8 = ((_lib.DecodeKv8Factors * len(factors))(*factors), inv0.stride(0), inv0.stride(1)) if kv8 else None
         self.keep = keep
         self.ws = ops.decode_step_workspace(dev, ops.decode_step_ws_floats(B, H, inter, nh, nkv, hd, t_max))
         self.logits = torch.empty(B, (V + 7) // 8 * 8, dtype=torch.float32, device=dev)[:, :V]
@@ -860,6 +872,8 @@ class DecodeStepPlan:
 
     def step(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, t: int, key_valid: torch.Tensor) -> torch.Tensor:
         """fp32 logits [B, V] (the plan's buffer, overwritten by the next step) of the token whose embeddings are x [B, H]."""
+        if self.kv8 is not None:
+            return ops.decode_step(self.desc, self.table, x, cos, sin, t, key_valid, self.ws, self.logits, kv8=self.kv8)
         return ops.decode_step(self.desc, self.table, x, cos, sin, t, key_valid, self.ws, self.logits)
 
 
@@ -922,14 +936,17 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
         nh_kv, hd = model.layers[0].self_attn.nkv, model.layers[0].self_attn.hd
         if beams > 1:
             return _beam_search(self, logits, kv_out, valid, L, int(max_new_tokens), eos_token_id, kwargs.get("pad_token_id"),
-                                beams)
+                                beams, _kv8_wanted(self, dev, kv_out))
         Lmax = L + max_new_tokens
-        caches = []
-        for k, v in kv_out:
-            kc = torch.zeros(B, nh_kv, Lmax, hd, dtype=k.dtype, device=dev)
-            vc = torch.zeros_like(kc)
-            kc[:, :, :L], vc[:, :, :L] = k, v
-            caches.append((kc, vc))
+        if _kv8_wanted(self, dev, kv_out):          # e4m3 K / V cache, opt-in: resolved once per call
+            caches = _kv8_prefill(kv_out, B, 1, nh_kv, L, Lmax, hd, dev)
+        else:
+            caches = []
+            for k, v in kv_out:
+                kc = torch.zeros(B, nh_kv, Lmax, hd, dtype=k.dtype, device=dev)
+                vc = torch.zeros_like(kc)
+                kc[:, :, :L], vc[:, :, :L] = k, v
+                caches.append((kc, vc))
         key_mask = torch.zeros(B, Lmax, dtype=torch.bool, device=dev)
         key_mask[:, :L] = valid
         n_tok = valid.long().sum(1)
@@ -974,6 +991,45 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
                 x = layer.decode(x, cos, sin, kc, vc, t, key_mask, fp8=fp8, **low)      # [B, Lmax]: the step reads columns 0..t
             logits = _decode_logits(self, x, fp8, **low)
         return torch.stack(out_ids, 1)
+
+
+def _kv8_wanted(self, dev, kv_out) -> bool:
+    """Whether this ``generate()`` call keeps its K / V cache in e4m3 (``ops.decode_kv_fp8_enabled``): only when every
+    layer's decode step takes the decode-attention kernel — GPU, bf16, ``CAMBRIAN_AMD_DECODE_ATTN`` not 0, one geometry
+    that ``ops.decode_attention_kv8_supported`` accepts — because the SDPA branch of ``decode`` reads bf16 caches.  Otherwise
+    the call keeps bf16 caches and nothing extra is allocated."""
+    if not ops.decode_kv_fp8_enabled(getattr(getattr(self, "config", None), "decode_kv_fp8", False)):
+        return False
+    layers = self.model.layers
+    if dev.type != "cuda" or not len(layers) or len(kv_out) != len(layers) or not ops.decode_attention_enabled():
+        return False
+    a0 = layers[0].self_attn
+    return all((l.self_attn.nh, l.self_attn.nkv, l.self_attn.hd) == (a0.nh, a0.nkv, a0.hd) for l in layers) \
+        and ops.decode_attention_kv8_supported(self.model.llm_dtype, a0.nh, a0.nkv, a0.hd) \
+        and all(k.dtype == v.dtype == torch.bfloat16 and k.is_cuda for k, v in kv_out)
+
+
+def _kv8_prefill(kv_out: list, B: int, nb: int, nkv: int, L: int, Lmax: int, hd: int, dev):
+    """The e4m3 caches of ``B * nb`` rows (``nb`` beams per prompt, 1 = none) from the prefill's ``kv_out``, layer by layer:
+    each layer's bf16 (k, v) is quantised (``ops.kv_quantize_e4m3``; with beams once per prompt, bytes and factors then copied
+    into every beam's row) and dropped from ``kv_out`` before the next layer's cache is allocated, so the peak never holds both
+    caches in full."""
+    caches = []
+    for i in range(len(kv_out)):
+        pair = []
+        for src in kv_out[i]:
+            c = ops.KvCacheE4M3.empty(B * nb, nkv, Lmax, hd, dev)
+            if nb == 1:
+                ops.kv_quantize_e4m3(src, c, L)
+            else:
+                one = ops.kv_quantize_e4m3(src, ops.KvCacheE4M3.empty(B, nkv, L, hd, dev), L)
+                c.q.view(B, nb, nkv, Lmax, hd)[:, :, :, :L] = one.q[:, None]
+                c.inv.view(B, nb, nkv, Lmax)[:, :, :, :L] = one.inv[:, None]
+            pair.append(c)
+        kv_out[i] = None
+        del src
+        caches.append(tuple(pair))
+    return caches
 
 
 def _greedy_fused(plan, emb, logits, key_mask, n_tok, L0: int, max_new_tokens: int, eos_token_id, hd: int, theta: float):
@@ -1042,20 +1098,24 @@ def _sample_fused(plan, emb, logits, key_mask, n_tok, L0: int, max_new_tokens: i
     return ids.contiguous()
 
 
-def _beam_search(self, logits, kv_out, valid, L: int, max_new_tokens: int, eos_token_id, pad_token_id, nb: int):
+def _beam_search(self, logits, kv_out, valid, L: int, max_new_tokens: int, eos_token_id, pad_token_id, nb: int,
+                 kv8: bool = False):
     """Beam search after the prefill (``logits`` fp32 [B, V], ``kv_out`` every layer's K / V of the B prompts): the ``nb`` beams
     of a prompt are ``nb`` rows of a decode step, so the caches take ``nb`` times the memory of greedy decoding and the
     prompt's columns are copied into every beam's row.  Where the one-call plan is available the loop is ``_beam_fused``;
     else selection is ``beam.beam_update`` (plain torch) around ``layer.decode`` / ``plan.step``, and each step moves the
-    generated columns of every cache from the parents' rows with an ``index_select``."""
+    generated columns of every cache from the parents' rows with an ``index_select``.  ``kv8``: e4m3 caches
+    (``_kv8_wanted``) — the B prompts are quantised once and their bytes and factors copied into every beam's row, the
+    selection is always the torch one (``cmb_decode_beam`` moves bf16 columns only) and the per-step ``index_select`` moves the
+    generated columns of bytes and of factors."""
     model = self.model
     B, V = logits.shape
     dev = logits.device
     R = B * nb
     nh_kv, hd = model.layers[0].self_attn.nkv, model.layers[0].self_attn.hd
     Lmax = L + max_new_tokens
-    caches = []
-    for k, v in kv_out:
+    caches = _kv8_prefill(kv_out, B, nb, nh_kv, L, Lmax, hd, dev) if kv8 else []
+    for k, v in ([] if kv8 else kv_out):
         kc = torch.zeros(R, nh_kv, Lmax, hd, dtype=k.dtype, device=dev)
         vc = torch.zeros_like(kc)
         kc.view(B, nb, nh_kv, Lmax, hd)[:, :, :, :L] = k[:, None]
@@ -1073,7 +1133,7 @@ def _beam_search(self, logits, kv_out, valid, L: int, max_new_tokens: int, eos_t
     plan = None
     if max_new_tokens > 1 and ops.decode_step_enabled(getattr(self.config, "decode_step_fused", False)):
         plan = DecodeStepPlan.build(self, R, caches, Lmax - 1, fp8, **low)
-    if plan is not None and R <= ops.DECODE_BEAM_MAX and V >= 2 and V * nb < 2 ** 31:
+    if plan is not None and not kv8 and R <= ops.DECODE_BEAM_MAX and V >= 2 and V * nb < 2 ** 31:
         emb = model.embed_tokens.weight
         if emb.dtype == torch.bfloat16 and emb.stride(1) == 1 and emb.stride(0) % 8 == 0 and emb.data_ptr() % 16 == 0 \
                 and emb.shape[0] >= V and (eos_token_id is None or 0 <= int(eos_token_id) < emb.shape[0]):
@@ -1088,8 +1148,8 @@ def _beam_search(self, logits, kv_out, valid, L: int, max_new_tokens: int, eos_t
         if step:
             rows = (parent + first).reshape(-1)
             for kc, vc in caches:
-                kc[:, :, L:t] = kc[:, :, L:t].index_select(0, rows)
-                vc[:, :, L:t] = vc[:, :, L:t].index_select(0, rows)
+                for c in ((kc.q, kc.inv, vc.q, vc.inv) if kv8 else (kc, vc)):
+                    c[:, :, L:t] = c[:, :, L:t].index_select(0, rows)
         key_mask[:, t] = True
         cos, sin = ops.rope_table((n_tok + step)[:, None], hd, theta)
         x = model.embed_tokens(tok.reshape(-1))[:, None, :].to(model.llm_dtype)

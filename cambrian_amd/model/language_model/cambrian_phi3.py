@@ -100,7 +100,7 @@ class Phi3Attention(nn.Module):
         if use_decode_kernel(x, self.nh, self.nkv, self.hd):
             nq, nk = self.nh * self.hd, self.nkv * self.hd
             row = self.qkv_proj(x.reshape(B, -1))
-            o = ops.decode_attention(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t, key_mask)
+            o = ops.decode_attention_any(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t, key_mask)
             return self.o_proj(o.view(B, 1, nq))
         key_mask = key_mask[:, :t + 1]
         q, k, v = ops.qkv_rope(self.qkv_proj(x).contiguous(), cos, sin, self.nh, self.nkv, self.hd)   # [B,h,1,hd]

@@ -2200,6 +2200,123 @@ def decode_attention_enabled() -> bool:
     return L.env_flag("CAMBRIAN_AMD_DECODE_ATTN", True)
 
 
+# ------------------------------------------------------------------------------------------------
+# the same step on an e4m3 K / V cache (decode_attn_kv8.hip): one byte per element plus one fp32 factor per cache row, about
+# half the cache's memory and stream.  Opt-in (``config.decode_kv_fp8`` / CAMBRIAN_AMD_DECODE_KV_FP8): it changes numerics
+# (profiles/decode_kv8.md has what was measured).
+# ------------------------------------------------------------------------------------------------
+def decode_kv_fp8_enabled(config_flag: bool = False) -> bool:
+    """Whether ``generate()`` keeps its K / V cache in e4m3: ``CAMBRIAN_AMD_DECODE_KV_FP8`` = ``1`` / ``0`` in the environment
+    overrides, unset (or empty) it is ``config_flag`` (the model's ``config.decode_kv_fp8``, absent = off)."""
+    v = os.environ.get("CAMBRIAN_AMD_DECODE_KV_FP8")
+    if v is None or v == "":
+        return bool(config_flag)
+    return v != "0"
+
+
+class KvCacheE4M3:
+    """One tensor (K or V) of a layer's cache in the format of ``cmb_decode_attn_kv8``: ``q`` uint8 [B, nkv, Lmax, hd] (OCP
+    e4m3fn bytes, rows of hd contiguous bytes) and ``inv`` fp32 [B, nkv, Lmax] (slot stride 1); an entry's value is
+    ``e4m3(q) * inv``."""
+    __slots__ = ("q", "inv")
+
+    def __init__(self, q: torch.Tensor, inv: torch.Tensor):
+        if q.dtype != torch.uint8 or inv.dtype != torch.float32 or q.dim() != 4 or inv.shape != q.shape[:3] \
+                or q.stride(3) != 1 or inv.stride(2) != 1 or q.device != inv.device:
+            raise L.CambrianAmdError("KvCacheE4M3: q is uint8 [B, nkv, Lmax, hd] with contiguous rows, inv fp32 [B, nkv, Lmax] "
+                                     "with contiguous slots, on one device")
+        self.q, self.inv = q, inv
+
+    @classmethod
+    def empty(cls, B: int, nkv: int, Lmax: int, hd: int, device) -> "KvCacheE4M3":
+        """Zero bytes (the value 0) and zero factors."""
+        return cls(torch.zeros(B, nkv, Lmax, hd, dtype=torch.uint8, device=device),
+                   torch.zeros(B, nkv, Lmax, dtype=torch.float32, device=device))
+
+    @property
+    def shape(self):
+        return self.q.shape
+
+    def dequantize(self) -> torch.Tensor:
+        """fp32 [B, nkv, Lmax, hd]: what the kernel reads (tests and tools; not on a hot path)."""
+        return self.q.view(torch.float8_e4m3fn).float() * self.inv[..., None]
+
+
+def decode_attention_kv8_supported(dtype: torch.dtype, nh: int, nkv: int, hd: int) -> bool:
+    """The geometries ``cmb_decode_attn_kv8`` takes: ``decode_attention_supported``'s with bf16 activations only."""
+    return dtype == torch.bfloat16 and decode_attention_supported(dtype, nh, nkv, hd)
+
+
+def kv_quantize_e4m3(src: torch.Tensor, cache: KvCacheE4M3, L_: Optional[int] = None) -> KvCacheE4M3:
+    """The prefill's K or V, bf16 [B, nkv, L, hd] (the ``kv_out`` tensors as they lie: any strides the kernel's 16-byte loads can take, else a contiguous copy
+    is made first), into slots 0 .. L-1 of ``cache``: bytes and factors of ``k_quantize_fp8_rows`` on the same rows.  Nothing else of
+    the cache is touched.  One launch."""
+    L.require_gpu(src, cache.q, cache.inv)
+    B, nkv, Ls, hd = src.shape
+    n = Ls if L_ is None else int(L_)
+    if src.dtype != torch.bfloat16 or cache.q.shape[:2] != (B, nkv) or cache.q.shape[3] != hd \
+            or not 0 <= n <= min(Ls, cache.q.shape[2]):
+        raise L.CambrianAmdError(f"kv_quantize_e4m3: src {tuple(src.shape)} {src.dtype} does not fit the cache "
+                                 f"{tuple(cache.q.shape)} at L = {n}")
+    if src.stride(3) != 1 or src.data_ptr() % 16 or any(src.stride(i) % 8 for i in range(3)):      # the kernel loads 16 bytes at a time
+        src = src.contiguous()
+    L.call("cmb_kv_quantize_e4m3", src.data_ptr(), src.stride(0), src.stride(1), src.stride(2), B, nkv, n, hd, cache.q.data_ptr(),
+           cache.q.stride(0), cache.q.stride(1), cache.q.stride(2), cache.inv.data_ptr(), cache.inv.stride(0), cache.inv.stride(1),
+           device=src.device)
+    return cache
+
+
+def decode_attention_kv8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                         kcache: KvCacheE4M3, vcache: KvCacheE4M3, t: int, key_valid: torch.Tensor,
+                         scale: Optional[float] = None, splits: int = 0) -> torch.Tensor:
+    """``decode_attention`` on e4m3 caches: bf16 q [B, nh*hd], k / v [B, nkv*hd], the caches ``KvCacheE4M3`` of one shape and
+    stride -> out bf16 [B, nh*hd].  Ropes q and k, quantises roped k (rounded to bf16 first) and raw v into slot ``t`` (bytes
+    and factors) and attends to slots 0..t as stored.  Inference only."""
+    L.require_gpu(q, k, v, cos, sin, kcache.q, kcache.inv, vcache.q, vcache.inv, key_valid)
+    if torch.is_grad_enabled() and any(x.requires_grad for x in (q, k, v)):
+        raise L.CambrianAmdError("decode_attention_kv8 has no backward: call it under torch.no_grad()")
+    B, nkv, Lmax, hd = kcache.q.shape
+    nh = q.shape[1] // hd
+    if not decode_attention_kv8_supported(q.dtype, nh, nkv, hd) or q.shape != (B, nh * hd) or k.shape != (B, nkv * hd) \
+            or v.shape != k.shape or vcache.q.shape != kcache.q.shape or not (k.dtype == v.dtype == q.dtype):
+        raise L.CambrianAmdError(f"decode_attention_kv8: unsupported geometry q {tuple(q.shape)} {q.dtype} k {tuple(k.shape)} "
+                                 f"cache {tuple(kcache.q.shape)}")
+    if not 0 <= t < Lmax or key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] < t + 1:
+        raise L.CambrianAmdError("decode_attention_kv8: slot t outside the cache or the key mask")
+    if q.stride(1) != 1 or k.stride(1) != 1 or v.stride(1) != 1 or vcache.q.stride() != kcache.q.stride() \
+            or vcache.inv.stride() != kcache.inv.stride() or key_valid.stride(1) != 1:
+        raise L.CambrianAmdError("decode_attention_kv8: rows of q / k / v and the key mask must be contiguous, and the two "
+                                 "caches of one layout")
+    if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape != (B, hd // 2) or sin.shape != cos.shape \
+            or not cos.is_contiguous() or not sin.is_contiguous():
+        raise L.CambrianAmdError("decode_attention_kv8: cos / sin are the contiguous fp32 [B, hd/2] tables of rope_table")
+    if key_valid.dtype == torch.bool:
+        key_valid = key_valid.view(torch.uint8)
+    elif key_valid.dtype != torch.uint8:
+        raise L.CambrianAmdError("decode_attention_kv8: key_valid is a bool / uint8 mask")
+    scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
+    need = L.load().cmb_decode_attn_ws(B, nh, nkv, hd, t, splits)
+    if need < 0:
+        L.check(int(need), "cmb_decode_attn_ws")
+    ws = _DECODE_WS.get(q.device)
+    if need > 0 and (ws is None or ws.numel() < need):
+        ws = _DECODE_WS[q.device] = torch.empty(int(need), dtype=torch.float32, device=q.device)
+    out = torch.empty((B, nh * hd), dtype=q.dtype, device=q.device)
+    L.call("cmb_decode_attn_kv8", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+           cos.data_ptr(), sin.data_ptr(), kcache.q.data_ptr(), vcache.q.data_ptr(), kcache.q.stride(0), kcache.q.stride(1),
+           kcache.q.stride(2), kcache.inv.data_ptr(), vcache.inv.data_ptr(), kcache.inv.stride(0), kcache.inv.stride(1), B, nh,
+           nkv, hd, t, key_valid.data_ptr(), key_valid.stride(0), scale, splits, L.ptr(ws) if need > 0 else None, int(need),
+           out.data_ptr(), device=q.device)
+    return out
+
+
+def decode_attention_any(q, k, v, cos, sin, kcache, vcache, t: int, key_valid) -> torch.Tensor:
+    """``decode_attention`` or, for ``KvCacheE4M3`` caches, ``decode_attention_kv8``: the one line the decode call sites share."""
+    if isinstance(kcache, KvCacheE4M3):
+        return decode_attention_kv8(q, k, v, cos, sin, kcache, vcache, t, key_valid)
+    return decode_attention(q, k, v, cos, sin, kcache, vcache, t, key_valid)
+
+
 # ================================================================================================
 # decode step of generate(): the layer's linears and the lm_head at M <= 16 rows as weight streams (decode_linear.hip)
 # ================================================================================================
@@ -2565,11 +2682,18 @@ def decode_step_workspace(device, floats: int) -> torch.Tensor:
 
 
 def decode_step(desc, layers, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, t: int, key_valid: torch.Tensor,
-                ws: torch.Tensor, logits: torch.Tensor) -> torch.Tensor:
+                ws: torch.Tensor, logits: torch.Tensor, kv8=None) -> torch.Tensor:
     """One token through every decoder layer and the lm_head: ``desc`` (``lib.DecodeStepDesc``) and ``layers`` (a ctypes
     array of ``lib.DecodeLayer``) describe the model, x bf16 [B, H], cos / sin the fp32 tables of ``rope_table``, ``t`` the
     cache slot, key_valid bool / uint8 [B, >= t+1], ``ws`` from ``decode_step_workspace``; fp32 logits [B, V] are written
-    into ``logits`` (row stride a multiple of 8) and returned.  Inference only."""
+    into ``logits`` (row stride a multiple of 8) and returned.  ``kv8``: None, or (a ctypes array of ``lib.DecodeKv8Factors``,
+    i_sb, i_sh) when ``layers`` hold e4m3 caches and ``desc`` their byte strides (``cmb_decode_step_kv8``).  Inference only."""
+    if kv8 is not None:
+        factors, i_sb, i_sh = kv8
+        L.call("cmb_decode_step_kv8", C.byref(desc), layers, factors, i_sb, i_sh, x.data_ptr(), x.stride(0), cos.data_ptr(),
+               sin.data_ptr(), t, key_valid.data_ptr(), key_valid.stride(0), ws.data_ptr(), ws.numel(), logits.data_ptr(),
+               logits.stride(0), device=x.device)
+        return logits
     L.call("cmb_decode_step", C.byref(desc), layers, x.data_ptr(), x.stride(0), cos.data_ptr(), sin.data_ptr(), t,
            key_valid.data_ptr(), key_valid.stride(0), ws.data_ptr(), ws.numel(), logits.data_ptr(), logits.stride(0),
            device=x.device)

@@ -72,7 +72,8 @@ const char* cmb_version(void);
  * (cmb_decode_step, cmb_decode_step_ws, cmb_decode_next and the two descriptors), and then the sampled selection
  * (cmb_decode_sample), and then beam search (cmb_decode_beam, cmb_decode_beam_state_bytes, cmb_decode_beam_reorder), and then the MXFP4
  * decode-step linear (cmb_quantize_mxfp4_rows, cmb_decode_linear_fp4, cmb_decode_linear_fp4_supported,
- * cmb_decode_linear_fp4_plan, and the value 2 of cmb_decode_step_desc.fp8) were
+ * cmb_decode_linear_fp4_plan, and the value 2 of cmb_decode_step_desc.fp8), and then the e4m3 K / V cache of the decode steps
+ * (cmb_kv_quantize_e4m3, cmb_decode_attn_kv8, cmb_decode_step_kv8 and cmb_decode_kv8_factors) were
  * ADDED under revision 13: no existing
  * signature or layout changed, which is the rule for a bump, so a binding written against 13 still calls everything it
  * knows correctly.  Bindings must compare it
@@ -835,6 +836,57 @@ int cmb_decode_step(const cmb_decode_step_desc* d, const cmb_decode_layer* layer
                     const float* cos_t, const float* sin_t, int64_t t, const uint8_t* key_valid, int64_t kv_ld, float* ws,
                     int64_t ws_floats, float* logits, int64_t logits_ld, void* stream);
 int64_t cmb_decode_step_ws(int32_t B, int32_t H, int32_t I, int32_t nh, int32_t nkv, int32_t hd, int64_t t_max);
+/* The K / V cache of the decode steps in one byte per element (opt-in; it changes numerics).
+ * Format.  kcache / vcache: uint8 [B, nkv, Lmax, hd], OCP e4m3fn bytes, with BYTE strides c_sb / c_sh / c_st (last dimension
+ * contiguous; multiples of 16, c_st >= hd) and one fp32 factor per (row, KV head, slot): k_inv / v_inv [B, nkv, Lmax] with
+ * element strides i_sb / i_sh and slot stride 1 — 1 + 4 / hd bytes per element.  A cache row of hd values is quantised by
+ * cmb_quantize_fp8_rows' rule, expression for expression: amax = max |x|; byte = e4m3(clamp(x * (448 / amax), +-448)), round to
+ * nearest even; factor = amax / 448; a zero row takes scale and factor 1.  The NaN codes 0x7F / 0xFF are never written.  The
+ * value of an entry is e4m3(byte) * factor.
+ *
+ * cmb_kv_quantize_e4m3: the prefill's K (or V) into slots 0 .. L-1 of such a cache, one launch per tensor.  src: bf16
+ * [B, nkv, L, hd] with ELEMENT strides s_sb / s_sh / s_st (last dimension contiguous).  Bytes and factors are those
+ * cmb_quantize_fp8_rows gives for the same rows, bit for bit, and those cmb_decode_attn_kv8 writes for the same bf16 values.
+ * Slots >= L, and bytes between a row's hd bytes and the next row when c_st > hd, are neither read nor written.  A streaming
+ * kernel (a row across a group of lanes, several rows per wave), deterministic.
+ * CMB_ERR_BAD_ARG: a NULL pointer, hd outside 16 .. 128 or hd % 16 != 0, a negative count or stride, s_st or c_st < hd;
+ * CMB_ERR_ALIGNMENT: src or cache not 16-byte aligned, inv not 4-byte aligned, a source stride that is no multiple of 8
+ * elements, a cache stride that is no multiple of 16 bytes.  B, nkv or L == 0 is CMB_OK.
+ *
+ * cmb_decode_attn_kv8: cmb_decode_attn's step on that cache.  q / k / v (bf16, row strides in elements), cos_t / sin_t,
+ * key_valid / kv_ld, slot t, scale, splits / ws / ws_floats (cmb_decode_attn_plan and cmb_decode_attn_ws serve it unchanged),
+ * out (bf16 [B, nh*hd]) and the geometry rule (hd 64 | 96 | 128, nh % nkv == 0, nh / nkv <= 8; B, nkv <= 65535) are that
+ * function's; activations are bf16 only.  Slots 0 .. t-1 are read as e4m3(byte) * factor.  The new token's k is roped and
+ * rounded to bf16 (the value a bf16 cache would hold), that row and the raw v row are quantised by the rule above and stored
+ * — bytes and both factors — into slot t, and the step attends to the dequantised slot, which is what later steps read.  A
+ * slot that is not attendable (masked, or past t) may hold any bytes and factors, NaN included; slots past t are not read.
+ * Deterministic: the same bits on every run, in out and in the caches.
+ * CMB_ERR_BAD_ARG: a NULL pointer (ws may be NULL when the call runs unsplit), a geometry outside the rule, t < 0, kv_ld < t + 1,
+ * c_st < hd, a negative stride, ws_floats below the need; CMB_ERR_ALIGNMENT: q, k, v, the caches or out not 16-byte
+ * aligned, a factor array not 4-byte aligned, a q / k / v row stride that is no multiple of 8 elements, a cache stride that is
+ * no multiple of 16 bytes.  Everything is checked before any launch; B == 0 is CMB_OK.
+ *
+ * cmb_decode_step_kv8: cmb_decode_step on such caches.  layers[l].kcache / vcache are the byte caches, d->c_sb / c_sh / c_st
+ * their BYTE strides (multiples of 16, c_st >= hd), factors[l] (HOST memory, one per layer) the layer's factor arrays with
+ * strides i_sb / i_sh.  Launch 1 of every layer is cmb_decode_attn_kv8; everything else, all three values of d->fp8 included,
+ * is cmb_decode_step's, by the same code; cmb_decode_step_ws gives the workspace.  Statuses as cmb_decode_step, plus
+ * CMB_ERR_BAD_ARG for factors == NULL, a NULL factor array or a negative factor stride and CMB_ERR_ALIGNMENT for a factor array
+ * that is not 4-byte aligned or a cache stride that is no multiple of 16 bytes. */
+typedef struct cmb_decode_kv8_factors {
+  float* k_inv; float* v_inv;          /* slot t of both is written by the step */
+} cmb_decode_kv8_factors;
+int cmb_kv_quantize_e4m3(const void* src, int64_t s_sb, int64_t s_sh, int64_t s_st, int64_t B, int32_t nkv, int64_t L, int32_t hd,
+                         void* cache, int64_t c_sb, int64_t c_sh, int64_t c_st, float* inv, int64_t i_sb, int64_t i_sh,
+                         void* stream);
+int cmb_decode_attn_kv8(const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v, int64_t v_ld,
+                        const float* cos_t, const float* sin_t, void* kcache, void* vcache, int64_t c_sb, int64_t c_sh,
+                        int64_t c_st, float* k_inv, float* v_inv, int64_t i_sb, int64_t i_sh, int64_t B, int32_t nh, int32_t nkv,
+                        int32_t hd, int64_t t, const uint8_t* key_valid, int64_t kv_ld, float scale, int32_t splits, float* ws,
+                        int64_t ws_floats, void* out, void* stream);
+int cmb_decode_step_kv8(const cmb_decode_step_desc* d, const cmb_decode_layer* layers, const cmb_decode_kv8_factors* factors,
+                        int64_t i_sb, int64_t i_sh, const void* x, int64_t x_ld, const float* cos_t, const float* sin_t, int64_t t,
+                        const uint8_t* key_valid, int64_t kv_ld, float* ws, int64_t ws_floats, float* logits, int64_t logits_ld,
+                        void* stream);
 /* Greedy token selection and the next step's inputs in one launch (+ the cmb_rope_table launch), one workgroup per row b:
  *   nxt = argmax(logits[b, 0..V))       fp32 logits, row stride logits_ld; ties: the lowest index; a NaN is greater than
  *                                       every number and the first NaN wins (torch.argmax's rules); -0 == +0
