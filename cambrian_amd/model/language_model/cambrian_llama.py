@@ -313,6 +313,47 @@ def decode_layer_fused(layer, x, cos, sin, kcache, vcache, t, key_mask, w_qkv, w
     return ops.decode_linear(inner, w_down, residual=x2).reshape(B, 1, -1)
 
 
+def lookup_mask(key_mask: torch.Tensor, t0: int, Q: int) -> torch.Tensor:
+    """bool [Q, t0 + Q]: what token j of a multi-token step may attend — cached slots s < t0 under ``key_mask[0]``, the step's
+    own slots t0 .. t0 + j always (``cmb_decode_attn_multi``'s rule; columns >= t0 of ``key_mask`` are not looked at)."""
+    m = torch.empty(Q, t0 + Q, dtype=torch.bool, device=key_mask.device)
+    m[:, :t0] = key_mask[0, :t0]
+    m[:, t0:] = torch.ones(Q, Q, dtype=torch.bool, device=key_mask.device).tril()
+    return m
+
+
+def decode_layer_fused_multi(layer, x, cos, sin, kcache, vcache, t0, key_mask, w, quant=None, fp4=False):
+    """``decode_layer_fused`` for Q consecutive tokens of ONE sequence, x [Q, 1, H]: the same five launches with
+    ``ops.decode_attention_multi`` in the middle.  ``w``: the four bf16 weights; ``quant``: their e4m3 (``fp4``: MXFP4) copies,
+    streamed instead when given."""
+    attn = layer.self_attn
+    Q = x.shape[0]
+    nq, nk = attn.nh * attn.hd, attn.nkv * attn.hd
+    n1, n2 = layer.input_layernorm, layer.post_attention_layernorm
+    if quant is None:
+        lin, mats = ops.decode_linear, [(wi,) for wi in w]
+    else:
+        lin, mats = (ops.decode_linear_fp4 if fp4 else ops.decode_linear_fp8), quant
+    x2 = x.reshape(Q, -1)
+    row = lin(x2, *mats[0], norm_weight=n1.weight, eps=n1.variance_epsilon)
+    o = ops.decode_attention_multi(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t0, key_mask)
+    x2 = lin(o, *mats[1], residual=x2)
+    inner = lin(x2, *mats[2], norm_weight=n2.weight, eps=n2.variance_epsilon, act="swiglu")
+    return lin(inner, *mats[3], residual=x2).reshape(Q, 1, -1)
+
+
+def decode_multi_fused_or_none(layer, x, cos, sin, kcache, vcache, t0, key_mask, fp8, fp4):
+    """The five-launch arm of a layer's ``decode_multi``, or None where it does not apply: ``decode``'s own five-launch
+    conditions for Q rows (``decode_operands``), bf16 caches and a geometry ``ops.decode_attention_multi`` takes."""
+    a = layer.self_attn
+    if isinstance(kcache, ops.KvCacheE4M3) or not ops.decode_attention_multi_supported(x.dtype, a.nh, a.nkv, a.hd, x.shape[0]):
+        return None
+    found = layer.decode_operands(x, fp8, fp4) if fp4 else layer.decode_operands(x, fp8)
+    if found is None:
+        return None
+    return decode_layer_fused_multi(layer, x, cos, sin, kcache, vcache, t0, key_mask, found[0], found[1], fp4=bool(fp4))
+
+
 class LlamaAttention(nn.Module):
     def __init__(self, cfg, device, dtype):
         super().__init__()
@@ -387,6 +428,19 @@ class LlamaAttention(nn.Module):
                                            enable_gqa=self.nkv != self.nh)
         return self.o_proj(o.transpose(1, 2).reshape(B, 1, self.nh * self.hd))
 
+    def decode_multi(self, x, cos, sin, kcache, vcache, t0: int, key_mask):
+        """Q consecutive tokens of ONE sequence against its cache, the plain torch body: x [Q,1,H]; cos / sin [Q, hd/2] at the
+        tokens' positions; caches [1,nkv,Lmax,hd], slots t0 .. t0+Q-1 are filled here; token j attends under ``lookup_mask``.
+        (The kernel form is the layer's: ``decode_layer_fused_multi``.)"""
+        Q = x.shape[0]
+        q = ops.rope(self.q_proj(x).view(Q, self.nh, self.hd), cos, sin)
+        k = ops.rope(self.k_proj(x).view(Q, self.nkv, self.hd), cos, sin)
+        kcache[0, :, t0:t0 + Q] = k.transpose(0, 1)
+        vcache[0, :, t0:t0 + Q] = self.v_proj(x).view(Q, self.nkv, self.hd).transpose(0, 1)
+        o = F.scaled_dot_product_attention(q.transpose(0, 1)[None], kcache[:, :, :t0 + Q], vcache[:, :, :t0 + Q],
+                                           attn_mask=lookup_mask(key_mask, t0, Q)[None, None], enable_gqa=self.nkv != self.nh)
+        return self.o_proj(o[0].transpose(0, 1).reshape(Q, 1, self.nh * self.hd))
+
 
 class LlamaDecoderLayer(nn.Module):
     def __init__(self, cfg, device, dtype):
@@ -457,6 +511,16 @@ class LlamaDecoderLayer(nn.Module):
                                                               (mlp.down_proj, "_w_fp8", w[3], None)))
                 return decode_layer_fused(self, x, cos, sin, kcache, vcache, t, key_mask, *w, fp8=q8)
         x = x + self.self_attn.decode(self.input_layernorm(x), cos, sin, kcache, vcache, t, key_mask)
+        return x + self.mlp(self.post_attention_layernorm(x))
+
+    def decode_multi(self, x, cos, sin, kcache, vcache, t0, key_mask, fp8=False, fp4=False):
+        """``decode`` for Q consecutive tokens of ONE sequence, x [Q, 1, H] (the verify step of prompt-lookup decoding): five
+        launches around ``ops.decode_attention_multi`` where ``decode`` itself would take five launches for Q rows, else the
+        modules' own projections and SDPA."""
+        out = decode_multi_fused_or_none(self, x, cos, sin, kcache, vcache, t0, key_mask, fp8, fp4)
+        if out is not None:
+            return out
+        x = x + self.self_attn.decode_multi(self.input_layernorm(x), cos, sin, kcache, vcache, t0, key_mask)
         return x + self.mlp(self.post_attention_layernorm(x))
 
 
@@ -879,7 +943,7 @@ class DecodeStepPlan:
 
 def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: int = 16, do_sample: bool = False,
               temperature: float = 1.0, eos_token_id=None, attention_mask=None, position_ids=None, top_p=None, top_k=None,
-              num_beams: int = 1, **kwargs):
+              num_beams: int = 1, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, _draft_fn=None, **kwargs):
     """cambrian_llama.py:437-483: ``generate(input_ids, images=, image_sizes=)`` of the eval harness
     (eval/eval/*/…_eval.py, e.g. gqa_eval.py:108-117: do_sample / temperature / top_p / num_beams / max_new_tokens /
     use_cache).  Prefill = the eval branch of prepare_inputs_labels_for_multimodal + the decoder with the per-sample in-LLM
@@ -889,7 +953,11 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
     GenerationMixin; what this loop does not implement RAISES instead of being dropped: beam search (``num_beams > 1``) unless
     it is switched on (``config.decode_beam_search`` / CAMBRIAN_AMD_DECODE_BEAM=1: ``_beam_search``, HF's beam search without
     sampling, length penalty 1, no early stopping, one returned sequence), ``inputs_embeds`` (the reference raises too,
-    cambrian_llama.py:447-448) and any keyword it does not know."""
+    cambrian_llama.py:447-448) and any keyword it does not know.
+    ``prompt_lookup_num_tokens`` (1 .. 15; None / 0 = off) with ``max_matching_ngram_size`` (default 2): HF's prompt-lookup
+    assisted decoding for greedy decoding of ONE prompt (``_lookup_loop``): drafts by n-gram lookup in the prompt and the
+    output so far, verified in one multi-token step; the call leaves ``self.lookup_stats``.  ``_draft_fn`` (private) stands in
+    for ``lookup.ngram_draft``."""
     if "inputs_embeds" in kwargs:
         raise NotImplementedError("`inputs_embeds` is not supported")          # cambrian_llama.py:447-448
     beams = 1 if num_beams is None else int(num_beams)
@@ -910,6 +978,8 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
         if k not in _GENERATE_ACCEPTED_NOOPS or (ok is not None and v not in ok):
             raise ValueError(f"generate(): unsupported argument {k}={v!r} (cambrian_amd implements greedy / temperature / "
                              "top_k / top_p decoding with a K/V cache)")
+    lookup = _lookup_args(self, inputs, prompt_lookup_num_tokens, max_matching_ngram_size, do_sample, temperature, beams)
+    prompt_ids, prompt_mask = inputs, attention_mask        # what the lookup drafts from (the multimodal prefill replaces both)
     with torch.no_grad():
         model = self.model
         if images is not None:
@@ -956,6 +1026,9 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
         fmt = ops.decode_weight_format(self.config)            # e4m3 or MXFP4 weight stream, opt-in; both on raises
         fp8, fp4 = fmt == "fp8", fmt == "fp4"
         low = {"fp4": True} if fp4 else {}                      # (the fp8 mode's calls stay what they were)
+        if lookup is not None:
+            return _lookup_loop(self, logits, caches, key_mask, n_tok, L, int(max_new_tokens), eos_token_id, prompt_ids,
+                                prompt_mask, lookup, _draft_fn, fp8, fp4, hd, theta)
         plan = None                                                                       # one library call per token, opt-in
         if max_new_tokens > 1 and ops.decode_step_enabled(getattr(self.config, "decode_step_fused", False)):
             plan = DecodeStepPlan.build(self, B, caches, Lmax - 1, fp8, **low)
@@ -991,6 +1064,98 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
                 x = layer.decode(x, cos, sin, kc, vc, t, key_mask, fp8=fp8, **low)      # [B, Lmax]: the step reads columns 0..t
             logits = _decode_logits(self, x, fp8, **low)
         return torch.stack(out_ids, 1)
+
+
+def _lookup_args(self, inputs, num_tokens, max_ngram, do_sample, temperature, beams):
+    """``generate``'s prompt-lookup arguments, checked before the model is touched: None when the mode is off, else
+    (num_tokens, max_ngram)."""
+    if max_ngram is not None and (isinstance(max_ngram, bool) or int(max_ngram) != max_ngram or int(max_ngram) < 1):
+        raise ValueError(f"generate(max_matching_ngram_size={max_ngram!r}): has to be an integer >= 1")
+    if num_tokens is None or (not isinstance(num_tokens, bool) and num_tokens == 0):
+        return None
+    if isinstance(num_tokens, bool) or int(num_tokens) != num_tokens or not 1 <= int(num_tokens) < ops.DECODE_LOOKUP_MAX_ROWS:
+        raise ValueError(f"generate(prompt_lookup_num_tokens={num_tokens!r}): has to be an integer in 1 .. "
+                         f"{ops.DECODE_LOOKUP_MAX_ROWS - 1} (a step verifies the last token and the drafts in at most "
+                         f"{ops.DECODE_LOOKUP_MAX_ROWS} rows), or None / 0 for off")
+    if inputs is not None and inputs.dim() == 2 and inputs.shape[0] != 1:
+        raise ValueError(f"generate(prompt_lookup_num_tokens=...): batch size 1 only, got {inputs.shape[0]} (HF's assisted "
+                         "decoding has the same rule)")
+    if do_sample and temperature > 0:
+        raise NotImplementedError("generate(prompt_lookup_num_tokens=..., do_sample=True): prompt-lookup decoding is greedy only")
+    if beams > 1:
+        raise NotImplementedError(f"generate(prompt_lookup_num_tokens=..., num_beams={beams}): prompt-lookup decoding does "
+                                  "not combine with beam search")
+    if ops.decode_kv_fp8_enabled(getattr(getattr(self, "config", None), "decode_kv_fp8", False)):
+        raise NotImplementedError("generate(prompt_lookup_num_tokens=...): the multi-token step reads bf16 K / V caches; switch "
+                                  "the e4m3 K / V cache off (config.decode_kv_fp8 / CAMBRIAN_AMD_DECODE_KV_FP8)")
+    return int(num_tokens), 2 if max_ngram is None else int(max_ngram)
+
+
+def lookup_step(self, ids, caches, t0: int, n_tok0: int, key_mask, fp8: bool = False, fp4: bool = False) -> torch.Tensor:
+    """fp32 logits [Q, V] of Q consecutive tokens ``ids`` [Q] of ONE sequence in one step: embeddings, the RoPE table at
+    positions n_tok0 .. n_tok0 + Q - 1, every layer's ``decode_multi`` (K / V of token j into cache slot t0 + j), final norm
+    + lm_head.  Row j is the model's distribution after ids[: j + 1]."""
+    model = self.model
+    Q = ids.shape[0]
+    hd = model.layers[0].self_attn.hd
+    theta = float(getattr(self.config, "rope_theta", 10000.0))
+    pos = torch.arange(n_tok0, n_tok0 + Q, dtype=torch.int64, device=ids.device)
+    cos, sin = ops.rope_table(pos[:, None], hd, theta)
+    x = model.embed_tokens(ids)[:, None, :].to(model.llm_dtype)
+    low = {"fp4": True} if fp4 else {}
+    for layer, (kc, vc) in zip(model.layers, caches):
+        x = layer.decode_multi(x, cos, sin, kc, vc, t0, key_mask, fp8=fp8, **low)
+    return _decode_logits(self, x, fp8, **low)
+
+
+def _lookup_loop(self, logits, caches, key_mask, n_tok, L: int, max_new_tokens: int, eos_token_id, prompt_ids, prompt_mask,
+                 lookup, draft_fn, fp8: bool, fp4: bool, hd: int, theta: float):
+    """Greedy decoding of one prompt with prompt-lookup drafts (HF ``generate(prompt_lookup_num_tokens=...)``).  Every step
+    drafts up to ``num_tokens`` ids from the prompt and the output so far; with d drafts it runs ``lookup_step`` on
+    [last token, drafts] (Q = d + 1 rows), takes the argmax of every row — one host read — and emits the leading drafts the
+    model reproduced plus the model's own next token.  K / V of rejected drafts stay in their slots, closed in the key mask,
+    and are overwritten by the next step.  A step without drafts is the per-launch loop's step, ``layer.decode``.  Drafts are
+    cut to the remaining budget, so no slot past L + max_new_tokens - 2 (the per-launch loop's last) is written."""
+    from .lookup import accept, ngram_draft
+    model = self.model
+    num_tokens, max_ngram = lookup
+    draft_fn = ngram_draft if draft_fn is None else draft_fn
+    a0 = model.layers[0].self_attn
+    max_rows = min(ops.DECODE_LOOKUP_MAX_ROWS, 64 // max(1, a0.nh // a0.nkv))
+    vocab = logits.shape[1]
+    eos = None if eos_token_id is None else int(eos_token_id)
+    src = prompt_ids[0] if prompt_mask is None else prompt_ids[0][prompt_mask[0].bool()]
+    src = [int(i) for i in src.tolist()]
+    n0 = int(n_tok[0])
+    low = {"fp4": True} if fp4 else {}
+    out = [int(logits.argmax(-1)[0])]
+    stats = {"steps": 0, "drafted": 0, "accepted": 0}
+    while len(out) < max_new_tokens and not (eos is not None and out[-1] == eos):
+        step = len(out) - 1
+        t = L + step                                   # slot of the last emitted token, which this step feeds
+        room = min(num_tokens, max_rows - 1, max_new_tokens - len(out) - 1)
+        draft = [int(i) for i in draft_fn(src + out, room, max_ngram, vocab, eos)][:room] if room > 0 else []
+        stats["steps"] += 1
+        if not draft:
+            key_mask[:, t] = True
+            cos, sin = ops.rope_table((n_tok + step)[:, None], hd, theta)
+            x = model.embed_tokens(torch.tensor([out[-1]], dtype=torch.int64, device=logits.device))[:, None, :].to(model.llm_dtype)
+            for layer, (kc, vc) in zip(model.layers, caches):
+                x = layer.decode(x, cos, sin, kc, vc, t, key_mask, fp8=fp8, **low)
+            out.append(int(_decode_logits(self, x, fp8, **low).argmax(-1)[0]))
+            continue
+        ids = torch.tensor([out[-1]] + draft, dtype=torch.int64, device=logits.device)
+        picked = lookup_step(self, ids, caches, t, n0 + step, key_mask, fp8, fp4).argmax(-1).tolist()
+        a = accept(draft, picked)
+        key_mask[:, t:t + a + 1] = True
+        stats["drafted"] += len(draft)
+        stats["accepted"] += a
+        new = draft[:a] + [int(picked[a])]
+        if eos is not None and eos in new:
+            new = new[:new.index(eos) + 1]
+        out.extend(new)
+    self.lookup_stats = stats
+    return torch.tensor([out], dtype=torch.int64, device=logits.device)
 
 
 def _kv8_wanted(self, dev, kv_out) -> bool:

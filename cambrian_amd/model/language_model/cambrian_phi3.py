@@ -33,7 +33,8 @@ except Exception:  # pragma: no cover
 from ... import lib as L
 from ... import ops
 from .cambrian_llama import (CambrianLlamaForCausalLM, CambrianLlamaModel, HipRMSNorm, _down_proj, _frozen_plain, _lin,
-                             decode_fp4_copies, decode_fp8_copies, decode_layer_fused, decode_linear_weights, use_decode_kernel)
+                             decode_fp4_copies, decode_fp8_copies, decode_layer_fused, decode_linear_weights, decode_multi_fused_or_none,
+                             lookup_mask, use_decode_kernel)
 
 
 class CambrianConfig(Phi3Config):
@@ -110,6 +111,16 @@ class Phi3Attention(nn.Module):
                                            attn_mask=key_mask[:, None, None, :], enable_gqa=self.nkv != self.nh)
         return self.o_proj(o.transpose(1, 2).reshape(B, 1, self.nh * self.hd))
 
+    def decode_multi(self, x, cos, sin, kcache, vcache, t0: int, key_mask):
+        """Q consecutive tokens of ONE sequence against its cache, the plain torch body (see LlamaAttention.decode_multi)."""
+        Q = x.shape[0]
+        q, k, v = ops.qkv_rope(self.qkv_proj(x.transpose(0, 1)).contiguous(), cos, sin, self.nh, self.nkv, self.hd)   # [1,h,Q,hd]
+        kcache[:, :, t0:t0 + Q] = k
+        vcache[:, :, t0:t0 + Q] = v
+        o = F.scaled_dot_product_attention(q, kcache[:, :, :t0 + Q], vcache[:, :, :t0 + Q],
+                                           attn_mask=lookup_mask(key_mask, t0, Q)[None, None], enable_gqa=self.nkv != self.nh)
+        return self.o_proj(o[0].transpose(0, 1).reshape(Q, 1, self.nh * self.hd))
+
 
 class Phi3DecoderLayer(nn.Module):
     def __init__(self, cfg, device, dtype):
@@ -146,6 +157,14 @@ class Phi3DecoderLayer(nn.Module):
                         (m, "_w_fp8", wi, "swiglu" if m is mlp.gate_up_proj else None) for m, wi in zip(mods, w)))
                 return decode_layer_fused(self, x, cos, sin, kcache, vcache, t, key_mask, *w, fp8=q8)
         x = x + self.self_attn.decode(self.input_layernorm(x), cos, sin, kcache, vcache, t, key_mask)
+        return x + self.mlp(self.post_attention_layernorm(x))
+
+    def decode_multi(self, x, cos, sin, kcache, vcache, t0, key_mask, fp8=False, fp4=False):
+        """``decode`` for Q consecutive tokens of ONE sequence (see LlamaDecoderLayer.decode_multi)."""
+        out = decode_multi_fused_or_none(self, x, cos, sin, kcache, vcache, t0, key_mask, fp8, fp4)
+        if out is not None:
+            return out
+        x = x + self.self_attn.decode_multi(self.input_layernorm(x), cos, sin, kcache, vcache, t0, key_mask)
         return x + self.mlp(self.post_attention_layernorm(x))
 
     def decode_operands(self, x, fp8=False, fp4=False):

@@ -2201,6 +2201,75 @@ def decode_attention_enabled() -> bool:
 
 
 # ------------------------------------------------------------------------------------------------
+# the same step for Q consecutive new tokens per sequence (decode_attn_multi.hip): the verify step of prompt-lookup decoding
+# ------------------------------------------------------------------------------------------------
+DECODE_LOOKUP_MAX_ROWS = 16     # rows of a multi-token step: the last token plus at most 15 drafts
+
+
+def decode_attention_multi_supported(dtype: torch.dtype, nh: int, nkv: int, hd: int, Q: int) -> bool:
+    """The geometries ``cmb_decode_attn_multi`` takes: bf16, head_dim 64 / 96 / 128, G = nh / nkv <= 8, 1 <= Q <= 16 and
+    Q * G <= 64."""
+    return (dtype == torch.bfloat16 and decode_attention_supported(dtype, nh, nkv, hd)
+            and 1 <= Q <= DECODE_LOOKUP_MAX_ROWS and Q * (nh // nkv) <= 64)
+
+
+def decode_attention_multi_plan(B: int, nkv: int, t0: int, Q: int, splits: int = 0) -> Tuple[int, int]:
+    """(splits, chunk) of a Q-token step over cache slots 0 .. t0 + Q - 1, ``splits * chunk >= t0 + Q > (splits - 1) * chunk``;
+    the last chunk holds the step's own slots.  ``splits`` = 0: the library's choice, a pure function of (B, nkv, t0 + Q, CU
+    count)."""
+    s, ch = C.c_int32(0), C.c_int64(0)
+    L.check(L.load().cmb_decode_attn_multi_plan(B, nkv, t0, Q, splits, C.byref(s), C.byref(ch), None),
+            "cmb_decode_attn_multi_plan")
+    return s.value, ch.value
+
+
+def decode_attention_multi(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                           kcache: torch.Tensor, vcache: torch.Tensor, t0: int, key_valid: torch.Tensor,
+                           scale: Optional[float] = None, splits: int = 0) -> torch.Tensor:
+    """Q consecutive new tokens per sequence: bf16 q [B*Q, nh*hd], k / v [B*Q, nkv*hd] (un-roped rows of the projections, row
+    b*Q + j = token j of sequence b; views into one packed row are fine), cos / sin fp32 [B*Q, hd/2], k / v caches
+    [B, nkv, Lmax, hd] -> out [B*Q, nh*hd].  Ropes q and k, stores roped k and v of token j into cache slot ``t0 + j`` and lets
+    token j attend to slots 0 .. t0 + j: cached slots under ``key_valid`` (bool / uint8 [B, >= t0+Q], columns >= t0 are not
+    read), the step's own slots always.  Inference only: there is no backward."""
+    L.require_gpu(q, k, v, cos, sin, kcache, vcache, key_valid)
+    if torch.is_grad_enabled() and any(x.requires_grad for x in (q, k, v, kcache, vcache)):
+        raise L.CambrianAmdError("decode_attention_multi has no backward: call it under torch.no_grad()")
+    B, nkv, Lmax, hd = kcache.shape
+    nh = q.shape[1] // hd
+    Q = q.shape[0] // B if B > 0 else 0
+    dt = q.dtype
+    if not decode_attention_multi_supported(dt, nh, nkv, hd, Q) or q.shape != (B * Q, nh * hd) or k.shape != (B * Q, nkv * hd) \
+            or v.shape != k.shape or vcache.shape != kcache.shape or not (k.dtype == v.dtype == kcache.dtype == vcache.dtype == dt):
+        raise L.CambrianAmdError(f"decode_attention_multi: unsupported geometry q {tuple(q.shape)} k {tuple(k.shape)} "
+                                 f"cache {tuple(kcache.shape)} {dt}")
+    if not 0 <= t0 or t0 + Q > Lmax or key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] < t0 + Q:
+        raise L.CambrianAmdError("decode_attention_multi: slots t0 .. t0 + Q - 1 outside the cache or the key mask")
+    if q.stride(1) != 1 or k.stride(1) != 1 or v.stride(1) != 1 or kcache.stride(3) != 1 \
+            or vcache.stride() != kcache.stride() or key_valid.stride(1) != 1:
+        raise L.CambrianAmdError("decode_attention_multi: rows of q / k / v, the caches and the key mask must be contiguous")
+    if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape != (B * Q, hd // 2) or sin.shape != cos.shape \
+            or not cos.is_contiguous() or not sin.is_contiguous():
+        raise L.CambrianAmdError("decode_attention_multi: cos / sin are the contiguous fp32 [B*Q, hd/2] tables of rope_table")
+    if key_valid.dtype == torch.bool:
+        key_valid = key_valid.view(torch.uint8)
+    elif key_valid.dtype != torch.uint8:
+        raise L.CambrianAmdError("decode_attention_multi: key_valid is a bool / uint8 mask")
+    scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
+    need = L.load().cmb_decode_attn_multi_ws(B, nh, nkv, hd, Q, t0, splits)
+    if need < 0:
+        L.check(int(need), "cmb_decode_attn_multi_ws")
+    ws = _DECODE_WS.get(q.device)
+    if need > 0 and (ws is None or ws.numel() < need):
+        ws = _DECODE_WS[q.device] = torch.empty(int(need), dtype=torch.float32, device=q.device)
+    out = torch.empty((B * Q, nh * hd), dtype=dt, device=q.device)
+    L.call("cmb_decode_attn_multi", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+           cos.data_ptr(), sin.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), kcache.stride(0), kcache.stride(1),
+           kcache.stride(2), B, nh, nkv, hd, Q, t0, key_valid.data_ptr(), key_valid.stride(0), scale, splits,
+           L.ptr(ws) if need > 0 else None, int(need), out.data_ptr(), device=q.device)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # the same step on an e4m3 K / V cache (decode_attn_kv8.hip): one byte per element plus one fp32 factor per cache row, about
 # half the cache's memory and stream.  Opt-in (``config.decode_kv_fp8`` / CAMBRIAN_AMD_DECODE_KV_FP8): it changes numerics
 # (profiles/decode_kv8.md has what was measured).

@@ -73,7 +73,8 @@ const char* cmb_version(void);
  * (cmb_decode_sample), and then beam search (cmb_decode_beam, cmb_decode_beam_state_bytes, cmb_decode_beam_reorder), and then the MXFP4
  * decode-step linear (cmb_quantize_mxfp4_rows, cmb_decode_linear_fp4, cmb_decode_linear_fp4_supported,
  * cmb_decode_linear_fp4_plan, and the value 2 of cmb_decode_step_desc.fp8), and then the e4m3 K / V cache of the decode steps
- * (cmb_kv_quantize_e4m3, cmb_decode_attn_kv8, cmb_decode_step_kv8 and cmb_decode_kv8_factors) were
+ * (cmb_kv_quantize_e4m3, cmb_decode_attn_kv8, cmb_decode_step_kv8 and cmb_decode_kv8_factors), and then the multi-token
+ * decode attention of prompt-lookup decoding (cmb_decode_attn_multi, cmb_decode_attn_multi_ws, cmb_decode_attn_multi_plan) were
  * ADDED under revision 13: no existing
  * signature or layout changed, which is the rule for a bump, so a binding written against 13 still calls everything it
  * knows correctly.  Bindings must compare it
@@ -887,6 +888,34 @@ int cmb_decode_step_kv8(const cmb_decode_step_desc* d, const cmb_decode_layer* l
                         int64_t i_sb, int64_t i_sh, const void* x, int64_t x_ld, const float* cos_t, const float* sin_t, int64_t t,
                         const uint8_t* key_valid, int64_t kv_ld, float* ws, int64_t ws_floats, float* logits, int64_t logits_ld,
                         void* stream);
+/* cmb_decode_attn for Q consecutive new tokens per cache row (the verify step of prompt-lookup speculative decoding in
+ * generate()): bf16 only, no dtype argument.  q [B*Q, nh*hd], k / v [B*Q, nkv*hd] (un-roped rows of the packed projection, row
+ * strides in elements), cos_t / sin_t fp32 [B*Q, hd/2], out [B*Q, nh*hd] contiguous; row b*Q + j is token j of sequence b.
+ * Roped k (fp32 rotate-half RoPE, then rounded to bf16) and raw v (bit for bit) of row (b, j) are stored into slot t0 + j of
+ * cache row b.  Query (b, j) attends slots s <= t0 + j: cached slots s < t0 under key_valid[b][s], the step's own slots
+ * t0 .. t0 + j always (cmb_decode_attn's "slot t is open" rule, extended); bytes of key_valid at slots >= t0 are not read,
+ * slots past t0 + Q - 1 are neither read nor written, and a masked or unwritten slot may hold anything, NaN included.  No
+ * workgroup reads from the cache a slot the launch writes: the new keys and values come from the arguments, the attended new
+ * k being the value as stored.
+ * hd 64 | 96 | 128; nh % nkv == 0, G = nh / nkv <= 8; 1 <= Q <= 16 and Q * G <= 64; B, nkv <= 65535; pointers and strides
+ * 16-byte aligned.  fp32 scores, running max / sum and accumulators; both products run on the bf16 MFMA (q after RoPE and the
+ * softmax weights are rounded to bf16), so Q = 1 agrees with cmb_decode_attn within bf16 rounding, not in bits.  One workgroup
+ * per (batch row, KV head, chunk of keys) holds all Q * G query rows: the cache is read once per launch.  splits / ws /
+ * ws_floats as cmb_decode_attn, planned over slots 0 .. t0 + Q - 1 (splits == 0: a pure function of (B, nkv, t0 + Q, CU
+ * count); splits * chunk >= t0 + Q > (splits - 1) * chunk; the last chunk holds the step's own slots); partials are merged in
+ * chunk order by a second small launch: no atomics, the same bits on every run.
+ * Statuses and check order of cmb_decode_attn, everything before any launch: CMB_ERR_BAD_ARG for a NULL pointer (ws may be
+ * NULL when the call runs unsplit), a geometry or Q outside the rule, B or nkv out of range, t0 < 0, kv_ld < t0 + Q, ws_floats
+ * below the need; CMB_ERR_ALIGNMENT; B == 0 is CMB_OK.  cmb_decode_attn_multi_ws: floats of `ws` (0 when unsplit) or a negative
+ * status; both queries are host functions. */
+int cmb_decode_attn_multi(const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v, int64_t v_ld,
+                          const float* cos_t, const float* sin_t, void* kcache, void* vcache, int64_t c_sb, int64_t c_sh,
+                          int64_t c_st, int64_t B, int32_t nh, int32_t nkv, int32_t hd, int32_t Q, int64_t t0,
+                          const uint8_t* key_valid, int64_t kv_ld, float scale, int32_t splits, float* ws, int64_t ws_floats,
+                          void* out, void* stream);
+int64_t cmb_decode_attn_multi_ws(int64_t B, int32_t nh, int32_t nkv, int32_t hd, int32_t Q, int64_t t0, int32_t splits);
+int cmb_decode_attn_multi_plan(int64_t B, int32_t nkv, int64_t t0, int32_t Q, int32_t splits, int32_t* splits_out,
+                               int64_t* chunk_out, int32_t* max_splits_out);
 /* Greedy token selection and the next step's inputs in one launch (+ the cmb_rope_table launch), one workgroup per row b:
  *   nxt = argmax(logits[b, 0..V))       fp32 logits, row stride logits_ld; ties: the lowest index; a NaN is greater than
  *                                       every number and the first NaN wins (torch.argmax's rules); -0 == +0
