@@ -294,6 +294,9 @@ SIGNATURES = {
                                         _p]),
     "cmb_decode_linear_fp4_supported": (C.c_int, [_i32, _i64, _i64, _i32]),
     "cmb_decode_linear_fp4_plan": (C.c_int, [_i32, _i64, _i64, _i32, _i32, C.POINTER(_i32), C.POINTER(_i64)]),
+    "cmb_decode_linear_wide": (C.c_int, [_p, _i64, _i32, _p, _f, _p, _i64, _i64, _i64, _i32, _p, _i64, _p, _i64, _i32, _p]),
+    "cmb_decode_linear_wide_supported": (C.c_int, [_i32, _i64, _i64, _i32]),
+    "cmb_decode_linear_wide_plan": (C.c_int, [_i32, _i64, _i64, _i32, _i32, C.POINTER(_i32), C.POINTER(_i64)]),
     "cmb_decode_step": (C.c_int, [C.POINTER(DecodeStepDesc), C.POINTER(DecodeLayer), _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _p,
                                   _i64, _p]),
     "cmb_decode_step_ws": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32, _i64]),

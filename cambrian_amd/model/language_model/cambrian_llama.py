@@ -209,18 +209,41 @@ def _frozen_plain(*mods) -> bool:
                    or getattr(m, "_cmb_no_weight_cache", False) for m in mods)
 
 
-def decode_linear_weights(x: torch.Tensor, w_qkv, w_o, w_gate_up, w_down, norms) -> bool:
+def decode_linear_weights(x: torch.Tensor, w_qkv, w_o, w_gate_up, w_down, norms, wide: bool = False) -> bool:
     """The weights' side of "this decode step runs as five launches" (``ops.decode_linear`` around
     ``ops.decode_attention``): the four (packed) weights present and taken by the kernel for x's rows, the norms frozen bf16
     vectors.  Callers have checked the rest: bf16 x of at most 16 sequences inside the ``use_decode_kernel`` arm, and the
-    switch (``ops.decode_linear_enabled``) on for this batch."""
+    switch (``ops.decode_linear_enabled``) on for this batch.  ``wide``: the same question put to ``ops.decode_linear_wide``
+    (17-64 rows, ``decode_wide_rows``)."""
     B = x.shape[0]
     if any(w is None for w in (w_qkv, w_o, w_gate_up, w_down)):
         return False
     if any(n.weight.requires_grad or n.weight.dtype != torch.bfloat16 for n in norms):
         return False
+    if wide:
+        return (ops.decode_linear_wide_supported(x.reshape(B, -1), w_qkv) and ops.decode_linear_wide_weight_supported(B, w_o)
+                and ops.decode_linear_wide_weight_supported(B, w_gate_up, "swiglu")
+                and ops.decode_linear_wide_weight_supported(B, w_down))
     return (ops.decode_linear_supported(x.reshape(B, -1), w_qkv) and ops.decode_linear_weight_supported(B, w_o)
             and ops.decode_linear_weight_supported(B, w_gate_up, "swiglu") and ops.decode_linear_weight_supported(B, w_down))
+
+
+def decode_wide_rows(holder, rows: int) -> bool:
+    """Whether a decode step of ``rows`` rows takes ``ops.decode_linear_wide`` in the place of ``ops.decode_linear``: 17-64
+    rows, the wide switch on (``config.decode_linear_wide`` of the config ``holder`` was built from, or
+    CAMBRIAN_AMD_DECODE_LINEAR_WIDE), and CAMBRIAN_AMD_DECODE_LINEAR not 0.  Off, which is the default, or at 16 rows and
+    fewer, no dispatch site behaves differently.  What the step does NOT take at these rows: the e4m3 / MXFP4 weight streams
+    (17-64 rows run the bf16 wide kernel and no quantised copy is made for them, exactly as none is made above 16 rows
+    without the switch), the one-call step (``DecodeStepPlan.build`` keeps refusing more than 16 rows, so such a batch stays
+    on the per-launch loop) and prompt lookup (16 rows at most).  The e4m3 K / V cache works through
+    ``ops.decode_attention_any`` as at 16 rows.  fp32 models, trainable or biased projections and more than 64 rows keep the
+    stock sequence."""
+    if rows <= ops.DECODE_LINEAR_MAX_ROWS:
+        return False
+    cfg = holder.__dict__.get("_decode_cfg")               # a decoder layer; the language model has .config
+    if cfg is None:
+        cfg = getattr(holder, "config", None)
+    return ops.decode_linear_wide_rows(rows, getattr(cfg, "decode_linear_wide", False))
 
 
 def _decode_fp8_tag(w: torch.Tensor):
@@ -282,11 +305,13 @@ def decode_fp4_copies(holder: nn.Module, B: int, entries):
     return [c[1] for c in cached]
 
 
-def decode_layer_fused(layer, x, cos, sin, kcache, vcache, t, key_mask, w_qkv, w_o, w_gate_up, w_down, fp8=None, fp4=None):
+def decode_layer_fused(layer, x, cos, sin, kcache, vcache, t, key_mask, w_qkv, w_o, w_gate_up, w_down, fp8=None, fp4=None,
+                       linear=None):
     """The five launches of a decode step: norm + QKV projection, attention on the cache, o_proj + skip connection,
     norm + gate / up projection + SwiGLU, down_proj + skip connection.  ``fp8``: the four (bytes, factors) pairs of
     ``decode_fp8_copies`` — the linears then stream those instead of the bf16 weights.  ``fp4``: the four (nibbles, scales)
-    pairs of ``decode_fp4_copies``, likewise (at most one of the two)."""
+    pairs of ``decode_fp4_copies``, likewise (at most one of the two).  ``linear``: the bf16 linear, ``ops.decode_linear`` unless
+    given (``ops.decode_linear_wide`` at 17-64 rows)."""
     attn = layer.self_attn
     B = x.shape[0]
     nq, nk = attn.nh * attn.hd, attn.nkv * attn.hd
@@ -306,11 +331,12 @@ def decode_layer_fused(layer, x, cos, sin, kcache, vcache, t, key_mask, w_qkv, w
         x2 = ops.decode_linear_fp8(o, *q_o, residual=x2)
         inner = ops.decode_linear_fp8(x2, *q_gate_up, norm_weight=n2.weight, eps=n2.variance_epsilon, act="swiglu")
         return ops.decode_linear_fp8(inner, *q_down, residual=x2).reshape(B, 1, -1)
-    row = ops.decode_linear(x2, w_qkv, norm_weight=n1.weight, eps=n1.variance_epsilon)
+    lin = ops.decode_linear if linear is None else linear
+    row = lin(x2, w_qkv, norm_weight=n1.weight, eps=n1.variance_epsilon)
     o = ops.decode_attention_any(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t, key_mask)
-    x2 = ops.decode_linear(o, w_o, residual=x2)
-    inner = ops.decode_linear(x2, w_gate_up, norm_weight=n2.weight, eps=n2.variance_epsilon, act="swiglu")
-    return ops.decode_linear(inner, w_down, residual=x2).reshape(B, 1, -1)
+    x2 = lin(o, w_o, residual=x2)
+    inner = lin(x2, w_gate_up, norm_weight=n2.weight, eps=n2.variance_epsilon, act="swiglu")
+    return lin(inner, w_down, residual=x2).reshape(B, 1, -1)
 
 
 def lookup_mask(key_mask: torch.Tensor, t0: int, Q: int) -> torch.Tensor:
@@ -445,6 +471,7 @@ class LlamaAttention(nn.Module):
 class LlamaDecoderLayer(nn.Module):
     def __init__(self, cfg, device, dtype):
         super().__init__()
+        self.__dict__["_decode_cfg"] = cfg                 # decode_wide_rows reads config.decode_linear_wide when a step runs
         self.self_attn = LlamaAttention(cfg, device, dtype)
         self.mlp = LlamaMLP(cfg, device, dtype)
         self.input_layernorm = HipRMSNorm(cfg.hidden_size, cfg.rms_norm_eps, device, dtype)
@@ -470,14 +497,18 @@ class LlamaDecoderLayer(nn.Module):
         conditions, restated for ``DecodeStepPlan`` (asked once per ``generate()`` call) so that the per-launch loop, the
         yardstick of the one-call step, stays line for line what it was."""
         a, mlp = self.self_attn, self.mlp
-        if x.dtype == torch.bfloat16 and x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS and ops.decode_linear_enabled(x.shape[0]) \
+        wide = decode_wide_rows(self, x.shape[0])           # 17-64 rows behind the wide switch: ops.decode_linear_wide
+        if x.dtype == torch.bfloat16 and (wide or (x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS
+                                                   and ops.decode_linear_enabled(x.shape[0]))) \
                 and use_decode_kernel(x, a.nh, a.nkv, a.hd):
             # the packed copies are the prefill's (_fused_frozen_weight: frozen bias-free projections only)
             w = (_fused_frozen_weight(a, "_w_qkv", (a.q_proj, a.k_proj, a.v_proj)),
                  a.o_proj.weight if _frozen_plain(a.o_proj) else None,
                  _fused_frozen_weight(mlp, "_w_gate_up", (mlp.gate_proj, mlp.up_proj)),
                  mlp.down_proj.weight if _frozen_plain(mlp.down_proj) else None)
-            if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm)):
+            if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm), wide):
+                if wide:
+                    return w, None
                 if fp4:
                     return w, self._decode_fp4(x.shape[0], w)
                 q8 = None
@@ -491,16 +522,21 @@ class LlamaDecoderLayer(nn.Module):
     def decode(self, x, cos, sin, kcache, vcache, t, key_mask, fp8=False, fp4=False):
         """``fp8``: stream e4m3 copies of the weights where the five-launch step is taken (``ops.decode_fp8_enabled``,
         resolved once by ``generate``).  ``fp4``: MXFP4 copies instead (``ops.decode_fp4_enabled``); ``generate`` never sets
-        both (``ops.decode_weight_format``), and ``fp4`` wins here if a caller does."""
+        both (``ops.decode_weight_format``), and ``fp4`` wins here if a caller does.  At 17-64 rows with the wide switch on
+        (``decode_wide_rows``) the five launches run on ``ops.decode_linear_wide`` and the bf16 weights."""
         a, mlp = self.self_attn, self.mlp
-        if x.dtype == torch.bfloat16 and x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS and ops.decode_linear_enabled(x.shape[0]) \
+        wide = decode_wide_rows(self, x.shape[0])           # 17-64 rows behind the wide switch: ops.decode_linear_wide
+        if x.dtype == torch.bfloat16 and (wide or (x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS
+                                                   and ops.decode_linear_enabled(x.shape[0]))) \
                 and use_decode_kernel(x, a.nh, a.nkv, a.hd):
             # the packed copies are the prefill's (_fused_frozen_weight: frozen bias-free projections only)
             w = (_fused_frozen_weight(a, "_w_qkv", (a.q_proj, a.k_proj, a.v_proj)),
                  a.o_proj.weight if _frozen_plain(a.o_proj) else None,
                  _fused_frozen_weight(mlp, "_w_gate_up", (mlp.gate_proj, mlp.up_proj)),
                  mlp.down_proj.weight if _frozen_plain(mlp.down_proj) else None)
-            if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm)):
+            if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm), wide):
+                if wide:     # bf16 weights whatever fp8 / fp4 say: no quantised copies are made for more than 16 rows
+                    return decode_layer_fused(self, x, cos, sin, kcache, vcache, t, key_mask, *w, linear=ops.decode_linear_wide)
                 if fp4:
                     return decode_layer_fused(self, x, cos, sin, kcache, vcache, t, key_mask, *w,
                                               fp4=self._decode_fp4(x.shape[0], w))
@@ -814,9 +850,13 @@ def _decode_logits_operands(self, x: torch.Tensor, fp8: bool = False, fp4: bool 
     model, head = self.model, self.lm_head
     a = model.layers[0].self_attn if len(model.layers) else None        # a decoder without layers keeps the stock line
     B = x.shape[0]
-    if a is not None and use_decode_kernel(x, a.nh, a.nkv, a.hd) and x.dtype == torch.bfloat16 and B <= ops.DECODE_LINEAR_MAX_ROWS \
-            and ops.decode_linear_enabled(B) and _frozen_plain(head) and not model.norm.weight.requires_grad \
-            and model.norm.weight.dtype == torch.bfloat16 and ops.decode_linear_supported(x[:, 0], head.weight):
+    wide = decode_wide_rows(self, B)
+    if a is not None and use_decode_kernel(x, a.nh, a.nkv, a.hd) and x.dtype == torch.bfloat16 \
+            and (wide or (B <= ops.DECODE_LINEAR_MAX_ROWS and ops.decode_linear_enabled(B))) \
+            and _frozen_plain(head) and not model.norm.weight.requires_grad and model.norm.weight.dtype == torch.bfloat16 \
+            and (ops.decode_linear_wide_supported if wide else ops.decode_linear_supported)(x[:, 0], head.weight):
+        if wide:
+            return head.weight, None
         if fp4:
             q8 = decode_fp4_copies(head, B, ((head, "_w_fp4", head.weight, None),))
         else:
@@ -829,13 +869,19 @@ def _decode_logits(self, x: torch.Tensor, fp8: bool = False, fp4: bool = False) 
     """fp32 logits of a decode step from the last layer's x [B, 1, H]: final norm + lm_head in one ``ops.decode_linear``
     launch under the conditions of the layers' five-launch step, else the norm kernel, the stock GEMM and a cast.
     ``fp8``: that launch streams the lm_head's e4m3 copy (``ops.decode_linear_fp8``) where the kernel takes it; ``fp4``: its
-    MXFP4 copy (``ops.decode_linear_fp4``)."""
+    MXFP4 copy (``ops.decode_linear_fp4``).  At 17-64 rows with the wide switch on (``decode_wide_rows``) the one launch is
+    ``ops.decode_linear_wide`` on the bf16 lm_head, whatever ``fp8`` / ``fp4`` say."""
     model, head = self.model, self.lm_head
     a = model.layers[0].self_attn if len(model.layers) else None        # a decoder without layers keeps the stock line
     B = x.shape[0]
-    if a is not None and use_decode_kernel(x, a.nh, a.nkv, a.hd) and x.dtype == torch.bfloat16 and B <= ops.DECODE_LINEAR_MAX_ROWS \
-            and ops.decode_linear_enabled(B) and _frozen_plain(head) and not model.norm.weight.requires_grad \
-            and model.norm.weight.dtype == torch.bfloat16 and ops.decode_linear_supported(x[:, 0], head.weight):
+    wide = decode_wide_rows(self, B)
+    if a is not None and use_decode_kernel(x, a.nh, a.nkv, a.hd) and x.dtype == torch.bfloat16 \
+            and (wide or (B <= ops.DECODE_LINEAR_MAX_ROWS and ops.decode_linear_enabled(B))) \
+            and _frozen_plain(head) and not model.norm.weight.requires_grad and model.norm.weight.dtype == torch.bfloat16 \
+            and (ops.decode_linear_wide_supported if wide else ops.decode_linear_supported)(x[:, 0], head.weight):
+        if wide:
+            return ops.decode_linear_wide(x[:, 0], head.weight, norm_weight=model.norm.weight, eps=model.norm.variance_epsilon,
+                                          out_dtype=torch.float32)
         q4 = decode_fp4_copies(head, B, ((head, "_w_fp4", head.weight, None),)) if fp4 else None
         if q4 is not None:
             return ops.decode_linear_fp4(x[:, 0], *q4[0], norm_weight=model.norm.weight, eps=model.norm.variance_epsilon,

@@ -34,7 +34,7 @@ from ... import lib as L
 from ... import ops
 from .cambrian_llama import (CambrianLlamaForCausalLM, CambrianLlamaModel, HipRMSNorm, _down_proj, _frozen_plain, _lin,
                              decode_fp4_copies, decode_fp8_copies, decode_layer_fused, decode_linear_weights, decode_multi_fused_or_none,
-                             lookup_mask, use_decode_kernel)
+                             decode_wide_rows, lookup_mask, use_decode_kernel)
 
 
 class CambrianConfig(Phi3Config):
@@ -126,6 +126,7 @@ class Phi3DecoderLayer(nn.Module):
     def __init__(self, cfg, device, dtype):
         super().__init__()
         _check_rope(cfg)
+        self.__dict__["_decode_cfg"] = cfg                 # decode_wide_rows reads config.decode_linear_wide when a step runs
         self.self_attn = Phi3Attention(cfg, device, dtype)
         self.mlp = Phi3MLP(cfg, device, dtype)
         self.input_layernorm = HipRMSNorm(cfg.hidden_size, cfg.rms_norm_eps, device, dtype)
@@ -141,12 +142,16 @@ class Phi3DecoderLayer(nn.Module):
 
     def decode(self, x, cos, sin, kcache, vcache, t, key_mask, fp8=False, fp4=False):
         a, mlp = self.self_attn, self.mlp
-        if x.dtype == torch.bfloat16 and x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS and ops.decode_linear_enabled(x.shape[0]) \
+        wide = decode_wide_rows(self, x.shape[0])           # 17-64 rows behind the wide switch: ops.decode_linear_wide
+        if x.dtype == torch.bfloat16 and (wide or (x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS
+                                                   and ops.decode_linear_enabled(x.shape[0]))) \
                 and use_decode_kernel(x, a.nh, a.nkv, a.hd):
             # qkv_proj / gate_up_proj are packed as the kernel wants them: no copies
             mods = (a.qkv_proj, a.o_proj, mlp.gate_up_proj, mlp.down_proj)
             w = tuple(m.weight if _frozen_plain(m) else None for m in mods)
-            if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm)):
+            if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm), wide):
+                if wide:     # bf16 weights whatever fp8 / fp4 say: no quantised copies are made for more than 16 rows
+                    return decode_layer_fused(self, x, cos, sin, kcache, vcache, t, key_mask, *w, linear=ops.decode_linear_wide)
                 if fp4:      # MXFP4 copies, cached on the Linear that owns the weight under a key of their own
                     q4 = decode_fp4_copies(self, x.shape[0], tuple(
                         (m, "_w_fp4", wi, "swiglu" if m is mlp.gate_up_proj else None) for m, wi in zip(mods, w)))
@@ -171,11 +176,15 @@ class Phi3DecoderLayer(nn.Module):
         """(the four weights, their e4m3 copies or None) when ``decode`` runs a step of x as five launches, else None:
         ``decode``'s conditions restated for ``DecodeStepPlan`` (see LlamaDecoderLayer.decode_operands)."""
         a, mlp = self.self_attn, self.mlp
-        if x.dtype == torch.bfloat16 and x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS and ops.decode_linear_enabled(x.shape[0]) \
+        wide = decode_wide_rows(self, x.shape[0])           # 17-64 rows behind the wide switch: ops.decode_linear_wide
+        if x.dtype == torch.bfloat16 and (wide or (x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS
+                                                   and ops.decode_linear_enabled(x.shape[0]))) \
                 and use_decode_kernel(x, a.nh, a.nkv, a.hd):
             mods = (a.qkv_proj, a.o_proj, mlp.gate_up_proj, mlp.down_proj)
             w = tuple(m.weight if _frozen_plain(m) else None for m in mods)
-            if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm)):
+            if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm), wide):
+                if wide:
+                    return w, None
                 if fp4:
                     return w, decode_fp4_copies(self, x.shape[0], tuple(
                         (m, "_w_fp4", wi, "swiglu" if m is mlp.gate_up_proj else None) for m, wi in zip(mods, w)))

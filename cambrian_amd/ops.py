@@ -2481,6 +2481,92 @@ def decode_linear(x: torch.Tensor, w: torch.Tensor, *, norm_weight: Optional[tor
 
 
 # ------------------------------------------------------------------------------------------------
+# the same linears at up to 64 rows (decode_linear_wide.hip): decode steps of 17-64 sequences, or beams.  Opt-in
+# (config.decode_linear_wide / CAMBRIAN_AMD_DECODE_LINEAR_WIDE): profiles/decode_linear_wide.md has what was measured.
+# ------------------------------------------------------------------------------------------------
+DECODE_LINEAR_WIDE_MAX_ROWS = 64
+
+
+def decode_linear_wide_enabled(config_flag: bool = False) -> bool:
+    """Whether decode steps of 17-64 rows run their linears on ``decode_linear_wide`` (five launches per layer) instead of the
+    stock sequence: ``CAMBRIAN_AMD_DECODE_LINEAR_WIDE`` = ``1`` / ``0`` in the environment overrides, unset it is
+    ``config_flag`` (the model's ``config.decode_linear_wide``, absent = off).  Any other value raises: a typo must not
+    silently pick a side.  ``CAMBRIAN_AMD_DECODE_LINEAR=0`` (the stock sequence everywhere) wins over this switch at the
+    dispatch sites."""
+    v = os.environ.get("CAMBRIAN_AMD_DECODE_LINEAR_WIDE")
+    if v is None or v == "":
+        return bool(config_flag)
+    if v not in ("0", "1"):
+        raise ValueError(f"CAMBRIAN_AMD_DECODE_LINEAR_WIDE={v!r}: the switch takes 1 or 0")
+    return v == "1"
+
+
+def decode_linear_wide_rows(rows: int, config_flag: bool = False) -> bool:
+    """The dispatch sites' question: do ``rows`` rows of a decode step go to ``decode_linear_wide``?  17-64 rows, the wide
+    switch on, and ``CAMBRIAN_AMD_DECODE_LINEAR`` not ``0``."""
+    return (DECODE_LINEAR_MAX_ROWS < rows <= DECODE_LINEAR_WIDE_MAX_ROWS and decode_linear_wide_enabled(config_flag)
+            and os.environ.get("CAMBRIAN_AMD_DECODE_LINEAR") != "0")
+
+
+def decode_linear_wide_plan(M: int, N: int, K: int, act: Optional[str] = None, cus: int = 0) -> Tuple[int, int]:
+    """(weight rows per workgroup, workgroups) of a ``decode_linear_wide`` call: a pure function of (N, act, CU count);
+    ``cus`` = 0 takes the current device's count."""
+    rows, wgs = C.c_int32(0), C.c_int64(0)
+    L.check(L.load().cmb_decode_linear_wide_plan(M, N, K, _decode_linear_act(act), cus, C.byref(rows), C.byref(wgs)),
+            "cmb_decode_linear_wide_plan")
+    return rows.value, wgs.value
+
+
+def decode_linear_wide_weight_supported(M: int, w: torch.Tensor, act: Optional[str] = None) -> bool:
+    """The weight's side of ``decode_linear_wide_supported``, for ``M`` rows of x that are yet to be computed."""
+    return (w.dim() == 2 and _decode_linear_rows_ok(w, w.shape[1])
+            and bool(L.load().cmb_decode_linear_wide_supported(M, w.shape[0], w.shape[1], _decode_linear_act(act))))
+
+
+def decode_linear_wide_supported(x: torch.Tensor, w: torch.Tensor, act: Optional[str] = None) -> bool:
+    """Whether ``decode_linear_wide(x, w, act=act)`` takes these operands: ``decode_linear_supported``'s conditions with
+    x [M <= 64, K]."""
+    return (w.dim() == 2 and x.dim() == 2 and x.shape[0] >= 1 and _decode_linear_rows_ok(x, w.shape[1])
+            and decode_linear_wide_weight_supported(x.shape[0], w, act))
+
+
+def decode_linear_wide(x: torch.Tensor, w: torch.Tensor, *, norm_weight: Optional[torch.Tensor] = None, eps: float = 0.0,
+                       act: Optional[str] = None, residual: Optional[torch.Tensor] = None,
+                       out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``decode_linear`` for bf16 x [M <= 64, K]: the same function, arguments and checks, one launch that reads the weights
+    once.  The same inputs give the same bits, and a row's bits depend neither on M nor on the other rows; they are not
+    ``decode_linear``'s bits (another order of the same fp32 sum).  Inference only: there is no backward."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w, norm_weight, residual)):
+        raise L.CambrianAmdError("decode_linear_wide has no backward: call it under torch.no_grad()")
+    L.require_gpu(x, w, norm_weight, residual, out)
+    code = _decode_linear_act(act)
+    if not decode_linear_wide_supported(x, w, act):
+        raise L.CambrianAmdError(f"decode_linear_wide: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, "
+                                 f"w {tuple(w.shape)} {w.dtype} strides {w.stride()}, act {act!r}")
+    (M, K), N = x.shape, w.shape[0]
+    cols = N // 2 if code else N
+    if norm_weight is not None and (norm_weight.dtype != torch.bfloat16 or norm_weight.shape != (K,)
+                                    or not norm_weight.is_contiguous()):
+        raise L.CambrianAmdError("decode_linear_wide: norm_weight is a contiguous bf16 [K] vector")
+    if residual is not None and (code or residual.dtype != torch.bfloat16 or residual.shape != (M, cols)
+                                 or residual.stride(1) != 1):
+        raise L.CambrianAmdError("decode_linear_wide: residual is bf16 [M, N] with contiguous rows, and not combined with act")
+    out_dtype = out_dtype or (torch.bfloat16 if out is None else out.dtype)
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise L.CambrianAmdError(f"decode_linear_wide: out_dtype {out_dtype} (bf16 or fp32)")
+    if out is None:
+        ld = (cols + 7) // 8 * 8
+        out = torch.empty((M, ld), dtype=out_dtype, device=x.device)[:, :cols]
+    elif not out.is_cuda or out.dtype != out_dtype or out.shape != (M, cols) or out.stride(1) != 1:
+        raise L.CambrianAmdError(f"decode_linear_wide: out must be a {out_dtype} GPU tensor [{M}, {cols}] with contiguous rows")
+    ld = out.stride(0)
+    L.call("cmb_decode_linear_wide", x.data_ptr(), x.stride(0), M, L.ptr(norm_weight), float(eps), w.data_ptr(), w.stride(0), N,
+           K, code, L.ptr(residual), 0 if residual is None else residual.stride(0), out.data_ptr(), ld,
+           int(out_dtype == torch.float32), device=x.device)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # the same linears on weight-only e4m3 weights (decode_linear_fp8.hip): half the weight stream of a decode step.  Opt-in
 # (``config.decode_fp8_weights`` / CAMBRIAN_AMD_DECODE_FP8): it changes numerics — row-wise e4m3 weights are about 2.5–2.7 %
 # relative L2 error per product on Gaussian weights — and keeps a 1-byte copy of every decoder weight beside the bf16 one.

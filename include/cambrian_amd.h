@@ -74,7 +74,8 @@ const char* cmb_version(void);
  * decode-step linear (cmb_quantize_mxfp4_rows, cmb_decode_linear_fp4, cmb_decode_linear_fp4_supported,
  * cmb_decode_linear_fp4_plan, and the value 2 of cmb_decode_step_desc.fp8), and then the e4m3 K / V cache of the decode steps
  * (cmb_kv_quantize_e4m3, cmb_decode_attn_kv8, cmb_decode_step_kv8 and cmb_decode_kv8_factors), and then the multi-token
- * decode attention of prompt-lookup decoding (cmb_decode_attn_multi, cmb_decode_attn_multi_ws, cmb_decode_attn_multi_plan) were
+ * decode attention of prompt-lookup decoding (cmb_decode_attn_multi, cmb_decode_attn_multi_ws, cmb_decode_attn_multi_plan), and then the decode-step linear for up to
+ * 64 rows (cmb_decode_linear_wide, cmb_decode_linear_wide_supported, cmb_decode_linear_wide_plan) were
  * ADDED under revision 13: no existing
  * signature or layout changed, which is the rule for a bump, so a binding written against 13 still calls everything it
  * knows correctly.  Bindings must compare it
@@ -746,6 +747,26 @@ int cmb_decode_linear(const void* x, int64_t x_ld, int32_t M, const void* norm_w
                       int64_t o_ld, int32_t out_f32, void* stream);
 int cmb_decode_linear_supported(int32_t M, int64_t N, int64_t K, int32_t act);
 int cmb_decode_linear_plan(int32_t M, int64_t N, int64_t K, int32_t act, int32_t cus, int32_t* rows_out, int64_t* wgs_out);
+/* cmb_decode_linear for 1 <= M <= 64 rows (decode steps of 17-64 sequences or beams): the same function, arguments, checks
+ * and statuses, with "M in 1 .. 64" in place of "M in 1 .. 16".  x is taken as ceil(M / 16) row blocks of the 16-column
+ * operand of the matrix unit; weights stream as in cmb_decode_linear (non-temporal 16-byte loads straight to registers, a
+ * full 128-byte line per row and instruction, every weight byte read from HBM once per launch); a workgroup owns a slab of
+ * 16 or 32 weight rows and reads all of x through the caches; K is split over the workgroup's four waves and summed through
+ * LDS in wave order.  No split of K across workgroups, no atomics, no flags, no workspace.  The same inputs give the same
+ * bits on every run, and the bits of an output row depend neither on M nor on the other rows nor on the slab.  The order of
+ * a row's sum is NOT cmb_decode_linear's: the two agree within fp32 summation error, not to the bit.  Under the norm
+ * prologue x[m, k] * norm_w[k] goes through the matrix unit as its bf16 rounding plus the (exact, bf16) remainder, so the
+ * normalised row is never rounded.
+ * cmb_decode_linear_wide_supported: 1 / 0 for the shape conditions, no launch.  cmb_decode_linear_wide_plan: the weight rows
+ * a workgroup owns (16 or 32; with act = 1 half of them gate rows and half the matching up rows) and the number of
+ * workgroups, a pure function of (N, act, CU count): 32 rows where that leaves one workgroup per CU, else 16.  cus = 0 asks
+ * for the current device's count (256 when there is none). */
+int cmb_decode_linear_wide(const void* x, int64_t x_ld, int32_t M, const void* norm_w, float norm_eps, const void* W,
+                           int64_t w_ld, int64_t N, int64_t K, int32_t act, const void* residual, int64_t r_ld, void* out,
+                           int64_t o_ld, int32_t out_f32, void* stream);
+int cmb_decode_linear_wide_supported(int32_t M, int64_t N, int64_t K, int32_t act);
+int cmb_decode_linear_wide_plan(int32_t M, int64_t N, int64_t K, int32_t act, int32_t cus, int32_t* rows_out,
+                                int64_t* wgs_out);
 /* cmb_decode_linear on weight-only e4m3 weights, half the weight stream of a decode step:
  *   out = epilogue(rstd? * w_inv_scale[n] * sum_k prologue(x)[m, k] * e4m3(Wq[n, k]))
  * Wq: OCP e4m3fn bytes [N, K] with row stride w_ld BYTES, w_inv_scale: fp32 [N] — what cmb_quantize_fp8_rows writes (a
