@@ -313,6 +313,8 @@ SIGNATURES = {
                                   _i64, _i32, _f, _p, _p, _p]),
     "cmb_decode_sample": (C.c_int, [_p, _i64, _i32, _i64, _f, _i64, _f, _p, _i64, _p, _p, _i64, _i64, _p, _p, _p, _i64, _i64, _p,
                                     _i64, _i64, _i64, _p, _i64, _i32, _f, _p, _p, _p, _p, _p]),
+    "cmb_decode_process": (C.c_int, [_p, _i64, _i32, _i64, _p, _i64, _i64, _f, _i64, _i64, _p, _i32, _p, _i32, _p, _i64, _p, _i32,
+                                     _p, _p]),
     "cmb_decode_beam_state_bytes": (_i64, [_i32, _i32, _i64]),
     "cmb_decode_beam": (C.c_int, [_p, _i64, _i32, _i32, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _p, _i64, _i64,
                                   _i64, _p, _i64, _i32, _f, _p, _p, C.POINTER(DecodeStepDesc), C.POINTER(DecodeLayer), _i64, _p,

@@ -35,6 +35,7 @@ from ... import lib as _lib
 from ... import ops
 from ...constants import IGNORE_INDEX
 from ..cambrian_arch import CambrianMetaForCausalLM, CambrianMetaModel, SvaContext
+from . import processors as PROC
 from .beam import BeamState, beam_done, beam_fill, beam_result, beam_update
 
 
@@ -1003,7 +1004,13 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
     ``prompt_lookup_num_tokens`` (1 .. 15; None / 0 = off) with ``max_matching_ngram_size`` (default 2): HF's prompt-lookup
     assisted decoding for greedy decoding of ONE prompt (``_lookup_loop``): drafts by n-gram lookup in the prompt and the
     output so far, verified in one multi-token step; the call leaves ``self.lookup_stats``.  ``_draft_fn`` (private) stands in
-    for ``lookup.ngram_draft``."""
+    for ``lookup.ngram_draft``.
+    With the logits processors switched on (``config.decode_logits_processors`` / CAMBRIAN_AMD_DECODE_PROCESS=1):
+    ``repetition_penalty``, ``no_repeat_ngram_size``, ``min_new_tokens``, ``bad_words_ids``, ``suppress_tokens`` as HF's
+    processors define them over the GENERATED ids (``processors.py``; one ``ops.decode_process`` launch per token before the
+    selection, on both loops), and ``eos_token_id`` may be a list: a row is done from its first id of the set and then emits
+    ``eos[0]``.  They do not combine with beam search or prompt-lookup decoding (NotImplementedError); switched off, anything
+    but their off values raises a ValueError that names the switch."""
     if "inputs_embeds" in kwargs:
         raise NotImplementedError("`inputs_embeds` is not supported")          # cambrian_llama.py:447-448
     beams = 1 if num_beams is None else int(num_beams)
@@ -1019,12 +1026,18 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
     if "max_length" in kwargs and kwargs["max_length"] is not None:
         raise NotImplementedError("generate(max_length=...): use max_new_tokens")
     kwargs.pop("max_length", None)
+    # the logits processors that read the generated ids, opt-in; switched off, repetition_penalty keeps the rule below
+    proc_on = ops.decode_process_enabled(getattr(getattr(self, "config", None), "decode_logits_processors", False))
+    proc_args = {k: kwargs.pop(k, None) for k in PROC.ARGUMENTS if k != "repetition_penalty" or proc_on}
     for k, v in kwargs.items():
         ok = _GENERATE_ACCEPTED_NOOPS.get(k, ())
         if k not in _GENERATE_ACCEPTED_NOOPS or (ok is not None and v not in ok):
             raise ValueError(f"generate(): unsupported argument {k}={v!r} (cambrian_amd implements greedy / temperature / "
                              "top_k / top_p decoding with a K/V cache)")
     lookup = _lookup_args(self, inputs, prompt_lookup_num_tokens, max_matching_ngram_size, do_sample, temperature, beams)
+    spec = PROC.parse(proc_on, eos_token_id, beams=beams, lookup=lookup is not None, **proc_args)
+    if proc_on and eos_token_id is not None:            # an int, a list of one id, or a set: eos[0] is what a done row emits
+        eos_token_id = PROC.eos_list(eos_token_id)[0]
     prompt_ids, prompt_mask = inputs, attention_mask        # what the lookup drafts from (the multimodal prefill replaces both)
     with torch.no_grad():
         model = self.model
@@ -1079,15 +1092,22 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
         if max_new_tokens > 1 and ops.decode_step_enabled(getattr(self.config, "decode_step_fused", False)):
             plan = DecodeStepPlan.build(self, B, caches, Lmax - 1, fp8, **low)
         sampled = bool(do_sample and temperature > 0)
+        proc = None if spec is None else ops.DecodeProcess(spec, dev)          # the lists go to the device once per call
+        pk = {} if proc is None else {"proc": proc}                              # (without processors the calls stay what they were)
         if plan is not None and (not sampled or ops.decode_sample_enabled(getattr(self.config, "decode_sample_device", False))):
             emb = model.embed_tokens.weight
             if emb.dtype == torch.bfloat16 and emb.stride(1) == 1 and emb.stride(0) % 8 == 0 and emb.data_ptr() % 16 == 0 \
                     and emb.shape[0] >= logits.shape[1] and (eos_token_id is None or 0 <= int(eos_token_id) < emb.shape[0]):
                 if sampled:
                     return _sample_fused(plan, emb, logits, key_mask, n_tok, L, max_new_tokens, eos_token_id, hd, theta,
-                                         temperature, top_k, top_p)
-                return _greedy_fused(plan, emb, logits, key_mask, n_tok, L, max_new_tokens, eos_token_id, hd, theta)
+                                         temperature, top_k, top_p, **pk)
+                return _greedy_fused(plan, emb, logits, key_mask, n_tok, L, max_new_tokens, eos_token_id, hd, theta, **pk)
+        if proc is not None:                     # the history the kernel reads, and the eos set a row is done on
+            hist = torch.zeros(B, max_new_tokens, dtype=torch.int64, device=dev)
+            eos_set = torch.tensor(spec.eos, dtype=torch.int64, device=dev)
         for step in range(max_new_tokens):
+            if proc is not None:                 # processors first, warpers after: HF's order
+                ops.decode_process(logits, hist, step, proc)
             if do_sample and temperature > 0:
                 warped = filter_logits_top_k_top_p(logits / temperature, top_k, top_p)
                 nxt = torch.multinomial(torch.softmax(warped, -1), 1)[:, 0]
@@ -1095,7 +1115,9 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
                 nxt = logits.argmax(-1)
             if eos_token_id is not None:
                 nxt = torch.where(done, torch.full_like(nxt, eos_token_id), nxt)
-                done = done | (nxt == eos_token_id)
+                done = done | (nxt == eos_token_id if proc is None else torch.isin(nxt, eos_set))
+            if proc is not None:
+                hist[:, step] = nxt
             out_ids.append(nxt)
             if step + 1 == max_new_tokens or (eos_token_id is not None and bool(done.all())):
                 break
@@ -1243,12 +1265,16 @@ def _kv8_prefill(kv_out: list, B: int, nb: int, nkv: int, L: int, Lmax: int, hd:
     return caches
 
 
-def _greedy_fused(plan, emb, logits, key_mask, n_tok, L0: int, max_new_tokens: int, eos_token_id, hd: int, theta: float):
+def _greedy_fused(plan, emb, logits, key_mask, n_tok, L0: int, max_new_tokens: int, eos_token_id, hd: int, theta: float,
+                  proc=None):
     """The greedy loop as two library calls per token and no ATen call: ``ops.decode_next`` (selection, eos rule, position,
     key mask, embedding row, RoPE table) then ``ops.decode_step`` (every layer and the lm_head).  The first token comes from
     the prefill ``logits`` through the same selection.  With an eos id the host reads ``done`` only every
     ``ops.DECODE_STEP_POLL`` steps, so the loop may run up to that many tokens past the point where every row is done;
-    ``ops.trim_after_all_done`` cuts the result back to the column where the per-token loop stops."""
+    ``ops.trim_after_all_done`` cuts the result back to the column where the per-token loop stops.  ``proc`` (an
+    ``ops.DecodeProcess``): one more library call per token, ``ops.decode_process`` on the logits before the selection, reading
+    the ids in ``out``; a row that ends on a secondary eos is marked done by that call one step later, so the trim looks for
+    ids of the set (``ops.trim_after_all_done_set``)."""
     B = logits.shape[0]
     dev = logits.device
     eos = -1 if eos_token_id is None else int(eos_token_id)
@@ -1261,6 +1287,8 @@ def _greedy_fused(plan, emb, logits, key_mask, n_tok, L0: int, max_new_tokens: i
     n_tok = n_tok.contiguous()
     n = 0
     for step in range(max_new_tokens):
+        if proc is not None:
+            ops.decode_process(logits, out, step, proc, done)
         ops.decode_next(logits, eos, done, out, step, n_tok, pos, key_mask, L0 + step, emb, x, hd, theta, cos, sin)
         n = step + 1
         if n == max_new_tokens or (eos >= 0 and n % ops.DECODE_STEP_POLL == 0 and bool(done.all())):
@@ -1268,17 +1296,18 @@ def _greedy_fused(plan, emb, logits, key_mask, n_tok, L0: int, max_new_tokens: i
         logits = plan.step(x, cos, sin, L0 + step, key_mask)
     ids = out[:, :n]
     if eos >= 0:
-        ids = ops.trim_after_all_done(ids, eos)
+        ids = ops.trim_after_all_done(ids, eos) if proc is None else ops.trim_after_all_done_set(ids, proc.spec.eos)
     return ids.contiguous()
 
 
 def _sample_fused(plan, emb, logits, key_mask, n_tok, L0: int, max_new_tokens: int, eos_token_id, hd: int, theta: float,
-                  temperature: float, top_k, top_p):
+                  temperature: float, top_k, top_p, proc=None):
     """``_greedy_fused`` with ``ops.decode_sample`` in the place of ``ops.decode_next``: temperature, top-k, top-p and the draw
     on the device, so sampled decoding too is two library calls per token and no ATen call.  ``top_k`` None / 0 and ``top_p``
     None / >= 1 mean off; ``top_p <= 0`` raises what ``filter_logits_top_k_top_p`` raises.  The seed is one int64 drawn once
     per call ON the device from torch's generator (``torch.manual_seed`` governs it, the host never waits for it); the draws of
-    a call are counted by (element, row, step) under that seed, so they are not torch.multinomial's stream."""
+    a call are counted by (element, row, step) under that seed, so they are not torch.multinomial's stream.  ``proc``: as in
+    ``_greedy_fused`` — the processors run before the warpers, HF's order."""
     k = 0 if top_k is None else max(int(top_k), 0)
     p = 1.0 if top_p is None or float(top_p) >= 1.0 else float(top_p)
     if not 0.0 < p:
@@ -1297,6 +1326,8 @@ def _sample_fused(plan, emb, logits, key_mask, n_tok, L0: int, max_new_tokens: i
     n_tok = n_tok.contiguous()
     n = 0
     for step in range(max_new_tokens):
+        if proc is not None:
+            ops.decode_process(logits, out, step, proc, done)
         ops.decode_sample(logits, inv_t, k, p, seed, eos, done, out, step, n_tok, pos, key_mask, L0 + step, emb, x, hd, theta,
                           cos, sin)
         n = step + 1
@@ -1305,7 +1336,7 @@ def _sample_fused(plan, emb, logits, key_mask, n_tok, L0: int, max_new_tokens: i
         logits = plan.step(x, cos, sin, L0 + step, key_mask)
     ids = out[:, :n]
     if eos >= 0:
-        ids = ops.trim_after_all_done(ids, eos)
+        ids = ops.trim_after_all_done(ids, eos) if proc is None else ops.trim_after_all_done_set(ids, proc.spec.eos)
     return ids.contiguous()
 
 

@@ -2897,6 +2897,62 @@ def decode_sample(logits: torch.Tensor, inv_temperature: float, top_k: int, top_
            hd, rope_base, cos.data_ptr(), sin.data_ptr(), L.ptr(thr), L.ptr(n_keep), device=logits.device)
 
 
+def decode_process_enabled(config_flag: bool = False) -> bool:
+    """Whether ``generate()`` takes the logits processors that read the generated ids (``repetition_penalty``,
+    ``no_repeat_ngram_size``, ``min_new_tokens``, ``bad_words_ids``, ``suppress_tokens``) and a list ``eos_token_id``, and runs
+    them on the device (``decode_process``): ``CAMBRIAN_AMD_DECODE_PROCESS`` = ``1`` / ``0`` in the environment overrides, unset
+    it is ``config_flag`` (the model's ``config.decode_logits_processors``, absent = off).  Any other value raises."""
+    v = os.environ.get("CAMBRIAN_AMD_DECODE_PROCESS")
+    if v is None or v == "":
+        return bool(config_flag)
+    if v not in ("0", "1"):
+        raise ValueError(f"CAMBRIAN_AMD_DECODE_PROCESS={v!r}: the switch takes 1 or 0")
+    return v == "1"
+
+
+class DecodeProcess:
+    """One ``generate()`` call's processors on the device: the ``processors.ProcessSpec`` and its lists (eos ids, single-id
+    bans, the word table), uploaded once."""
+
+    def __init__(self, spec, device):
+        self.spec = spec
+        self.eos, self.bans, self.word_ids, self.word_off = spec.device_lists(device)
+        self.n_eos, self.n_bans, self.n_words = len(spec.eos), len(spec.bans), len(spec.words)
+        self.n_word_ids = 0 if self.word_ids is None else self.word_ids.numel()
+
+
+def decode_process(logits: torch.Tensor, hist: Optional[torch.Tensor], n_hist: int, proc: DecodeProcess,
+                   done: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The logits processors of ``proc`` on fp32 ``logits`` [B, V] (unit column stride, any row stride and alignment) IN PLACE,
+    in one launch: ``hist`` int64 [B, >= n_hist] holds each row's generated ids (None with ``n_hist`` 0), ``done`` bool / uint8
+    [B] is set where the row's last id is in the eos set.  Run it before ``decode_next`` / ``decode_sample`` or the argmax of
+    the same step; the rule is spelled out at ``cmb_decode_process`` in include/cambrian_amd.h and restated in
+    ``processors.apply_torch``.  Returns ``logits``."""
+    L.require_gpu(logits, hist, done)
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise L.CambrianAmdError("decode_process: logits is an fp32 [B, V] tensor with unit column stride")
+    if hist is not None and (hist.dtype != torch.int64 or hist.dim() != 2 or hist.stride(1) != 1 or hist.shape[0] != logits.shape[0]):
+        raise L.CambrianAmdError("decode_process: hist is an int64 [B, n] tensor with unit column stride")
+    if done is not None and (done.dtype not in (torch.bool, torch.uint8) or done.shape != (logits.shape[0],) or not done.is_contiguous()):
+        raise L.CambrianAmdError("decode_process: done is a contiguous bool / uint8 [B] tensor")
+    B, V = logits.shape
+    s = proc.spec
+    L.call("cmb_decode_process", logits.data_ptr(), logits.stride(0), B, V, L.ptr(hist), 0 if hist is None else hist.stride(0),
+           n_hist, s.penalty, s.ngram, s.min_new, L.ptr(proc.eos), proc.n_eos, L.ptr(proc.bans), proc.n_bans,
+           L.ptr(proc.word_ids), proc.n_word_ids, L.ptr(proc.word_off), proc.n_words, L.ptr(done), device=logits.device)
+    return logits
+
+
+def trim_after_all_done_set(ids: torch.Tensor, eos: Sequence[int]) -> torch.Tensor:
+    """``trim_after_all_done`` for an eos SET: a row is done from its first id that is in ``eos`` on.  The fused loops mark a
+    row that ends on a secondary eos one step late, so the columns are searched for ids of the set, not for ``eos[0]``."""
+    if ids.shape[1] == 0:
+        return ids
+    from .model.language_model.processors import first_in_set
+    hit = torch.nonzero(first_in_set(ids, eos).all(dim=0))
+    return ids if hit.numel() == 0 else ids[:, :int(hit[0, 0]) + 1]
+
+
 def decode_beam_enabled(config_flag: bool = False) -> bool:
     """Whether ``generate(num_beams > 1)`` runs beam search (on the device, ``decode_beam``, where the one-call decode step
     runs; else on the per-launch loop around model/language_model/beam.py) instead of raising: ``CAMBRIAN_AMD_DECODE_BEAM`` =

@@ -75,7 +75,8 @@ const char* cmb_version(void);
  * cmb_decode_linear_fp4_plan, and the value 2 of cmb_decode_step_desc.fp8), and then the e4m3 K / V cache of the decode steps
  * (cmb_kv_quantize_e4m3, cmb_decode_attn_kv8, cmb_decode_step_kv8 and cmb_decode_kv8_factors), and then the multi-token
  * decode attention of prompt-lookup decoding (cmb_decode_attn_multi, cmb_decode_attn_multi_ws, cmb_decode_attn_multi_plan), and then the decode-step linear for up to
- * 64 rows (cmb_decode_linear_wide, cmb_decode_linear_wide_supported, cmb_decode_linear_wide_plan) were
+ * 64 rows (cmb_decode_linear_wide, cmb_decode_linear_wide_supported, cmb_decode_linear_wide_plan), and then the logits
+ * processors of generate() (cmb_decode_process) were
  * ADDED under revision 13: no existing
  * signature or layout changed, which is the rule for a bump, so a binding written against 13 still calls everything it
  * knows correctly.  Bindings must compare it
@@ -973,6 +974,36 @@ int cmb_decode_sample(const float* logits, int64_t logits_ld, int32_t B, int64_t
                       int64_t step, const int64_t* n_tok, int64_t* pos, uint8_t* key_valid, int64_t kv_ld, int64_t t,
                       const void* embed, int64_t embed_ld, int64_t embed_rows, int64_t H, void* x, int64_t x_ld, int32_t hd,
                       float rope_base, float* cos_t, float* sin_t, float* thr, int32_t* n_keep, void* stream);
+/* The logits processors of generate() that read the ids produced so far, applied to a step's fp32 logits IN PLACE before
+ * cmb_decode_next / cmb_decode_sample select from them: one launch, one workgroup per row b, any B >= 1.  HF's
+ * RepetitionPenalty, NoRepeatNGram, NoBadWords, MinNewTokensLength and SuppressTokens processors chained in that order over the
+ * GENERATED ids (generate() with inputs_embeds never shows them the prompt); restated in torch in
+ * cambrian_amd/model/language_model/processors.py (apply_torch), the predicates are those of csrc/decode_process_core.h.
+ * With h = hist[b * hist_ld + 0 .. n_hist) (int64), n = n_hist, and "column of id" = id when 0 <= id < V, else none:
+ *   penalty != 1: for every DISTINCT id of h that has a column, once: l = logits[b, id]; logits[b, id] = l < 0 ? l * penalty
+ *                 : l / penalty  (fp32, IEEE-rounded; the lane at the id's first occurrence applies it);
+ *   then -inf at the column of each of:
+ *   - ngram = g > 0 and n + 1 >= g: every h[i + g - 1] with 0 <= i <= n - g and h[i .. i + g - 1) == h[n - g + 1 .. n)
+ *     (g = 1: every id of h);
+ *   - bans[0 .. n_bans): suppressed tokens and bad words of one id;
+ *   - word w = word_ids[word_off[w] .. word_off[w + 1]) of m ids, 0 <= w < n_words: its last id, when m == 1, or m <= n and
+ *     h[n - m + 1 .. n) == w[0 .. m - 1)  (HF's length rule is m <= n, not m - 1 <= n); offsets that do not describe a piece
+ *     of word_ids[0 .. n_word_ids) ban nothing;
+ *   - n < min_new: every id of eos[0 .. n_eos).
+ *   done != NULL, n_eos > 0, n >= 1 and h[n - 1] in eos: done[b] = 1 (else done[b] is left alone) — the selection that follows
+ *   then emits ITS eos argument, eos[0], for that row, which is how a row ends on any id of an eos set.
+ * An id without a column (the eos of an embedding table padded past V, a placeholder) is never used as an index and still
+ * takes part in n-gram and word matching.  Elements the rule does not name keep their bits; columns V .. logits_ld are not
+ * touched.  A barrier separates the penalty from the bans, so a banned id ends at -inf; plain stores, no atomics: the same bits
+ * on every run.  hist, eos, bans, word_ids and word_off (int64, n_words + 1 offsets) are DEVICE arrays; a list of no entries
+ * may be NULL, hist too when n_hist == 0.  Checked before any launch: CMB_ERR_BAD_ARG for logits NULL, a negative count, a
+ * missing list, n_word_ids < n_words, B < 1, V < 1 or > 2^31 - 1, logits_ld < V, hist_ld < n_hist, penalty not finite or <= 0,
+ * ngram < 0, min_new < 0; then CMB_ERR_ALIGNMENT for logits not 4-byte or an int64 array not 8-byte aligned (any row stride
+ * and any row alignment of the logits are taken). */
+int cmb_decode_process(float* logits, int64_t logits_ld, int32_t B, int64_t V, const int64_t* hist, int64_t hist_ld,
+                       int64_t n_hist, float penalty, int64_t ngram, int64_t min_new, const int64_t* eos, int32_t n_eos,
+                       const int64_t* bans, int32_t n_bans, const int64_t* word_ids, int64_t n_word_ids, const int64_t* word_off,
+                       int32_t n_words, uint8_t* done, void* stream);
 /* Beam search between two decode steps: cmb_decode_next's place in the loop when rows = prompts * num_beams rows of a decode step
  * are the beams of `prompts` prompts (row r = prompt * num_beams + slot).  HF GenerationMixin._beam_search with do_sample = False,
  * length_penalty = 1, early_stopping = False, equal scores ordered by the lowest index; restated in torch in
