@@ -6,7 +6,18 @@ import math
 import pytest
 import torch
 
+import attn_check as A
+
 pytestmark = pytest.mark.gpu
+
+
+def _block_check(label, got, ref64, zero_ok=False):
+    """(o, lse, dq, dk, dv) per block of 16 rows against the fp64 reference (tests/attn_check.py), `gauss` tolerances: the
+    global-maximum assertions beside it are set by the early rows and let a wrong late tile through."""
+    for name, a, r in zip(A.OUTPUTS, got, ref64):
+        err, tol = A.check("gauss", name, a, r, zero_ok=zero_ok and name in ("dq", "dk"))
+        print(f"{label} {name}: {err:.3g} (tol {tol})")
+        assert err <= tol, f"{label} {name}: block error {err:.3g} > {tol}"
 
 
 def _ref(q, k, v, g):
@@ -37,6 +48,9 @@ def test_flash_bwd_matches_fp32_autograd(dev, B, S, H, HKV):
     # forward log-sum-exp: natural log of sum exp(scale * q.k), and interchangeable with the stock flash kernel's
     lse = out.grad_fn.saved_tensors[4]
     assert lse.shape == (B, H, S) and (lse - ref_lse).abs().max().item() < 2e-2
+    # fp64 reference on the same inputs; dO is w as the kernels receive it (autograd casts it to the output's bf16)
+    ref64 = A.reference(q.detach(), k.detach(), v.detach(), w.to(torch.bfloat16), A.causal_allow(S, device=dev))
+    assert A.lse_err(lse, ref64[1]) <= A.TOL["gauss"]["lse"], A.lse_err(lse, ref64[1])
     ke, ve = k.repeat_interleave(H // HKV, 1), v.repeat_interleave(H // HKV, 1)
     res = torch.ops.aten._scaled_dot_product_flash_attention(q, ke, ve, 0.0, True, False)
     assert (res[1] - lse).abs().max().item() < 2e-2
@@ -46,6 +60,7 @@ def test_flash_bwd_matches_fp32_autograd(dev, B, S, H, HKV):
     for name, a, b in (("dq", q.grad, qr.grad), ("dk", k.grad, kr.grad), ("dv", v.grad, vr.grad)):
         err = ((a.float() - b).abs().max() / b.abs().max()).item()
         assert err < 3e-2, f"{name}: rel err {err}"
+    _block_check(f"S={S} H={H}/{HKV}", (out, lse, q.grad, k.grad, v.grad), ref64)
     # bit-reproducible (no atomics)
     q2, k2, v2 = (t.detach().clone().requires_grad_() for t in (q, k, v))
     (ops.causal_attention(q2, k2, v2).float() * w).sum().backward()
@@ -86,6 +101,7 @@ def test_flash_key_padding_mask_matches_fp32_autograd(dev, B, S, H, HKV):
     for kvmask in masks:
         q, k, v = (t.transpose(1, 2).detach().requires_grad_() for t in (qs, ks, vs))
         out = ops.causal_attention(q, k, v, kvmask.to(dev))
+        lse = out.grad_fn.saved_tensors[4]
         qr, kr, vr = (t.transpose(1, 2).detach().float().requires_grad_() for t in (qs, ks, vs))
         dense = (torch.ones(S, S, dtype=torch.bool, device=dev).tril_()[None, None] & kvmask.to(dev)[:, None, None, :]) \
             | torch.eye(S, dtype=torch.bool, device=dev)[None, None]
@@ -97,6 +113,10 @@ def test_flash_key_padding_mask_matches_fp32_autograd(dev, B, S, H, HKV):
         for name, a, b in (("dq", q.grad, qr.grad), ("dk", k.grad, kr.grad), ("dv", v.grad, vr.grad)):
             err = ((a.float() - b).abs().max() / b.abs().max()).item()
             assert err < 3e-2, f"{name}: rel err {err}"
+        # rows that see only themselves (a padded prefix) have dq = dk = 0: block_errs' zero_ok
+        ref64 = A.reference(q.detach(), k.detach(), v.detach(), w.to(torch.bfloat16), A.causal_allow(S, kvmask, device=dev))
+        _block_check(f"S={S} masked", (out, lse, q.grad, k.grad, v.grad), ref64, zero_ok=True)
+        del ref64
         if not kvmask.all():             # a padded key receives gradient only from its own (ignored) query row
             pad = ~kvmask.to(dev)
             assert torch.isfinite(k.grad.float()).all() and torch.isfinite(out.float()).all()
@@ -227,6 +247,7 @@ def test_every_shipped_flash_variant(dev, masked):
         allow = allow & (key_valid[:, None, None, :] | torch.eye(S, dtype=torch.bool, device=dev)[None, None])
     ref = torch.softmax(s.masked_fill(~allow, float("-inf")), -1) @ vr.repeat_interleave(H // HKV, 1)
     (ref * w).sum().backward()
+    ref64 = A.reference(qr.detach(), kr.detach(), vr.detach(), w.to(torch.bfloat16), allow.expand(B, 1, S, S))
     results = {}
     default = L.load().cmb_knob_get(L.KNOB_FLASH)
     try:
@@ -234,7 +255,9 @@ def test_every_shipped_flash_variant(dev, masked):
             L.knob_set(L.KNOB_FLASH, knob)
             q, k, v = (t.transpose(1, 2).detach().requires_grad_() for t in (qs, ks, vs))
             out = ops.causal_attention(q, k, v, key_valid=key_valid)
+            lse = out.grad_fn.saved_tensors[4]
             (out.float() * w).sum().backward()
+            _block_check(f"knob {knob}", (out, lse, q.grad, k.grad, v.grad), ref64, zero_ok=masked)
             results[knob] = (out.detach(), q.grad, k.grad, v.grad)
             assert ((out.float() - ref).abs().max() / ref.abs().max()).item() < 2e-2, f"knob {knob}: forward"
             for name, a, b in (("dq", q.grad, qr.grad), ("dk", k.grad, kr.grad), ("dv", v.grad, vr.grad)):
