@@ -251,59 +251,43 @@ def _decode_fp8_tag(w: torch.Tensor):
     return (w.data_ptr(), w._version, w.dtype)             # _frozen_transposed's tag
 
 
-def decode_fp8_copies(holder: nn.Module, B: int, entries):
-    """The quantised copies — (e4m3 bytes, fp32 row factors) per linear — of the weights a decode step streams through
-    ``ops.decode_linear_fp8``, or None when the kernel or the quantiser does not take ONE of them: the step then runs on
-    the bf16 weights exactly as without the mode, and nothing is quantised or kept for it.  ``entries``: (owner, key, w, act)
-    per linear.  A copy is cached on its ``owner`` under ``key`` with _frozen_transposed's tag and rebuilt when the weight
-    moves or changes; the entry holds ``w`` itself, so that a packed ``w`` (which _fused_frozen_weight replaces by a new
-    tensor when a part changes) cannot hand its address to its successor while the copy lives.  Every weight that needs a
-    new copy is put to ``ops.decode_linear_fp8_weight_supported`` BEFORE any is quantised (a cached one was accepted when it
-    was made, and callers keep B within 16 rows); a refusal is remembered on ``holder`` against the same tags, so the
-    following steps ask nothing again, and stale copies of a refused set are dropped.  Callers have established the
-    five-launch conditions, so no owner is a ZeRO-3 unit.  The bf16 weights stay: prefill and training use them."""
+def _decode_quant_copies(fmt: str, holder: nn.Module, B: int, entries):
+    """The quantised copies a decode step streams in the format ``fmt`` ("fp8": (e4m3 bytes, fp32 row factors) per linear,
+    "fp4": (e2m1 nibbles, e8m0 block scales)), or None when ONE weight is refused: the step then runs on the bf16 weights and
+    nothing is quantised or kept.  ``entries``: (owner, key, w, act) per linear; a copy is cached on ``owner`` under ``key``
+    with _frozen_transposed's tag and the weight itself (so a replaced packed weight cannot hand its address on), and
+    rebuilt when the weight moves or changes.  Every weight that needs a new copy is put to
+    ``ops.decode_linear_<fmt>_weight_supported`` BEFORE any is quantised; a refusal is remembered on ``holder`` against the
+    same tags, so the following steps ask nothing again, and stale copies of a refused set are dropped."""
+    refused = "_decode_" + fmt + "_refused"
     tags = tuple(_decode_fp8_tag(w) for _, _, w, _ in entries)
-    if holder.__dict__.get("_decode_fp8_refused") == tags:
+    if holder.__dict__.get(refused) == tags:
         return None
     cached = [owner.__dict__.get(key) for owner, key, _, _ in entries]
     miss = [i for i, (c, tag) in enumerate(zip(cached, tags)) if c is None or c[0] != tag]
     if miss:
-        if not all(ops.decode_linear_fp8_weight_supported(B, entries[i][2], entries[i][3]) for i in miss):
-            holder.__dict__["_decode_fp8_refused"] = tags
+        supported = getattr(ops, "decode_linear_" + fmt + "_weight_supported")        # looked up when a step runs
+        if not all(supported(B, entries[i][2], entries[i][3]) for i in miss):
+            holder.__dict__[refused] = tags
             for owner, key, _, _ in entries:
                 owner.__dict__.pop(key, None)
             return None
-        holder.__dict__.pop("_decode_fp8_refused", None)
+        holder.__dict__.pop(refused, None)
+        quantise = getattr(ops, "decode_" + fmt + "_weight")
         for i in miss:
             owner, key, w, _ = entries[i]
-            cached[i] = owner.__dict__[key] = (tags[i], ops.decode_fp8_weight(w), w)
+            cached[i] = owner.__dict__[key] = (tags[i], quantise(w), w)
     return [c[1] for c in cached]
+
+
+def decode_fp8_copies(holder: nn.Module, B: int, entries):
+    """``_decode_quant_copies`` for e4m3.  Kept as a public name; the model code calls that function with the format."""
+    return _decode_quant_copies("fp8", holder, B, entries)
 
 
 def decode_fp4_copies(holder: nn.Module, B: int, entries):
-    """``decode_fp8_copies`` for the MXFP4 mode: the (e2m1 nibbles, e8m0 block scales) pair per linear that
-    ``ops.decode_linear_fp4`` streams, or None when the kernel does not take ONE of the weights (K % 32 != 0) — the step then
-    runs on the bf16 weights exactly as without the mode and nothing is quantised or kept.  The rules are that function's:
-    every weight that needs a new copy is put to ``ops.decode_linear_fp4_weight_supported`` before any is quantised, a refusal
-    is remembered on ``holder`` against the same tags, copies are cached on the owning module under ``key + "_fp4"``-style keys
-    of their own (the e4m3 copies live under other keys and are not touched) with _frozen_transposed's tag, and rebuilt when the
-    weight moves or changes."""
-    tags = tuple(_decode_fp8_tag(w) for _, _, w, _ in entries)
-    if holder.__dict__.get("_decode_fp4_refused") == tags:
-        return None
-    cached = [owner.__dict__.get(key) for owner, key, _, _ in entries]
-    miss = [i for i, (c, tag) in enumerate(zip(cached, tags)) if c is None or c[0] != tag]
-    if miss:
-        if not all(ops.decode_linear_fp4_weight_supported(B, entries[i][2], entries[i][3]) for i in miss):
-            holder.__dict__["_decode_fp4_refused"] = tags
-            for owner, key, _, _ in entries:
-                owner.__dict__.pop(key, None)
-            return None
-        holder.__dict__.pop("_decode_fp4_refused", None)
-        for i in miss:
-            owner, key, w, _ = entries[i]
-            cached[i] = owner.__dict__[key] = (tags[i], ops.decode_fp4_weight(w), w)
-    return [c[1] for c in cached]
+    """``_decode_quant_copies`` for MXFP4 (a refusal: K % 32 != 0).  Kept as a public name, like ``decode_fp8_copies``."""
+    return _decode_quant_copies("fp4", holder, B, entries)
 
 
 def decode_layer_fused(layer, x, cos, sin, kcache, vcache, t, key_mask, w_qkv, w_o, w_gate_up, w_down, fp8=None, fp4=None,
@@ -311,33 +295,30 @@ def decode_layer_fused(layer, x, cos, sin, kcache, vcache, t, key_mask, w_qkv, w
     """The five launches of a decode step: norm + QKV projection, attention on the cache, o_proj + skip connection,
     norm + gate / up projection + SwiGLU, down_proj + skip connection.  ``fp8``: the four (bytes, factors) pairs of
     ``decode_fp8_copies`` — the linears then stream those instead of the bf16 weights.  ``fp4``: the four (nibbles, scales)
-    pairs of ``decode_fp4_copies``, likewise (at most one of the two).  ``linear``: the bf16 linear, ``ops.decode_linear`` unless
-    given (``ops.decode_linear_wide`` at 17-64 rows)."""
+    pairs of ``decode_fp4_copies``, likewise (``fp4`` wins when both are given).  ``linear``: the bf16 linear,
+    ``ops.decode_linear`` unless given (``ops.decode_linear_wide`` at 17-64 rows)."""
+    return _five_launches(layer, x, (w_qkv, w_o, w_gate_up, w_down), fp8 if fp4 is None else fp4, fp4 is not None, linear,
+                          ops.decode_attention_any, cos, sin, kcache, vcache, t, key_mask)
+
+
+def _five_launches(layer, x, w, quant, fp4, linear, attend, *cache_args):
+    """The one body of ``decode_layer_fused`` / ``decode_layer_fused_multi`` and the layers' ``decode``: x [rows, 1, H] through
+    the bf16 weights ``w`` on ``linear`` (None: ``ops.decode_linear``) or, given ``quant``, their e4m3 (``fp4``: MXFP4) copies,
+    around ``attend`` on the three views of the QKV row and ``cache_args`` (cos, sin, the caches, the slot, the key mask)."""
+    if quant is None:
+        lin, mats = (ops.decode_linear if linear is None else linear), ((w[0],), (w[1],), (w[2],), (w[3],))
+    else:
+        lin, mats = (ops.decode_linear_fp4 if fp4 else ops.decode_linear_fp8), quant
     attn = layer.self_attn
-    B = x.shape[0]
+    rows = x.shape[0]
     nq, nk = attn.nh * attn.hd, attn.nkv * attn.hd
     n1, n2 = layer.input_layernorm, layer.post_attention_layernorm
-    x2 = x.reshape(B, -1)
-    if fp4 is not None:
-        q_qkv, q_o, q_gate_up, q_down = fp4
-        row = ops.decode_linear_fp4(x2, *q_qkv, norm_weight=n1.weight, eps=n1.variance_epsilon)
-        o = ops.decode_attention_any(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t, key_mask)
-        x2 = ops.decode_linear_fp4(o, *q_o, residual=x2)
-        inner = ops.decode_linear_fp4(x2, *q_gate_up, norm_weight=n2.weight, eps=n2.variance_epsilon, act="swiglu")
-        return ops.decode_linear_fp4(inner, *q_down, residual=x2).reshape(B, 1, -1)
-    if fp8 is not None:
-        q_qkv, q_o, q_gate_up, q_down = fp8
-        row = ops.decode_linear_fp8(x2, *q_qkv, norm_weight=n1.weight, eps=n1.variance_epsilon)
-        o = ops.decode_attention_any(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t, key_mask)
-        x2 = ops.decode_linear_fp8(o, *q_o, residual=x2)
-        inner = ops.decode_linear_fp8(x2, *q_gate_up, norm_weight=n2.weight, eps=n2.variance_epsilon, act="swiglu")
-        return ops.decode_linear_fp8(inner, *q_down, residual=x2).reshape(B, 1, -1)
-    lin = ops.decode_linear if linear is None else linear
-    row = lin(x2, w_qkv, norm_weight=n1.weight, eps=n1.variance_epsilon)
-    o = ops.decode_attention_any(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t, key_mask)
-    x2 = lin(o, w_o, residual=x2)
-    inner = lin(x2, w_gate_up, norm_weight=n2.weight, eps=n2.variance_epsilon, act="swiglu")
-    return lin(inner, w_down, residual=x2).reshape(B, 1, -1)
+    x2 = x.reshape(rows, -1)
+    row = lin(x2, *mats[0], norm_weight=n1.weight, eps=n1.variance_epsilon)
+    o = attend(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], *cache_args)
+    x2 = lin(o, *mats[1], residual=x2)
+    inner = lin(x2, *mats[2], norm_weight=n2.weight, eps=n2.variance_epsilon, act="swiglu")
+    return lin(inner, *mats[3], residual=x2).reshape(rows, 1, -1)
 
 
 def lookup_mask(key_mask: torch.Tensor, t0: int, Q: int) -> torch.Tensor:
@@ -353,20 +334,7 @@ def decode_layer_fused_multi(layer, x, cos, sin, kcache, vcache, t0, key_mask, w
     """``decode_layer_fused`` for Q consecutive tokens of ONE sequence, x [Q, 1, H]: the same five launches with
     ``ops.decode_attention_multi`` in the middle.  ``w``: the four bf16 weights; ``quant``: their e4m3 (``fp4``: MXFP4) copies,
     streamed instead when given."""
-    attn = layer.self_attn
-    Q = x.shape[0]
-    nq, nk = attn.nh * attn.hd, attn.nkv * attn.hd
-    n1, n2 = layer.input_layernorm, layer.post_attention_layernorm
-    if quant is None:
-        lin, mats = ops.decode_linear, [(wi,) for wi in w]
-    else:
-        lin, mats = (ops.decode_linear_fp4 if fp4 else ops.decode_linear_fp8), quant
-    x2 = x.reshape(Q, -1)
-    row = lin(x2, *mats[0], norm_weight=n1.weight, eps=n1.variance_epsilon)
-    o = ops.decode_attention_multi(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t0, key_mask)
-    x2 = lin(o, *mats[1], residual=x2)
-    inner = lin(x2, *mats[2], norm_weight=n2.weight, eps=n2.variance_epsilon, act="swiglu")
-    return lin(inner, *mats[3], residual=x2).reshape(Q, 1, -1)
+    return _five_launches(layer, x, w, quant, fp4, None, ops.decode_attention_multi, cos, sin, kcache, vcache, t0, key_mask)
 
 
 def decode_multi_fused_or_none(layer, x, cos, sin, kcache, vcache, t0, key_mask, fp8, fp4):
@@ -375,10 +343,29 @@ def decode_multi_fused_or_none(layer, x, cos, sin, kcache, vcache, t0, key_mask,
     a = layer.self_attn
     if isinstance(kcache, ops.KvCacheE4M3) or not ops.decode_attention_multi_supported(x.dtype, a.nh, a.nkv, a.hd, x.shape[0]):
         return None
-    found = layer.decode_operands(x, fp8, fp4) if fp4 else layer.decode_operands(x, fp8)
+    found = layer.decode_operands(x, fp8, fp4)
     if found is None:
         return None
     return decode_layer_fused_multi(layer, x, cos, sin, kcache, vcache, t0, key_mask, found[0], found[1], fp4=bool(fp4))
+
+
+def decode_step_operands(layer, x, fp8: bool = False, fp4: bool = False):
+    """THE condition under which a decoder layer runs a decode step of x [B, 1, H] as five launches: (the four bf16 weights,
+    their quantised copies or None, wide), or None for the stock sequence.  ``decode`` and ``decode_operands`` of both layer
+    classes ask here, so the per-launch loop and ``DecodeStepPlan`` cannot disagree.  ``fp4`` / ``fp8`` ask for the MXFP4 /
+    e4m3 copies (``fp4`` wins); None stands in their place when one weight is refused, and at wide rows
+    (``decode_wide_rows``), which stream the bf16 weights on ``ops.decode_linear_wide`` and get no quantised copy."""
+    a = layer.self_attn
+    B = x.shape[0]
+    wide = decode_wide_rows(layer, B)
+    if not (x.dtype == torch.bfloat16 and (wide or (B <= ops.DECODE_LINEAR_MAX_ROWS and ops.decode_linear_enabled(B)))
+            and use_decode_kernel(x, a.nh, a.nkv, a.hd)):
+        return None
+    fmt = None if wide else ("fp4" if fp4 else ("fp8" if fp8 else None))
+    w, entries = layer.decode_entries(fmt)
+    if not decode_linear_weights(x, *w, (layer.input_layernorm, layer.post_attention_layernorm), wide):
+        return None
+    return w, (None if fmt is None else _decode_quant_copies(fmt, layer, B, entries)), wide
 
 
 class LlamaAttention(nn.Module):
@@ -486,69 +473,37 @@ class LlamaDecoderLayer(nn.Module):
         x, h = ops.add_rmsnorm(x, a, n2.weight, n2.variance_epsilon)  # x + a and norm(x + a) in one pass
         return self.mlp(h, residual=x)
 
-    def _decode_fp4(self, B, w):
+    def decode_entries(self, fmt=None):
+        """(the four weights of a five-launch step, None where a projection is trainable or biased; with ``fmt`` their (owner,
+        key, weight, act) entries for ``_decode_quant_copies``, else None).  The packed ones are _fused_frozen_weight's."""
         a, mlp = self.self_attn, self.mlp
-        return decode_fp4_copies(self, B, ((a, "_w_qkv_fp4", w[0], None), (a.o_proj, "_w_fp4", w[1], None),
-                                           (mlp, "_w_gate_up_fp4", w[2], "swiglu"), (mlp.down_proj, "_w_fp4", w[3], None)))
+        w = (_fused_frozen_weight(a, "_w_qkv", (a.q_proj, a.k_proj, a.v_proj)),
+             a.o_proj.weight if _frozen_plain(a.o_proj) else None,
+             _fused_frozen_weight(mlp, "_w_gate_up", (mlp.gate_proj, mlp.up_proj)),
+             mlp.down_proj.weight if _frozen_plain(mlp.down_proj) else None)
+        if fmt is None:
+            return w, None
+        return w, ((a, "_w_qkv_" + fmt, w[0], None), (a.o_proj, "_w_" + fmt, w[1], None),
+                   (mlp, "_w_gate_up_" + fmt, w[2], "swiglu"), (mlp.down_proj, "_w_" + fmt, w[3], None))
 
     def decode_operands(self, x, fp8=False, fp4=False):
-        """(the four weights, their e4m3 copies or None) when ``decode`` runs a step of x [B, 1, H] as five launches, else
-        None.  ``fp8``: ask for the e4m3 copies; None in their place when one weight is refused.  ``fp4``: the same with the
-        MXFP4 copies in that place.  These are ``decode``'s own
-        conditions, restated for ``DecodeStepPlan`` (asked once per ``generate()`` call) so that the per-launch loop, the
-        yardstick of the one-call step, stays line for line what it was."""
-        a, mlp = self.self_attn, self.mlp
-        wide = decode_wide_rows(self, x.shape[0])           # 17-64 rows behind the wide switch: ops.decode_linear_wide
-        if x.dtype == torch.bfloat16 and (wide or (x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS
-                                                   and ops.decode_linear_enabled(x.shape[0]))) \
-                and use_decode_kernel(x, a.nh, a.nkv, a.hd):
-            # the packed copies are the prefill's (_fused_frozen_weight: frozen bias-free projections only)
-            w = (_fused_frozen_weight(a, "_w_qkv", (a.q_proj, a.k_proj, a.v_proj)),
-                 a.o_proj.weight if _frozen_plain(a.o_proj) else None,
-                 _fused_frozen_weight(mlp, "_w_gate_up", (mlp.gate_proj, mlp.up_proj)),
-                 mlp.down_proj.weight if _frozen_plain(mlp.down_proj) else None)
-            if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm), wide):
-                if wide:
-                    return w, None
-                if fp4:
-                    return w, self._decode_fp4(x.shape[0], w)
-                q8 = None
-                if fp8:
-                    q8 = decode_fp8_copies(self, x.shape[0], ((a, "_w_qkv_fp8", w[0], None), (a.o_proj, "_w_fp8", w[1], None),
-                                                              (mlp, "_w_gate_up_fp8", w[2], "swiglu"),
-                                                              (mlp.down_proj, "_w_fp8", w[3], None)))
-                return w, q8
-        return None
+        """(the four weights, their e4m3 — ``fp4``: MXFP4 — copies or None) when ``decode`` runs a step of x [B, 1, H] as five
+        launches, else None: ``decode_step_operands``, the condition ``decode`` runs on, for ``DecodeStepPlan``."""
+        found = decode_step_operands(self, x, fp8, fp4)
+        return None if found is None else found[:2]
 
     def decode(self, x, cos, sin, kcache, vcache, t, key_mask, fp8=False, fp4=False):
         """``fp8``: stream e4m3 copies of the weights where the five-launch step is taken (``ops.decode_fp8_enabled``,
         resolved once by ``generate``).  ``fp4``: MXFP4 copies instead (``ops.decode_fp4_enabled``); ``generate`` never sets
         both (``ops.decode_weight_format``), and ``fp4`` wins here if a caller does.  At 17-64 rows with the wide switch on
         (``decode_wide_rows``) the five launches run on ``ops.decode_linear_wide`` and the bf16 weights."""
-        a, mlp = self.self_attn, self.mlp
-        wide = decode_wide_rows(self, x.shape[0])           # 17-64 rows behind the wide switch: ops.decode_linear_wide
-        if x.dtype == torch.bfloat16 and (wide or (x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS
-                                                   and ops.decode_linear_enabled(x.shape[0]))) \
-                and use_decode_kernel(x, a.nh, a.nkv, a.hd):
-            # the packed copies are the prefill's (_fused_frozen_weight: frozen bias-free projections only)
-            w = (_fused_frozen_weight(a, "_w_qkv", (a.q_proj, a.k_proj, a.v_proj)),
-                 a.o_proj.weight if _frozen_plain(a.o_proj) else None,
-                 _fused_frozen_weight(mlp, "_w_gate_up", (mlp.gate_proj, mlp.up_proj)),
-                 mlp.down_proj.weight if _frozen_plain(mlp.down_proj) else None)
-            if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm), wide):
-                if wide:     # bf16 weights whatever fp8 / fp4 say: no quantised copies are made for more than 16 rows
-                    return decode_layer_fused(self, x, cos, sin, kcache, vcache, t, key_mask, *w, linear=ops.decode_linear_wide)
-                if fp4:
-                    return decode_layer_fused(self, x, cos, sin, kcache, vcache, t, key_mask, *w,
-                                              fp4=self._decode_fp4(x.shape[0], w))
-                q8 = None
-                if fp8:
-                    q8 = decode_fp8_copies(self, x.shape[0], ((a, "_w_qkv_fp8", w[0], None), (a.o_proj, "_w_fp8", w[1], None),
-                                                              (mlp, "_w_gate_up_fp8", w[2], "swiglu"),
-                                                              (mlp.down_proj, "_w_fp8", w[3], None)))
-                return decode_layer_fused(self, x, cos, sin, kcache, vcache, t, key_mask, *w, fp8=q8)
-        x = x + self.self_attn.decode(self.input_layernorm(x), cos, sin, kcache, vcache, t, key_mask)
-        return x + self.mlp(self.post_attention_layernorm(x))
+        found = decode_step_operands(self, x, fp8, fp4)
+        if found is None:
+            x = x + self.self_attn.decode(self.input_layernorm(x), cos, sin, kcache, vcache, t, key_mask)
+            return x + self.mlp(self.post_attention_layernorm(x))
+        w, quant, wide = found
+        return _five_launches(self, x, w, quant, fp4, ops.decode_linear_wide if wide else None, ops.decode_attention_any,
+                              cos, sin, kcache, vcache, t, key_mask)
 
     def decode_multi(self, x, cos, sin, kcache, vcache, t0, key_mask, fp8=False, fp4=False):
         """``decode`` for Q consecutive tokens of ONE sequence, x [Q, 1, H] (the verify step of prompt-lookup decoding): five
@@ -845,9 +800,10 @@ def filter_logits_top_k_top_p(logits: torch.Tensor, top_k=None, top_p=None) -> t
     return logits
 
 
-def _decode_logits_operands(self, x: torch.Tensor, fp8: bool = False, fp4: bool = False):
-    """(lm_head weight, its e4m3 — with ``fp4`` its MXFP4 — copy or None) when ``_decode_logits`` takes its one-launch arm, else None: that function's
-    condition restated for ``DecodeStepPlan``, so that the per-launch loop stays what it was."""
+def _decode_logits_found(self, x: torch.Tensor, fp8: bool, fp4: bool):
+    """(lm_head weight, its e4m3 — with ``fp4`` its MXFP4 — copy or None, wide) when a decode step's logits are one launch,
+    else None: the one condition ``_decode_logits`` and ``DecodeStepPlan`` share.  A refused MXFP4 head falls back to bf16,
+    not to e4m3; at wide rows (``decode_wide_rows``) no copy is made."""
     model, head = self.model, self.lm_head
     a = model.layers[0].self_attn if len(model.layers) else None        # a decoder without layers keeps the stock line
     B = x.shape[0]
@@ -856,14 +812,16 @@ def _decode_logits_operands(self, x: torch.Tensor, fp8: bool = False, fp4: bool 
             and (wide or (B <= ops.DECODE_LINEAR_MAX_ROWS and ops.decode_linear_enabled(B))) \
             and _frozen_plain(head) and not model.norm.weight.requires_grad and model.norm.weight.dtype == torch.bfloat16 \
             and (ops.decode_linear_wide_supported if wide else ops.decode_linear_supported)(x[:, 0], head.weight):
-        if wide:
-            return head.weight, None
-        if fp4:
-            q8 = decode_fp4_copies(head, B, ((head, "_w_fp4", head.weight, None),))
-        else:
-            q8 = decode_fp8_copies(head, B, ((head, "_w_fp8", head.weight, None),)) if fp8 else None
-        return head.weight, (None if q8 is None else q8[0])
+        fmt = None if wide else ("fp4" if fp4 else ("fp8" if fp8 else None))
+        quant = None if fmt is None else _decode_quant_copies(fmt, head, B, ((head, "_w_" + fmt, head.weight, None),))
+        return head.weight, (None if quant is None else quant[0]), wide
     return None
+
+
+def _decode_logits_operands(self, x: torch.Tensor, fp8: bool = False, fp4: bool = False):
+    """(lm_head weight, its quantised copy or None) when ``_decode_logits`` takes its one-launch arm, else None."""
+    found = _decode_logits_found(self, x, fp8, fp4)
+    return None if found is None else found[:2]
 
 
 def _decode_logits(self, x: torch.Tensor, fp8: bool = False, fp4: bool = False) -> torch.Tensor:
@@ -872,28 +830,16 @@ def _decode_logits(self, x: torch.Tensor, fp8: bool = False, fp4: bool = False) 
     ``fp8``: that launch streams the lm_head's e4m3 copy (``ops.decode_linear_fp8``) where the kernel takes it; ``fp4``: its
     MXFP4 copy (``ops.decode_linear_fp4``).  At 17-64 rows with the wide switch on (``decode_wide_rows``) the one launch is
     ``ops.decode_linear_wide`` on the bf16 lm_head, whatever ``fp8`` / ``fp4`` say."""
-    model, head = self.model, self.lm_head
-    a = model.layers[0].self_attn if len(model.layers) else None        # a decoder without layers keeps the stock line
-    B = x.shape[0]
-    wide = decode_wide_rows(self, B)
-    if a is not None and use_decode_kernel(x, a.nh, a.nkv, a.hd) and x.dtype == torch.bfloat16 \
-            and (wide or (B <= ops.DECODE_LINEAR_MAX_ROWS and ops.decode_linear_enabled(B))) \
-            and _frozen_plain(head) and not model.norm.weight.requires_grad and model.norm.weight.dtype == torch.bfloat16 \
-            and (ops.decode_linear_wide_supported if wide else ops.decode_linear_supported)(x[:, 0], head.weight):
-        if wide:
-            return ops.decode_linear_wide(x[:, 0], head.weight, norm_weight=model.norm.weight, eps=model.norm.variance_epsilon,
-                                          out_dtype=torch.float32)
-        q4 = decode_fp4_copies(head, B, ((head, "_w_fp4", head.weight, None),)) if fp4 else None
-        if q4 is not None:
-            return ops.decode_linear_fp4(x[:, 0], *q4[0], norm_weight=model.norm.weight, eps=model.norm.variance_epsilon,
-                                         out_dtype=torch.float32)
-        q8 = decode_fp8_copies(head, B, ((head, "_w_fp8", head.weight, None),)) if fp8 and not fp4 else None
-        if q8 is not None:
-            return ops.decode_linear_fp8(x[:, 0], *q8[0], norm_weight=model.norm.weight, eps=model.norm.variance_epsilon,
-                                         out_dtype=torch.float32)
-        return ops.decode_linear(x[:, 0], head.weight, norm_weight=model.norm.weight, eps=model.norm.variance_epsilon,
-                                 out_dtype=torch.float32)
-    return head(model.norm(x)[:, 0]).float()
+    norm = self.model.norm
+    found = _decode_logits_found(self, x, fp8, fp4)
+    if found is None:
+        return self.lm_head(norm(x)[:, 0]).float()
+    w, quant, wide = found
+    if quant is None:
+        lin, mat = (ops.decode_linear_wide if wide else ops.decode_linear), (w,)
+    else:
+        lin, mat = (ops.decode_linear_fp4 if fp4 else ops.decode_linear_fp8), quant
+    return lin(x[:, 0], *mat, norm_weight=norm.weight, eps=norm.variance_epsilon, out_dtype=torch.float32)
 
 
 class DecodeStepPlan:
@@ -983,9 +929,7 @@ class DecodeStepPlan:
 
     def step(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, t: int, key_valid: torch.Tensor) -> torch.Tensor:
         """fp32 logits [B, V] (the plan's buffer, overwritten by the next step) of the token whose embeddings are x [B, H]."""
-        if self.kv8 is not None:
-            return ops.decode_step(self.desc, self.table, x, cos, sin, t, key_valid, self.ws, self.logits, kv8=self.kv8)
-        return ops.decode_step(self.desc, self.table, x, cos, sin, t, key_valid, self.ws, self.logits)
+        return ops.decode_step(self.desc, self.table, x, cos, sin, t, key_valid, self.ws, self.logits, kv8=self.kv8)
 
 
 def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: int = 16, do_sample: bool = False,
@@ -1067,15 +1011,8 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
             return _beam_search(self, logits, kv_out, valid, L, int(max_new_tokens), eos_token_id, kwargs.get("pad_token_id"),
                                 beams, _kv8_wanted(self, dev, kv_out))
         Lmax = L + max_new_tokens
-        if _kv8_wanted(self, dev, kv_out):          # e4m3 K / V cache, opt-in: resolved once per call
-            caches = _kv8_prefill(kv_out, B, 1, nh_kv, L, Lmax, hd, dev)
-        else:
-            caches = []
-            for k, v in kv_out:
-                kc = torch.zeros(B, nh_kv, Lmax, hd, dtype=k.dtype, device=dev)
-                vc = torch.zeros_like(kc)
-                kc[:, :, :L], vc[:, :, :L] = k, v
-                caches.append((kc, vc))
+        # e4m3 K / V cache, opt-in: resolved once per call
+        caches = (_kv8_prefill if _kv8_wanted(self, dev, kv_out) else _bf16_prefill)(kv_out, B, 1, nh_kv, L, Lmax, hd, dev)
         key_mask = torch.zeros(B, Lmax, dtype=torch.bool, device=dev)
         key_mask[:, :L] = valid
         n_tok = valid.long().sum(1)
@@ -1084,24 +1021,21 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
         theta = float(getattr(self.config, "rope_theta", 10000.0))
         fmt = ops.decode_weight_format(self.config)            # e4m3 or MXFP4 weight stream, opt-in; both on raises
         fp8, fp4 = fmt == "fp8", fmt == "fp4"
-        low = {"fp4": True} if fp4 else {}                      # (the fp8 mode's calls stay what they were)
         if lookup is not None:
             return _lookup_loop(self, logits, caches, key_mask, n_tok, L, int(max_new_tokens), eos_token_id, prompt_ids,
                                 prompt_mask, lookup, _draft_fn, fp8, fp4, hd, theta)
         plan = None                                                                       # one library call per token, opt-in
         if max_new_tokens > 1 and ops.decode_step_enabled(getattr(self.config, "decode_step_fused", False)):
-            plan = DecodeStepPlan.build(self, B, caches, Lmax - 1, fp8, **low)
+            plan = DecodeStepPlan.build(self, B, caches, Lmax - 1, fp8, fp4)
         sampled = bool(do_sample and temperature > 0)
         proc = None if spec is None else ops.DecodeProcess(spec, dev)          # the lists go to the device once per call
-        pk = {} if proc is None else {"proc": proc}                              # (without processors the calls stay what they were)
         if plan is not None and (not sampled or ops.decode_sample_enabled(getattr(self.config, "decode_sample_device", False))):
             emb = model.embed_tokens.weight
-            if emb.dtype == torch.bfloat16 and emb.stride(1) == 1 and emb.stride(0) % 8 == 0 and emb.data_ptr() % 16 == 0 \
-                    and emb.shape[0] >= logits.shape[1] and (eos_token_id is None or 0 <= int(eos_token_id) < emb.shape[0]):
+            if _fused_embedding_ok(emb, logits.shape[1], eos_token_id):
                 if sampled:
                     return _sample_fused(plan, emb, logits, key_mask, n_tok, L, max_new_tokens, eos_token_id, hd, theta,
-                                         temperature, top_k, top_p, **pk)
-                return _greedy_fused(plan, emb, logits, key_mask, n_tok, L, max_new_tokens, eos_token_id, hd, theta, **pk)
+                                         temperature, top_k, top_p, proc)
+                return _greedy_fused(plan, emb, logits, key_mask, n_tok, L, max_new_tokens, eos_token_id, hd, theta, proc)
         if proc is not None:                     # the history the kernel reads, and the eos set a row is done on
             hist = torch.zeros(B, max_new_tokens, dtype=torch.int64, device=dev)
             eos_set = torch.tensor(spec.eos, dtype=torch.int64, device=dev)
@@ -1127,11 +1061,24 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
             x = model.embed_tokens(nxt)[:, None, :].to(model.llm_dtype)
             if plan is not None:                 # sampling: torch's warpers above, the layers and the logits in one call
                 logits = plan.step(x[:, 0], cos, sin, t, key_mask)
-                continue
-            for layer, (kc, vc) in zip(model.layers, caches):
-                x = layer.decode(x, cos, sin, kc, vc, t, key_mask, fp8=fp8, **low)      # [B, Lmax]: the step reads columns 0..t
-            logits = _decode_logits(self, x, fp8, **low)
+            else:
+                logits = _decode_token(self, x, cos, sin, caches, t, key_mask, fp8, fp4)
         return torch.stack(out_ids, 1)
+
+
+def _decode_token(self, x, cos, sin, caches, t: int, key_mask, fp8: bool, fp4: bool) -> torch.Tensor:
+    """The per-launch decode step: x [B, 1, H] through every layer's ``decode`` (K / V into cache slot ``t``; the step reads
+    columns 0..t of ``key_mask`` [B, Lmax]), then ``_decode_logits``."""
+    for layer, (kc, vc) in zip(self.model.layers, caches):
+        x = layer.decode(x, cos, sin, kc, vc, t, key_mask, fp8=fp8, fp4=fp4)
+    return _decode_logits(self, x, fp8, fp4)
+
+
+def _fused_embedding_ok(emb: torch.Tensor, V: int, eos_token_id) -> bool:
+    """Whether the fused selection kernels can read rows of the embedding table ``emb`` for a vocabulary of ``V``: bf16 rows,
+    aligned, at least V of them, and the eos id (if any) one of them."""
+    return (emb.dtype == torch.bfloat16 and emb.stride(1) == 1 and emb.stride(0) % 8 == 0 and emb.data_ptr() % 16 == 0
+            and emb.shape[0] >= V and (eos_token_id is None or 0 <= int(eos_token_id) < emb.shape[0]))
 
 
 def _lookup_args(self, inputs, num_tokens, max_ngram, do_sample, temperature, beams):
@@ -1170,10 +1117,9 @@ def lookup_step(self, ids, caches, t0: int, n_tok0: int, key_mask, fp8: bool = F
     pos = torch.arange(n_tok0, n_tok0 + Q, dtype=torch.int64, device=ids.device)
     cos, sin = ops.rope_table(pos[:, None], hd, theta)
     x = model.embed_tokens(ids)[:, None, :].to(model.llm_dtype)
-    low = {"fp4": True} if fp4 else {}
     for layer, (kc, vc) in zip(model.layers, caches):
-        x = layer.decode_multi(x, cos, sin, kc, vc, t0, key_mask, fp8=fp8, **low)
-    return _decode_logits(self, x, fp8, **low)
+        x = layer.decode_multi(x, cos, sin, kc, vc, t0, key_mask, fp8=fp8, fp4=fp4)
+    return _decode_logits(self, x, fp8, fp4)
 
 
 def _lookup_loop(self, logits, caches, key_mask, n_tok, L: int, max_new_tokens: int, eos_token_id, prompt_ids, prompt_mask,
@@ -1195,7 +1141,6 @@ def _lookup_loop(self, logits, caches, key_mask, n_tok, L: int, max_new_tokens: 
     src = prompt_ids[0] if prompt_mask is None else prompt_ids[0][prompt_mask[0].bool()]
     src = [int(i) for i in src.tolist()]
     n0 = int(n_tok[0])
-    low = {"fp4": True} if fp4 else {}
     out = [int(logits.argmax(-1)[0])]
     stats = {"steps": 0, "drafted": 0, "accepted": 0}
     while len(out) < max_new_tokens and not (eos is not None and out[-1] == eos):
@@ -1208,9 +1153,7 @@ def _lookup_loop(self, logits, caches, key_mask, n_tok, L: int, max_new_tokens: 
             key_mask[:, t] = True
             cos, sin = ops.rope_table((n_tok + step)[:, None], hd, theta)
             x = model.embed_tokens(torch.tensor([out[-1]], dtype=torch.int64, device=logits.device))[:, None, :].to(model.llm_dtype)
-            for layer, (kc, vc) in zip(model.layers, caches):
-                x = layer.decode(x, cos, sin, kc, vc, t, key_mask, fp8=fp8, **low)
-            out.append(int(_decode_logits(self, x, fp8, **low).argmax(-1)[0]))
+            out.append(int(_decode_token(self, x, cos, sin, caches, t, key_mask, fp8, fp4).argmax(-1)[0]))
             continue
         ids = torch.tensor([out[-1]] + draft, dtype=torch.int64, device=logits.device)
         picked = lookup_step(self, ids, caches, t, n0 + step, key_mask, fp8, fp4).argmax(-1).tolist()
@@ -1265,16 +1208,31 @@ def _kv8_prefill(kv_out: list, B: int, nb: int, nkv: int, L: int, Lmax: int, hd:
     return caches
 
 
+def _bf16_prefill(kv_out: list, B: int, nb: int, nkv: int, L: int, Lmax: int, hd: int, dev):
+    """The caches of ``B * nb`` rows in the prefill's own dtype: zeros of ``Lmax`` slots per layer with the prefill's (k, v) in
+    slots 0 .. L - 1, each prompt's columns copied into all of its ``nb`` beams' rows (1 = no beams)."""
+    caches = []
+    for k, v in kv_out:
+        kc = torch.zeros(B * nb, nkv, Lmax, hd, dtype=k.dtype, device=dev)
+        vc = torch.zeros_like(kc)
+        kc.view(B, nb, nkv, Lmax, hd)[:, :, :, :L] = k[:, None]
+        vc.view(B, nb, nkv, Lmax, hd)[:, :, :, :L] = v[:, None]
+        caches.append((kc, vc))
+    return caches
+
+
 def _greedy_fused(plan, emb, logits, key_mask, n_tok, L0: int, max_new_tokens: int, eos_token_id, hd: int, theta: float,
-                  proc=None):
+                  proc=None, select=None):
     """The greedy loop as two library calls per token and no ATen call: ``ops.decode_next`` (selection, eos rule, position,
-    key mask, embedding row, RoPE table) then ``ops.decode_step`` (every layer and the lm_head).  The first token comes from
-    the prefill ``logits`` through the same selection.  With an eos id the host reads ``done`` only every
-    ``ops.DECODE_STEP_POLL`` steps, so the loop may run up to that many tokens past the point where every row is done;
-    ``ops.trim_after_all_done`` cuts the result back to the column where the per-token loop stops.  ``proc`` (an
-    ``ops.DecodeProcess``): one more library call per token, ``ops.decode_process`` on the logits before the selection, reading
-    the ids in ``out``; a row that ends on a secondary eos is marked done by that call one step later, so the trim looks for
-    ids of the set (``ops.trim_after_all_done_set``)."""
+    key mask, embedding row, RoPE table; ``select``, given by ``_sample_fused``, stands in for it) then ``ops.decode_step``
+    (every layer and the lm_head).  The first token comes from the prefill ``logits`` through the same selection.  With an
+    eos id the host reads ``done`` only every ``ops.DECODE_STEP_POLL`` steps, so the loop may run up to that many tokens
+    past the point where every row is done; ``ops.trim_after_all_done`` cuts the result back to the column where the
+    per-token loop stops.  ``proc`` (an ``ops.DecodeProcess``): one more library call per token, ``ops.decode_process`` on
+    the logits before the selection (HF's order: processors, then warpers), reading the ids in ``out``; a row that ends on a
+    secondary eos is marked done by that call one step later, so the trim looks for ids of the set
+    (``ops.trim_after_all_done_set``)."""
+    select = ops.decode_next if select is None else select
     B = logits.shape[0]
     dev = logits.device
     eos = -1 if eos_token_id is None else int(eos_token_id)
@@ -1289,7 +1247,7 @@ def _greedy_fused(plan, emb, logits, key_mask, n_tok, L0: int, max_new_tokens: i
     for step in range(max_new_tokens):
         if proc is not None:
             ops.decode_process(logits, out, step, proc, done)
-        ops.decode_next(logits, eos, done, out, step, n_tok, pos, key_mask, L0 + step, emb, x, hd, theta, cos, sin)
+        select(logits, eos, done, out, step, n_tok, pos, key_mask, L0 + step, emb, x, hd, theta, cos, sin)
         n = step + 1
         if n == max_new_tokens or (eos >= 0 and n % ops.DECODE_STEP_POLL == 0 and bool(done.all())):
             break
@@ -1302,42 +1260,23 @@ def _greedy_fused(plan, emb, logits, key_mask, n_tok, L0: int, max_new_tokens: i
 
 def _sample_fused(plan, emb, logits, key_mask, n_tok, L0: int, max_new_tokens: int, eos_token_id, hd: int, theta: float,
                   temperature: float, top_k, top_p, proc=None):
-    """``_greedy_fused`` with ``ops.decode_sample`` in the place of ``ops.decode_next``: temperature, top-k, top-p and the draw
-    on the device, so sampled decoding too is two library calls per token and no ATen call.  ``top_k`` None / 0 and ``top_p``
-    None / >= 1 mean off; ``top_p <= 0`` raises what ``filter_logits_top_k_top_p`` raises.  The seed is one int64 drawn once
-    per call ON the device from torch's generator (``torch.manual_seed`` governs it, the host never waits for it); the draws of
-    a call are counted by (element, row, step) under that seed, so they are not torch.multinomial's stream.  ``proc``: as in
-    ``_greedy_fused`` — the processors run before the warpers, HF's order."""
+    """``_greedy_fused`` with ``ops.decode_sample`` as the selection: temperature, top-k, top-p and the draw on the device, so
+    sampled decoding too is two library calls per token and no ATen call.  ``top_k`` None / 0 and ``top_p`` None / >= 1 mean
+    off; ``top_p <= 0`` raises what ``filter_logits_top_k_top_p`` raises.  The seed is one int64 drawn once per call ON the
+    device from torch's generator (``torch.manual_seed`` governs it, the host never waits for it), before any buffer of the
+    loop is allocated; the draws of a call are counted by (element, row, step) under that seed, so they are not
+    torch.multinomial's stream."""
     k = 0 if top_k is None else max(int(top_k), 0)
     p = 1.0 if top_p is None or float(top_p) >= 1.0 else float(top_p)
     if not 0.0 < p:
         raise ValueError(f"`top_p` has to be a float > 0 and <= 1, but is {top_p}")
-    B = logits.shape[0]
-    dev = logits.device
     inv_t = float(torch.tensor(1.0 / float(temperature), dtype=torch.float32))        # float32(1 / T), formed on the host
-    seed = torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64, device=dev)
-    eos = -1 if eos_token_id is None else int(eos_token_id)
-    out = torch.zeros(B, max_new_tokens, dtype=torch.int64, device=dev)
-    done = torch.zeros(B, dtype=torch.bool, device=dev) if eos >= 0 else None
-    pos = torch.empty(B, dtype=torch.int64, device=dev)
-    x = torch.empty(B, plan.H, dtype=torch.bfloat16, device=dev)
-    cos = torch.empty(B, hd // 2, dtype=torch.float32, device=dev)
-    sin = torch.empty_like(cos)
-    n_tok = n_tok.contiguous()
-    n = 0
-    for step in range(max_new_tokens):
-        if proc is not None:
-            ops.decode_process(logits, out, step, proc, done)
-        ops.decode_sample(logits, inv_t, k, p, seed, eos, done, out, step, n_tok, pos, key_mask, L0 + step, emb, x, hd, theta,
-                          cos, sin)
-        n = step + 1
-        if n == max_new_tokens or (eos >= 0 and n % ops.DECODE_STEP_POLL == 0 and bool(done.all())):
-            break
-        logits = plan.step(x, cos, sin, L0 + step, key_mask)
-    ids = out[:, :n]
-    if eos >= 0:
-        ids = ops.trim_after_all_done(ids, eos) if proc is None else ops.trim_after_all_done_set(ids, proc.spec.eos)
-    return ids.contiguous()
+    seed = torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64, device=logits.device)
+
+    def select(logits, *rest):
+        ops.decode_sample(logits, inv_t, k, p, seed, *rest)
+
+    return _greedy_fused(plan, emb, logits, key_mask, n_tok, L0, max_new_tokens, eos_token_id, hd, theta, proc, select)
 
 
 def _beam_search(self, logits, kv_out, valid, L: int, max_new_tokens: int, eos_token_id, pad_token_id, nb: int,
@@ -1356,13 +1295,7 @@ def _beam_search(self, logits, kv_out, valid, L: int, max_new_tokens: int, eos_t
     R = B * nb
     nh_kv, hd = model.layers[0].self_attn.nkv, model.layers[0].self_attn.hd
     Lmax = L + max_new_tokens
-    caches = _kv8_prefill(kv_out, B, nb, nh_kv, L, Lmax, hd, dev) if kv8 else []
-    for k, v in ([] if kv8 else kv_out):
-        kc = torch.zeros(R, nh_kv, Lmax, hd, dtype=k.dtype, device=dev)
-        vc = torch.zeros_like(kc)
-        kc.view(B, nb, nh_kv, Lmax, hd)[:, :, :, :L] = k[:, None]
-        vc.view(B, nb, nh_kv, Lmax, hd)[:, :, :, :L] = v[:, None]
-        caches.append((kc, vc))
+    caches = (_kv8_prefill if kv8 else _bf16_prefill)(kv_out, B, nb, nh_kv, L, Lmax, hd, dev)
     key_mask = torch.zeros(R, Lmax, dtype=torch.bool, device=dev)
     key_mask[:, :L] = valid.repeat_interleave(nb, dim=0)
     n_tok = valid.long().sum(1).repeat_interleave(nb).contiguous()
@@ -1370,15 +1303,13 @@ def _beam_search(self, logits, kv_out, valid, L: int, max_new_tokens: int, eos_t
     theta = float(getattr(self.config, "rope_theta", 10000.0))
     fmt = ops.decode_weight_format(self.config)
     fp8, fp4 = fmt == "fp8", fmt == "fp4"
-    low = {"fp4": True} if fp4 else {}
     fill = beam_fill(pad_token_id, eos_token_id)
     plan = None
     if max_new_tokens > 1 and ops.decode_step_enabled(getattr(self.config, "decode_step_fused", False)):
-        plan = DecodeStepPlan.build(self, R, caches, Lmax - 1, fp8, **low)
+        plan = DecodeStepPlan.build(self, R, caches, Lmax - 1, fp8, fp4)
     if plan is not None and not kv8 and R <= ops.DECODE_BEAM_MAX and V >= 2 and V * nb < 2 ** 31:
         emb = model.embed_tokens.weight
-        if emb.dtype == torch.bfloat16 and emb.stride(1) == 1 and emb.stride(0) % 8 == 0 and emb.data_ptr() % 16 == 0 \
-                and emb.shape[0] >= V and (eos_token_id is None or 0 <= int(eos_token_id) < emb.shape[0]):
+        if _fused_embedding_ok(emb, V, eos_token_id):
             return _beam_fused(plan, emb, logits, key_mask, n_tok, L, max_new_tokens, eos_token_id, fill, nb, hd, theta)
     state = BeamState(B, nb, max_new_tokens, dev)
     first = (torch.arange(B, device=dev) * nb)[:, None]
@@ -1397,10 +1328,8 @@ def _beam_search(self, logits, kv_out, valid, L: int, max_new_tokens: int, eos_t
         x = model.embed_tokens(tok.reshape(-1))[:, None, :].to(model.llm_dtype)
         if plan is not None:
             logits = plan.step(x[:, 0], cos, sin, t, key_mask)
-            continue
-        for layer, (kc, vc) in zip(model.layers, caches):
-            x = layer.decode(x, cos, sin, kc, vc, t, key_mask, fp8=fp8, **low)
-        logits = _decode_logits(self, x, fp8, **low)
+        else:
+            logits = _decode_token(self, x, cos, sin, caches, t, key_mask, fp8, fp4)
     return beam_result(state, fill)
 
 

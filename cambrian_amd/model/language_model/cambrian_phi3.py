@@ -32,9 +32,8 @@ except Exception:  # pragma: no cover
 
 from ... import lib as L
 from ... import ops
-from .cambrian_llama import (CambrianLlamaForCausalLM, CambrianLlamaModel, HipRMSNorm, _down_proj, _frozen_plain, _lin,
-                             decode_fp4_copies, decode_fp8_copies, decode_layer_fused, decode_linear_weights, decode_multi_fused_or_none,
-                             decode_wide_rows, lookup_mask, use_decode_kernel)
+from .cambrian_llama import (CambrianLlamaForCausalLM, CambrianLlamaModel, HipRMSNorm, LlamaDecoderLayer, _down_proj,
+                             _frozen_plain, _lin, lookup_mask, use_decode_kernel)
 
 
 class CambrianConfig(Phi3Config):
@@ -140,60 +139,19 @@ class Phi3DecoderLayer(nn.Module):
         x, h = ops.add_rmsnorm(x, a, n2.weight, n2.variance_epsilon)              # :903-911 residual + norm, one pass
         return self.mlp(h, residual=x)
 
-    def decode(self, x, cos, sin, kcache, vcache, t, key_mask, fp8=False, fp4=False):
+    def decode_entries(self, fmt=None):
+        """See LlamaDecoderLayer.decode_entries: qkv_proj / gate_up_proj are packed as the kernel wants them, so the weights
+        are the modules' own and a quantised copy is cached on the Linear that owns the weight."""
         a, mlp = self.self_attn, self.mlp
-        wide = decode_wide_rows(self, x.shape[0])           # 17-64 rows behind the wide switch: ops.decode_linear_wide
-        if x.dtype == torch.bfloat16 and (wide or (x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS
-                                                   and ops.decode_linear_enabled(x.shape[0]))) \
-                and use_decode_kernel(x, a.nh, a.nkv, a.hd):
-            # qkv_proj / gate_up_proj are packed as the kernel wants them: no copies
-            mods = (a.qkv_proj, a.o_proj, mlp.gate_up_proj, mlp.down_proj)
-            w = tuple(m.weight if _frozen_plain(m) else None for m in mods)
-            if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm), wide):
-                if wide:     # bf16 weights whatever fp8 / fp4 say: no quantised copies are made for more than 16 rows
-                    return decode_layer_fused(self, x, cos, sin, kcache, vcache, t, key_mask, *w, linear=ops.decode_linear_wide)
-                if fp4:      # MXFP4 copies, cached on the Linear that owns the weight under a key of their own
-                    q4 = decode_fp4_copies(self, x.shape[0], tuple(
-                        (m, "_w_fp4", wi, "swiglu" if m is mlp.gate_up_proj else None) for m, wi in zip(mods, w)))
-                    return decode_layer_fused(self, x, cos, sin, kcache, vcache, t, key_mask, *w, fp4=q4)
-                q8 = None
-                if fp8:      # e4m3 copies, cached on the Linear that owns the weight
-                    q8 = decode_fp8_copies(self, x.shape[0], tuple(
-                        (m, "_w_fp8", wi, "swiglu" if m is mlp.gate_up_proj else None) for m, wi in zip(mods, w)))
-                return decode_layer_fused(self, x, cos, sin, kcache, vcache, t, key_mask, *w, fp8=q8)
-        x = x + self.self_attn.decode(self.input_layernorm(x), cos, sin, kcache, vcache, t, key_mask)
-        return x + self.mlp(self.post_attention_layernorm(x))
+        mods = (a.qkv_proj, a.o_proj, mlp.gate_up_proj, mlp.down_proj)
+        w = tuple(m.weight if _frozen_plain(m) else None for m in mods)
+        if fmt is None:
+            return w, None
+        return w, tuple((m, "_w_" + fmt, wi, "swiglu" if m is mlp.gate_up_proj else None) for m, wi in zip(mods, w))
 
-    def decode_multi(self, x, cos, sin, kcache, vcache, t0, key_mask, fp8=False, fp4=False):
-        """``decode`` for Q consecutive tokens of ONE sequence (see LlamaDecoderLayer.decode_multi)."""
-        out = decode_multi_fused_or_none(self, x, cos, sin, kcache, vcache, t0, key_mask, fp8, fp4)
-        if out is not None:
-            return out
-        x = x + self.self_attn.decode_multi(self.input_layernorm(x), cos, sin, kcache, vcache, t0, key_mask)
-        return x + self.mlp(self.post_attention_layernorm(x))
-
-    def decode_operands(self, x, fp8=False, fp4=False):
-        """(the four weights, their e4m3 copies or None) when ``decode`` runs a step of x as five launches, else None:
-        ``decode``'s conditions restated for ``DecodeStepPlan`` (see LlamaDecoderLayer.decode_operands)."""
-        a, mlp = self.self_attn, self.mlp
-        wide = decode_wide_rows(self, x.shape[0])           # 17-64 rows behind the wide switch: ops.decode_linear_wide
-        if x.dtype == torch.bfloat16 and (wide or (x.shape[0] <= ops.DECODE_LINEAR_MAX_ROWS
-                                                   and ops.decode_linear_enabled(x.shape[0]))) \
-                and use_decode_kernel(x, a.nh, a.nkv, a.hd):
-            mods = (a.qkv_proj, a.o_proj, mlp.gate_up_proj, mlp.down_proj)
-            w = tuple(m.weight if _frozen_plain(m) else None for m in mods)
-            if decode_linear_weights(x, *w, (self.input_layernorm, self.post_attention_layernorm), wide):
-                if wide:
-                    return w, None
-                if fp4:
-                    return w, decode_fp4_copies(self, x.shape[0], tuple(
-                        (m, "_w_fp4", wi, "swiglu" if m is mlp.gate_up_proj else None) for m, wi in zip(mods, w)))
-                q8 = None
-                if fp8:
-                    q8 = decode_fp8_copies(self, x.shape[0], tuple(
-                        (m, "_w_fp8", wi, "swiglu" if m is mlp.gate_up_proj else None) for m, wi in zip(mods, w)))
-                return w, q8
-        return None
+    # the step itself is the Llama layer's: one condition (decode_step_operands), one body
+    decode, decode_multi, decode_operands = (LlamaDecoderLayer.decode, LlamaDecoderLayer.decode_multi,
+                                             LlamaDecoderLayer.decode_operands)
 
 
 class CambrianPhi3Model(CambrianLlamaModel):

@@ -2274,13 +2274,21 @@ def decode_attention_multi(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, co
 # half the cache's memory and stream.  Opt-in (``config.decode_kv_fp8`` / CAMBRIAN_AMD_DECODE_KV_FP8): it changes numerics
 # (profiles/decode_kv8.md has what was measured).
 # ------------------------------------------------------------------------------------------------
+def _config_switch(env_name: str, config_flag: bool, strict: bool = False) -> bool:
+    """The opt-in ``decode_*_enabled(config_flag)`` switches: ``env_name`` in the environment overrides, unset (or empty) it
+    is ``config_flag``.  ``strict``: only ``1`` / ``0`` are taken and anything else raises; else everything but ``0`` is on."""
+    v = os.environ.get(env_name)
+    if v is None or v == "":
+        return bool(config_flag)
+    if strict and v not in ("0", "1"):
+        raise ValueError(f"{env_name}={v!r}: the switch takes 1 or 0")
+    return v != "0"
+
+
 def decode_kv_fp8_enabled(config_flag: bool = False) -> bool:
     """Whether ``generate()`` keeps its K / V cache in e4m3: ``CAMBRIAN_AMD_DECODE_KV_FP8`` = ``1`` / ``0`` in the environment
     overrides, unset (or empty) it is ``config_flag`` (the model's ``config.decode_kv_fp8``, absent = off)."""
-    v = os.environ.get("CAMBRIAN_AMD_DECODE_KV_FP8")
-    if v is None or v == "":
-        return bool(config_flag)
-    return v != "0"
+    return _config_switch("CAMBRIAN_AMD_DECODE_KV_FP8", config_flag)
 
 
 class KvCacheE4M3:
@@ -2409,9 +2417,12 @@ def decode_linear_enabled(rows: int = 1) -> bool:
 def decode_linear_plan(M: int, N: int, K: int, act: Optional[str] = None, cus: int = 0) -> Tuple[int, int]:
     """(weight rows per workgroup, workgroups) of a ``decode_linear`` call: a pure function of (M, N, K, act, CU count);
     ``cus`` = 0 takes the current device's count."""
+    return _decode_plan("cmb_decode_linear_plan", M, N, K, act, cus)
+
+
+def _decode_plan(symbol: str, M: int, N: int, K: int, act, cus: int) -> Tuple[int, int]:
     rows, wgs = C.c_int32(0), C.c_int64(0)
-    L.check(L.load().cmb_decode_linear_plan(M, N, K, _decode_linear_act(act), cus, C.byref(rows), C.byref(wgs)),
-            "cmb_decode_linear_plan")
+    L.check(getattr(L.load(), symbol)(M, N, K, _decode_linear_act(act), cus, C.byref(rows), C.byref(wgs)), symbol)
     return rows.value, wgs.value
 
 
@@ -2441,6 +2452,42 @@ def decode_linear_supported(x: torch.Tensor, w: torch.Tensor, act: Optional[str]
             and decode_linear_weight_supported(x.shape[0], w, act))
 
 
+def _decode_linear_launch(name: str, supported, x: torch.Tensor, weights: tuple, grad_weights: tuple, describe, norm_weight,
+                          eps, act, residual, out_dtype, out) -> torch.Tensor:
+    """The one body of the four decode linears.  ``supported``: the caller's own ``*_supported`` test, put to (x, *weights,
+    act); ``describe()``: the weights' part of its message; ``grad_weights``: the weights a backward would flow to.  The
+    arguments of ``cmb_<name>`` differ in the weights alone: per tensor its pointer and, for a matrix, its row stride."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, *grad_weights, norm_weight, residual)):
+        raise L.CambrianAmdError(f"{name} has no backward: call it under torch.no_grad()")
+    L.require_gpu(x, *weights, norm_weight, residual, out)
+    code = _decode_linear_act(act)
+    if not supported(x, *weights, act):
+        raise L.CambrianAmdError(f"{name}: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, "
+                                 f"{describe()}, act {act!r}")
+    (M, K), N = x.shape, weights[0].shape[0]
+    cols = N // 2 if code else N
+    if norm_weight is not None and (norm_weight.dtype != torch.bfloat16 or norm_weight.shape != (K,)
+                                    or not norm_weight.is_contiguous()):
+        raise L.CambrianAmdError(f"{name}: norm_weight is a contiguous bf16 [K] vector")
+    if residual is not None and (code or residual.dtype != torch.bfloat16 or residual.shape != (M, cols)
+                                 or residual.stride(1) != 1):
+        raise L.CambrianAmdError(f"{name}: residual is bf16 [M, N] with contiguous rows, and not combined with act")
+    out_dtype = out_dtype or (torch.bfloat16 if out is None else out.dtype)
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise L.CambrianAmdError(f"{name}: out_dtype {out_dtype} (bf16 or fp32)")
+    if out is None:
+        out = torch.empty((M, (cols + 7) // 8 * 8), dtype=out_dtype, device=x.device)[:, :cols]
+    elif not out.is_cuda or out.dtype != out_dtype or out.shape != (M, cols) or out.stride(1) != 1:
+        raise L.CambrianAmdError(f"{name}: out must be a {out_dtype} GPU tensor [{M}, {cols}] with contiguous rows")
+    w_args = []
+    for t in weights:
+        w_args += (t.data_ptr(), t.stride(0)) if t.dim() == 2 else (t.data_ptr(),)
+    L.call("cmb_" + name, x.data_ptr(), x.stride(0), M, L.ptr(norm_weight), float(eps), *w_args, N, K, code,
+           L.ptr(residual), 0 if residual is None else residual.stride(0), out.data_ptr(), out.stride(0),
+           int(out_dtype == torch.float32), device=x.device)
+    return out
+
+
 def decode_linear(x: torch.Tensor, w: torch.Tensor, *, norm_weight: Optional[torch.Tensor] = None, eps: float = 0.0,
                   act: Optional[str] = None, residual: Optional[torch.Tensor] = None,
                   out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -2450,34 +2497,9 @@ def decode_linear(x: torch.Tensor, w: torch.Tensor, *, norm_weight: Optional[tor
     [gate; up] and the result is ``silu(gate) * up`` [M, N / 2] (``swiglu_packed``'s convention); ``residual`` [M, N]: added
     in fp32 before the rounding; ``out_dtype``: bf16 (default) or fp32; ``out``: write into this [M, N'] tensor or row view
     (16-byte aligned, row stride a multiple of 8) instead of a new one.  Inference only: there is no backward."""
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w, norm_weight, residual)):
-        raise L.CambrianAmdError("decode_linear has no backward: call it under torch.no_grad()")
-    L.require_gpu(x, w, norm_weight, residual, out)
-    code = _decode_linear_act(act)
-    if not decode_linear_supported(x, w, act):
-        raise L.CambrianAmdError(f"decode_linear: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, "
-                                 f"w {tuple(w.shape)} {w.dtype} strides {w.stride()}, act {act!r}")
-    (M, K), N = x.shape, w.shape[0]
-    cols = N // 2 if code else N
-    if norm_weight is not None and (norm_weight.dtype != torch.bfloat16 or norm_weight.shape != (K,)
-                                    or not norm_weight.is_contiguous()):
-        raise L.CambrianAmdError("decode_linear: norm_weight is a contiguous bf16 [K] vector")
-    if residual is not None and (code or residual.dtype != torch.bfloat16 or residual.shape != (M, cols)
-                                 or residual.stride(1) != 1):
-        raise L.CambrianAmdError("decode_linear: residual is bf16 [M, N] with contiguous rows, and not combined with act")
-    out_dtype = out_dtype or (torch.bfloat16 if out is None else out.dtype)
-    if out_dtype not in (torch.bfloat16, torch.float32):
-        raise L.CambrianAmdError(f"decode_linear: out_dtype {out_dtype} (bf16 or fp32)")
-    if out is None:
-        ld = (cols + 7) // 8 * 8
-        out = torch.empty((M, ld), dtype=out_dtype, device=x.device)[:, :cols]
-    elif not out.is_cuda or out.dtype != out_dtype or out.shape != (M, cols) or out.stride(1) != 1:
-        raise L.CambrianAmdError(f"decode_linear: out must be a {out_dtype} GPU tensor [{M}, {cols}] with contiguous rows")
-    ld = out.stride(0)
-    L.call("cmb_decode_linear", x.data_ptr(), x.stride(0), M, L.ptr(norm_weight), float(eps), w.data_ptr(), w.stride(0), N, K,
-           code, L.ptr(residual), 0 if residual is None else residual.stride(0), out.data_ptr(), ld,
-           int(out_dtype == torch.float32), device=x.device)
-    return out
+    return _decode_linear_launch("decode_linear", decode_linear_supported, x, (w,), (w,),
+                                 lambda: f"w {tuple(w.shape)} {w.dtype} strides {w.stride()}",
+                                 norm_weight, eps, act, residual, out_dtype, out)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2493,12 +2515,7 @@ def decode_linear_wide_enabled(config_flag: bool = False) -> bool:
     ``config_flag`` (the model's ``config.decode_linear_wide``, absent = off).  Any other value raises: a typo must not
     silently pick a side.  ``CAMBRIAN_AMD_DECODE_LINEAR=0`` (the stock sequence everywhere) wins over this switch at the
     dispatch sites."""
-    v = os.environ.get("CAMBRIAN_AMD_DECODE_LINEAR_WIDE")
-    if v is None or v == "":
-        return bool(config_flag)
-    if v not in ("0", "1"):
-        raise ValueError(f"CAMBRIAN_AMD_DECODE_LINEAR_WIDE={v!r}: the switch takes 1 or 0")
-    return v == "1"
+    return _config_switch("CAMBRIAN_AMD_DECODE_LINEAR_WIDE", config_flag, strict=True)
 
 
 def decode_linear_wide_rows(rows: int, config_flag: bool = False) -> bool:
@@ -2511,10 +2528,7 @@ def decode_linear_wide_rows(rows: int, config_flag: bool = False) -> bool:
 def decode_linear_wide_plan(M: int, N: int, K: int, act: Optional[str] = None, cus: int = 0) -> Tuple[int, int]:
     """(weight rows per workgroup, workgroups) of a ``decode_linear_wide`` call: a pure function of (N, act, CU count);
     ``cus`` = 0 takes the current device's count."""
-    rows, wgs = C.c_int32(0), C.c_int64(0)
-    L.check(L.load().cmb_decode_linear_wide_plan(M, N, K, _decode_linear_act(act), cus, C.byref(rows), C.byref(wgs)),
-            "cmb_decode_linear_wide_plan")
-    return rows.value, wgs.value
+    return _decode_plan("cmb_decode_linear_wide_plan", M, N, K, act, cus)
 
 
 def decode_linear_wide_weight_supported(M: int, w: torch.Tensor, act: Optional[str] = None) -> bool:
@@ -2536,34 +2550,9 @@ def decode_linear_wide(x: torch.Tensor, w: torch.Tensor, *, norm_weight: Optiona
     """``decode_linear`` for bf16 x [M <= 64, K]: the same function, arguments and checks, one launch that reads the weights
     once.  The same inputs give the same bits, and a row's bits depend neither on M nor on the other rows; they are not
     ``decode_linear``'s bits (another order of the same fp32 sum).  Inference only: there is no backward."""
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w, norm_weight, residual)):
-        raise L.CambrianAmdError("decode_linear_wide has no backward: call it under torch.no_grad()")
-    L.require_gpu(x, w, norm_weight, residual, out)
-    code = _decode_linear_act(act)
-    if not decode_linear_wide_supported(x, w, act):
-        raise L.CambrianAmdError(f"decode_linear_wide: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, "
-                                 f"w {tuple(w.shape)} {w.dtype} strides {w.stride()}, act {act!r}")
-    (M, K), N = x.shape, w.shape[0]
-    cols = N // 2 if code else N
-    if norm_weight is not None and (norm_weight.dtype != torch.bfloat16 or norm_weight.shape != (K,)
-                                    or not norm_weight.is_contiguous()):
-        raise L.CambrianAmdError("decode_linear_wide: norm_weight is a contiguous bf16 [K] vector")
-    if residual is not None and (code or residual.dtype != torch.bfloat16 or residual.shape != (M, cols)
-                                 or residual.stride(1) != 1):
-        raise L.CambrianAmdError("decode_linear_wide: residual is bf16 [M, N] with contiguous rows, and not combined with act")
-    out_dtype = out_dtype or (torch.bfloat16 if out is None else out.dtype)
-    if out_dtype not in (torch.bfloat16, torch.float32):
-        raise L.CambrianAmdError(f"decode_linear_wide: out_dtype {out_dtype} (bf16 or fp32)")
-    if out is None:
-        ld = (cols + 7) // 8 * 8
-        out = torch.empty((M, ld), dtype=out_dtype, device=x.device)[:, :cols]
-    elif not out.is_cuda or out.dtype != out_dtype or out.shape != (M, cols) or out.stride(1) != 1:
-        raise L.CambrianAmdError(f"decode_linear_wide: out must be a {out_dtype} GPU tensor [{M}, {cols}] with contiguous rows")
-    ld = out.stride(0)
-    L.call("cmb_decode_linear_wide", x.data_ptr(), x.stride(0), M, L.ptr(norm_weight), float(eps), w.data_ptr(), w.stride(0), N,
-           K, code, L.ptr(residual), 0 if residual is None else residual.stride(0), out.data_ptr(), ld,
-           int(out_dtype == torch.float32), device=x.device)
-    return out
+    return _decode_linear_launch("decode_linear_wide", decode_linear_wide_supported, x, (w,), (w,),
+                                 lambda: f"w {tuple(w.shape)} {w.dtype} strides {w.stride()}",
+                                 norm_weight, eps, act, residual, out_dtype, out)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2577,19 +2566,13 @@ DECODE_FP8_MAX_K = 16384       # cmb_quantize_fp8_rows holds a row in registers:
 def decode_fp8_enabled(config_flag: bool = False) -> bool:
     """Whether decode steps stream e4m3 weights: ``CAMBRIAN_AMD_DECODE_FP8`` = ``1`` / ``0`` in the environment overrides,
     unset it is ``config_flag`` (the model's ``config.decode_fp8_weights``, absent = off)."""
-    v = os.environ.get("CAMBRIAN_AMD_DECODE_FP8")
-    if v is None or v == "":
-        return bool(config_flag)
-    return v != "0"
+    return _config_switch("CAMBRIAN_AMD_DECODE_FP8", config_flag)
 
 
 def decode_linear_fp8_plan(M: int, N: int, K: int, act: Optional[str] = None, cus: int = 0) -> Tuple[int, int]:
     """(weight rows per workgroup, workgroups) of a ``decode_linear_fp8`` call: a pure function of (M, N, K, act, CU
     count); ``cus`` = 0 takes the current device's count."""
-    rows, wgs = C.c_int32(0), C.c_int64(0)
-    L.check(L.load().cmb_decode_linear_fp8_plan(M, N, K, _decode_linear_act(act), cus, C.byref(rows), C.byref(wgs)),
-            "cmb_decode_linear_fp8_plan")
-    return rows.value, wgs.value
+    return _decode_plan("cmb_decode_linear_fp8_plan", M, N, K, act, cus)
 
 
 def decode_linear_fp8_weight_supported(M: int, w: torch.Tensor, act: Optional[str] = None) -> bool:
@@ -2638,34 +2621,10 @@ def decode_linear_fp8(x: torch.Tensor, q: torch.Tensor, inv_scale: torch.Tensor,
     ``decode_fp8_weight``; one
     launch that reads one byte per weight.  ``norm_weight`` / ``eps`` / ``act`` / ``residual`` / ``out_dtype`` / ``out``
     mean what they mean in ``decode_linear``.  Inference only: there is no backward and no CPU path."""
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, inv_scale, norm_weight, residual)):
-        raise L.CambrianAmdError("decode_linear_fp8 has no backward: call it under torch.no_grad()")
-    L.require_gpu(x, q, inv_scale, norm_weight, residual, out)
-    code = _decode_linear_act(act)
-    if not decode_linear_fp8_supported(x, q, inv_scale, act):
-        raise L.CambrianAmdError(f"decode_linear_fp8: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, "
-                                 f"q {tuple(q.shape)} {q.dtype} strides {q.stride()}, inv_scale {tuple(inv_scale.shape)} "
-                                 f"{inv_scale.dtype}, act {act!r}")
-    (M, K), N = x.shape, q.shape[0]
-    cols = N // 2 if code else N
-    if norm_weight is not None and (norm_weight.dtype != torch.bfloat16 or norm_weight.shape != (K,)
-                                    or not norm_weight.is_contiguous()):
-        raise L.CambrianAmdError("decode_linear_fp8: norm_weight is a contiguous bf16 [K] vector")
-    if residual is not None and (code or residual.dtype != torch.bfloat16 or residual.shape != (M, cols)
-                                 or residual.stride(1) != 1):
-        raise L.CambrianAmdError("decode_linear_fp8: residual is bf16 [M, N] with contiguous rows, and not combined with act")
-    out_dtype = out_dtype or (torch.bfloat16 if out is None else out.dtype)
-    if out_dtype not in (torch.bfloat16, torch.float32):
-        raise L.CambrianAmdError(f"decode_linear_fp8: out_dtype {out_dtype} (bf16 or fp32)")
-    if out is None:
-        ld = (cols + 7) // 8 * 8
-        out = torch.empty((M, ld), dtype=out_dtype, device=x.device)[:, :cols]
-    elif not out.is_cuda or out.dtype != out_dtype or out.shape != (M, cols) or out.stride(1) != 1:
-        raise L.CambrianAmdError(f"decode_linear_fp8: out must be a {out_dtype} GPU tensor [{M}, {cols}] with contiguous rows")
-    L.call("cmb_decode_linear_fp8", x.data_ptr(), x.stride(0), M, L.ptr(norm_weight), float(eps), q.data_ptr(), q.stride(0),
-           inv_scale.data_ptr(), N, K, code, L.ptr(residual), 0 if residual is None else residual.stride(0), out.data_ptr(),
-           out.stride(0), int(out_dtype == torch.float32), device=x.device)
-    return out
+    return _decode_linear_launch("decode_linear_fp8", decode_linear_fp8_supported, x, (q, inv_scale), (inv_scale,),
+                                 lambda: f"q {tuple(q.shape)} {q.dtype} strides {q.stride()}, inv_scale "
+                                         f"{tuple(inv_scale.shape)} {inv_scale.dtype}",
+                                 norm_weight, eps, act, residual, out_dtype, out)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2682,10 +2641,7 @@ DECODE_FP4_BLOCK = 32
 def decode_fp4_enabled(config_flag: bool = False) -> bool:
     """Whether decode steps stream MXFP4 weights: ``CAMBRIAN_AMD_DECODE_FP4`` = ``1`` / ``0`` in the environment overrides,
     unset it is ``config_flag`` (the model's ``config.decode_fp4_weights``, absent = off)."""
-    v = os.environ.get("CAMBRIAN_AMD_DECODE_FP4")
-    if v is None or v == "":
-        return bool(config_flag)
-    return v != "0"
+    return _config_switch("CAMBRIAN_AMD_DECODE_FP4", config_flag)
 
 
 def decode_weight_format(config) -> Optional[str]:
@@ -2704,10 +2660,7 @@ def decode_weight_format(config) -> Optional[str]:
 def decode_linear_fp4_plan(M: int, N: int, K: int, act: Optional[str] = None, cus: int = 0) -> Tuple[int, int]:
     """(weight rows per workgroup, workgroups) of a ``decode_linear_fp4`` call: a pure function of (M, N, K, act, CU
     count); ``cus`` = 0 takes the current device's count."""
-    rows, wgs = C.c_int32(0), C.c_int64(0)
-    L.check(L.load().cmb_decode_linear_fp4_plan(M, N, K, _decode_linear_act(act), cus, C.byref(rows), C.byref(wgs)),
-            "cmb_decode_linear_fp4_plan")
-    return rows.value, wgs.value
+    return _decode_plan("cmb_decode_linear_fp4_plan", M, N, K, act, cus)
 
 
 def decode_linear_fp4_weight_supported(M: int, w: torch.Tensor, act: Optional[str] = None) -> bool:
@@ -2768,34 +2721,10 @@ def decode_linear_fp4(x: torch.Tensor, q: torch.Tensor, scales: torch.Tensor, *,
     q the packed nibbles [N, K / 2] and scales the e8m0 bytes [N, K / 32] of ``decode_fp4_weight`` (codes 1 .. 254, never 0 or
     255); one launch that reads 4.25 bits per weight.  ``norm_weight`` / ``eps`` / ``act`` / ``residual`` / ``out_dtype`` /
     ``out`` mean what they mean in ``decode_linear``.  Inference only: there is no backward and no CPU path."""
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, norm_weight, residual)):
-        raise L.CambrianAmdError("decode_linear_fp4 has no backward: call it under torch.no_grad()")
-    L.require_gpu(x, q, scales, norm_weight, residual, out)
-    code = _decode_linear_act(act)
-    if not decode_linear_fp4_supported(x, q, scales, act):
-        raise L.CambrianAmdError(f"decode_linear_fp4: unsupported operands x {tuple(x.shape)} {x.dtype} strides {x.stride()}, "
-                                 f"q {tuple(q.shape)} {q.dtype} strides {q.stride()}, scales {tuple(scales.shape)} "
-                                 f"{scales.dtype} strides {scales.stride()}, act {act!r}")
-    (M, K), N = x.shape, q.shape[0]
-    cols = N // 2 if code else N
-    if norm_weight is not None and (norm_weight.dtype != torch.bfloat16 or norm_weight.shape != (K,)
-                                    or not norm_weight.is_contiguous()):
-        raise L.CambrianAmdError("decode_linear_fp4: norm_weight is a contiguous bf16 [K] vector")
-    if residual is not None and (code or residual.dtype != torch.bfloat16 or residual.shape != (M, cols)
-                                 or residual.stride(1) != 1):
-        raise L.CambrianAmdError("decode_linear_fp4: residual is bf16 [M, N] with contiguous rows, and not combined with act")
-    out_dtype = out_dtype or (torch.bfloat16 if out is None else out.dtype)
-    if out_dtype not in (torch.bfloat16, torch.float32):
-        raise L.CambrianAmdError(f"decode_linear_fp4: out_dtype {out_dtype} (bf16 or fp32)")
-    if out is None:
-        ld = (cols + 7) // 8 * 8
-        out = torch.empty((M, ld), dtype=out_dtype, device=x.device)[:, :cols]
-    elif not out.is_cuda or out.dtype != out_dtype or out.shape != (M, cols) or out.stride(1) != 1:
-        raise L.CambrianAmdError(f"decode_linear_fp4: out must be a {out_dtype} GPU tensor [{M}, {cols}] with contiguous rows")
-    L.call("cmb_decode_linear_fp4", x.data_ptr(), x.stride(0), M, L.ptr(norm_weight), float(eps), q.data_ptr(), q.stride(0),
-           scales.data_ptr(), scales.stride(0), N, K, code, L.ptr(residual), 0 if residual is None else residual.stride(0),
-           out.data_ptr(), out.stride(0), int(out_dtype == torch.float32), device=x.device)
-    return out
+    return _decode_linear_launch("decode_linear_fp4", decode_linear_fp4_supported, x, (q, scales), (),
+                                 lambda: f"q {tuple(q.shape)} {q.dtype} strides {q.stride()}, scales {tuple(scales.shape)} "
+                                         f"{scales.dtype} strides {scales.stride()}",
+                                 norm_weight, eps, act, residual, out_dtype, out)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2814,10 +2743,7 @@ def decode_step_enabled(config_flag: bool = False) -> bool:
     """Whether decode steps of ``generate()`` are issued as one library call per token: ``CAMBRIAN_AMD_DECODE_STEP`` =
     ``1`` / ``0`` in the environment overrides, unset it is ``config_flag`` (the model's ``config.decode_step_fused``,
     absent = off)."""
-    v = os.environ.get("CAMBRIAN_AMD_DECODE_STEP")
-    if v is None or v == "":
-        return bool(config_flag)
-    return v != "0"
+    return _config_switch("CAMBRIAN_AMD_DECODE_STEP", config_flag)
 
 
 def decode_step_ws_floats(B: int, H: int, I: int, nh: int, nkv: int, hd: int, t_max: int) -> int:
@@ -2873,10 +2799,7 @@ def decode_sample_enabled(config_flag: bool = False) -> bool:
     """Whether sampled decoding of ``generate()`` selects its tokens on the device (``decode_sample``) where the one-call decode
     step runs: ``CAMBRIAN_AMD_DECODE_SAMPLE`` = ``1`` / ``0`` in the environment overrides, unset it is ``config_flag`` (the
     model's ``config.decode_sample_device``, absent = off)."""
-    v = os.environ.get("CAMBRIAN_AMD_DECODE_SAMPLE")
-    if v is None or v == "":
-        return bool(config_flag)
-    return v != "0"
+    return _config_switch("CAMBRIAN_AMD_DECODE_SAMPLE", config_flag)
 
 
 def decode_sample(logits: torch.Tensor, inv_temperature: float, top_k: int, top_p: float, seed: torch.Tensor, eos: int,
@@ -2902,12 +2825,7 @@ def decode_process_enabled(config_flag: bool = False) -> bool:
     ``no_repeat_ngram_size``, ``min_new_tokens``, ``bad_words_ids``, ``suppress_tokens``) and a list ``eos_token_id``, and runs
     them on the device (``decode_process``): ``CAMBRIAN_AMD_DECODE_PROCESS`` = ``1`` / ``0`` in the environment overrides, unset
     it is ``config_flag`` (the model's ``config.decode_logits_processors``, absent = off).  Any other value raises."""
-    v = os.environ.get("CAMBRIAN_AMD_DECODE_PROCESS")
-    if v is None or v == "":
-        return bool(config_flag)
-    if v not in ("0", "1"):
-        raise ValueError(f"CAMBRIAN_AMD_DECODE_PROCESS={v!r}: the switch takes 1 or 0")
-    return v == "1"
+    return _config_switch("CAMBRIAN_AMD_DECODE_PROCESS", config_flag, strict=True)
 
 
 class DecodeProcess:
@@ -2958,12 +2876,7 @@ def decode_beam_enabled(config_flag: bool = False) -> bool:
     runs; else on the per-launch loop around model/language_model/beam.py) instead of raising: ``CAMBRIAN_AMD_DECODE_BEAM`` =
     ``1`` / ``0`` in the environment overrides, unset it is ``config_flag`` (the model's ``config.decode_beam_search``, absent =
     off).  Any other value raises: a typo must not silently pick a side."""
-    v = os.environ.get("CAMBRIAN_AMD_DECODE_BEAM")
-    if v is None or v == "":
-        return bool(config_flag)
-    if v not in ("0", "1"):
-        raise ValueError(f"CAMBRIAN_AMD_DECODE_BEAM={v!r}: the switch takes 1 or 0")
-    return v == "1"
+    return _config_switch("CAMBRIAN_AMD_DECODE_BEAM", config_flag, strict=True)
 
 
 DECODE_BEAM_MAX = 16           # CMB_BEAM_MAX of csrc/decode_beam_core.h: beams of one prompt, and rows of a fused decode step

@@ -230,7 +230,6 @@ def _per_token_logits(model, ids, caches, t0, p0, mask, fp8, fp4):
     ops = _ops()
     cfg = model.config
     hd = model.model.layers[0].self_attn.hd
-    low = {"fp4": True} if fp4 else {}
     rows = []
     mask = mask.clone()
     for j in range(ids.shape[0]):
@@ -239,8 +238,8 @@ def _per_token_logits(model, ids, caches, t0, p0, mask, fp8, fp4):
         cos, sin = ops.rope_table(torch.tensor([[p0 + j]], device=ids.device), hd, float(cfg.rope_theta))
         h = model.model.embed_tokens(ids[j:j + 1])[:, None, :].to(model.model.llm_dtype)
         for layer, (kc, vc) in zip(model.model.layers, caches):
-            h = layer.decode(h, cos, sin, kc, vc, t, mask, fp8=fp8, **low)
-        rows.append(CL._decode_logits(model, h, fp8, **low))
+            h = layer.decode(h, cos, sin, kc, vc, t, mask, fp8=fp8, fp4=fp4)
+        rows.append(CL._decode_logits(model, h, fp8, fp4))
     return torch.cat(rows, 0)
 
 
