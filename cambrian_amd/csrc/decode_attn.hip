@@ -19,6 +19,7 @@
 // the arguments (k roped in registers, rounded to the cache dtype as later steps will read it) and is the only one that
 // stores them.
 #include "decode_attn_common.h"
+#include "decode_attn_host.h"
 
 namespace {
 
@@ -280,6 +281,9 @@ bool dec_plan(int64_t B, int32_t nkv, int64_t t, int32_t forced, int32_t* splits
   return true;
 }
 
+}  // namespace
+
+// dec_geometry_ok and the plan query, declared in decode_attn_host.h for the other two files
 bool dec_geometry_ok(int dtype, int32_t nh, int32_t nkv, int32_t hd) {
   if (dtype != CMB_BF16 && dtype != CMB_F32) return false;
   if (hd != 64 && hd != 96 && hd != 128) return false;
@@ -287,24 +291,27 @@ bool dec_geometry_ok(int dtype, int32_t nh, int32_t nkv, int32_t hd) {
   return true;
 }
 
-}  // namespace
-
-extern "C" int cmb_decode_attn_plan(int64_t B, int32_t nkv, int64_t t, int32_t splits, int32_t* splits_out,
-                                    int64_t* chunk_out, int32_t* max_splits_out) {
+int dec_plan_slots(int64_t B, int32_t nkv, int64_t t0, int64_t n, int32_t forced, int32_t* splits_out, int64_t* chunk_out,
+                   int32_t* max_splits_out) {
   if (max_splits_out) *max_splits_out = DEC_MAX_SPLITS;
   int32_t s = 0;
   int64_t ch = 0;
-  if (!dec_plan(B, nkv, t, splits, &s, &ch)) return CMB_ERR_BAD_ARG;
+  if (t0 < 0 || n < 1 || !dec_plan(B, nkv, t0 + n - 1, forced, &s, &ch)) return CMB_ERR_BAD_ARG;
   if (splits_out) *splits_out = s;
   if (chunk_out) *chunk_out = ch;
   return CMB_OK;
+}
+
+extern "C" int cmb_decode_attn_plan(int64_t B, int32_t nkv, int64_t t, int32_t splits, int32_t* splits_out,
+                                    int64_t* chunk_out, int32_t* max_splits_out) {
+  return dec_plan_slots(B, nkv, t, 1, splits, splits_out, chunk_out, max_splits_out);
 }
 
 extern "C" int64_t cmb_decode_attn_ws(int64_t B, int32_t nh, int32_t nkv, int32_t hd, int64_t t, int32_t splits) {
   int32_t s = 0;
   int64_t ch = 0;
   if (!dec_geometry_ok(CMB_F32, nh, nkv, hd) || !dec_plan(B, nkv, t, splits, &s, &ch)) return CMB_ERR_BAD_ARG;
-  return s == 1 ? 0 : B * nh * s * (int64_t)(hd + 2);
+  return dec_ws_need(B * nh, s, hd);
 }
 
 extern "C" int cmb_decode_attn(int dtype, const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v,
@@ -312,19 +319,15 @@ extern "C" int cmb_decode_attn(int dtype, const void* q, int64_t q_ld, const voi
                                int64_t c_sb, int64_t c_sh, int64_t c_st, int64_t B, int32_t nh, int32_t nkv, int32_t hd,
                                int64_t t, const uint8_t* key_valid, int64_t kv_ld, float scale, int32_t splits, float* ws,
                                int64_t ws_floats, void* out, void* stream) {
-  if (!q || !k || !v || !cos_t || !sin_t || !kcache || !vcache || !key_valid || !out) return CMB_ERR_BAD_ARG;
-  if (!dec_geometry_ok(dtype, nh, nkv, hd) || B < 0 || B > 65535 || nkv > 65535 || t < 0 || kv_ld < t + 1)
-    return CMB_ERR_BAD_ARG;
+  if (!dec_all_set({q, k, v, cos_t, sin_t, kcache, vcache, key_valid, out})) return CMB_ERR_BAD_ARG;
+  if (!dec_geometry_ok(dtype, nh, nkv, hd) || !dec_range_ok(B, nkv, t, 1, kv_ld)) return CMB_ERR_BAD_ARG;
   if (B == 0) return CMB_OK;
   int32_t s = 0;
   int64_t chunk = 0;
   if (!dec_plan(B, nkv, t, splits, &s, &chunk)) return CMB_ERR_BAD_ARG;
-  const int64_t need = s == 1 ? 0 : B * nh * s * (int64_t)(hd + 2);
+  const int64_t need = dec_ws_need(B * nh, s, hd);
   if (need > 0 && (!ws || ws_floats < need)) return CMB_ERR_BAD_ARG;
-  const int64_t es = dtype == CMB_BF16 ? 2 : 4;
-  if (!cmb_aligned16(q) || !cmb_aligned16(k) || !cmb_aligned16(v) || !cmb_aligned16(kcache) || !cmb_aligned16(vcache) ||
-      !cmb_aligned16(out) || (q_ld * es) % 16 || (k_ld * es) % 16 || (v_ld * es) % 16 || (c_sb * es) % 16 ||
-      (c_sh * es) % 16 || (c_st * es) % 16)
+  if (!dec_aligned16({q, k, v, kcache, vcache, out}, {q_ld, k_ld, v_ld, c_sb, c_sh, c_st}, dtype == CMB_BF16 ? 2 : 4))
     return CMB_ERR_ALIGNMENT;
 
   DecParams p;
@@ -336,7 +339,7 @@ extern "C" int cmb_decode_attn(int dtype, const void* q, int64_t q_ld, const voi
   p.G = nh / nkv; p.nkv = nkv;
   p.t = t;
   p.key_valid = key_valid; p.kv_ld = kv_ld;
-  p.scale_log2 = scale * 1.4426950408889634f;
+  p.scale_log2 = scale * DEC_LOG2E;
   p.splits = s; p.chunk = chunk;
   p.ws = s == 1 ? nullptr : ws;
   p.out = out;
@@ -364,12 +367,8 @@ extern "C" int cmb_decode_attn(int dtype, const void* q, int64_t q_ld, const voi
 #undef DEC_LAUNCH
   CMB_CHECK_LAUNCH();
   if (s > 1) {
-    if (dtype == CMB_BF16)
-      hipLaunchKernelGGL(decode_combine_kernel<bf16_t>, dim3((unsigned)(B * nh)), dim3(128), 0, st, (const float*)ws, G,
-                         (int)hd, (int)s, (bf16_t*)out);
-    else
-      hipLaunchKernelGGL(decode_combine_kernel<float>, dim3((unsigned)(B * nh)), dim3(128), 0, st, (const float*)ws, G,
-                         (int)hd, (int)s, (float*)out);
+    if (dtype == CMB_BF16) dec_launch_combine<bf16_t>(B * nh, ws, G, hd, s, out, st);
+    else dec_launch_combine<float>(B * nh, ws, G, hd, s, out, st);
     CMB_CHECK_LAUNCH();
   }
   return CMB_OK;

@@ -1,7 +1,8 @@
 // decode_attn_common.h — what the decode-attention kernels share (decode_attn.hip on bf16 / fp32 caches, decode_attn_kv8.hip on
-// e4m3 caches): the workgroup shape, the 16-byte row pieces, the DPP lane-group reductions, RoPE of a new-token slice, the
-// weight of a partial and the kernel that merges the chunks' partials.  Device code only; the plan and the geometry rule stay
-// in decode_attn.hip behind cmb_decode_attn_plan / cmb_decode_attn_ws.
+// e4m3 caches, decode_attn_multi.hip for Q tokens per step): the workgroup shape and the limits of the plan, the 16-byte row
+// pieces, the DPP lane-group reductions, RoPE of a new-token slice, the weight of a partial and the kernel that merges the
+// chunks' partials of the two single-token files.  Constants and device code; what the three launchers share on the host is in
+// decode_attn_host.h, and the plan and the geometry rule stay in decode_attn.hip (reached through that header).
 #pragma once
 #include "common.h"
 
@@ -34,20 +35,36 @@ template <> struct Row16<float> {
   static __device__ __forceinline__ raw from_f32(const float (&v)[4]) { return (raw){v[0], v[1], v[2], v[3]}; }
 };
 
-// v + (v of the lane the DPP control names); controls used: quad_perm [1,0,3,2] / [2,3,0,1], row_half_mirror, row_mirror
+// v + / max (v of the lane the DPP control names); controls used: quad_perm [1,0,3,2] / [2,3,0,1], row_half_mirror, row_mirror
 template <int CTRL>
 __device__ __forceinline__ float dpp_add(float v) {
   const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true);
   return v + __builtin_bit_cast(float, o);
 }
-// sum over an aligned group of LPK (8 / 16 / 32) lanes, result in every lane of the group; all 64 lanes must be active
+template <int CTRL>
+__device__ __forceinline__ float dpp_max(float v) {
+  const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true);
+  return fmaxf(v, __builtin_bit_cast(float, o));
+}
+// sum over an aligned group of LPK (4 / 8 / 16 / 32) lanes, result in every lane of the group; all 64 lanes must be active
 template <int LPK>
 __device__ __forceinline__ float group_sum(float v) {
+  static_assert(LPK == 4 || LPK == 8 || LPK == 16 || LPK == 32, "lane groups of 4, 8, 16 or 32");
   v = dpp_add<0xB1>(v);
   v = dpp_add<0x4E>(v);
-  v = dpp_add<0x141>(v);                      // quads hold equal sums: the mirrored lane is in the other quad
+  if (LPK >= 8) v = dpp_add<0x141>(v);        // quads hold equal sums: the mirrored lane is in the other quad
   if (LPK >= 16) v = dpp_add<0x140>(v);
   if (LPK >= 32) v += __shfl_xor(v, 16, 64);
+  return v;
+}
+// the maximum likewise, over 4 / 8 / 16 lanes
+template <int LPK>
+__device__ __forceinline__ float group_max(float v) {
+  static_assert(LPK == 4 || LPK == 8 || LPK == 16, "lane groups of 4, 8 or 16");
+  v = dpp_max<0xB1>(v);
+  v = dpp_max<0x4E>(v);
+  if (LPK >= 8) v = dpp_max<0x141>(v);
+  if (LPK >= 16) v = dpp_max<0x140>(v);
   return v;
 }
 

@@ -38,6 +38,7 @@
 // cmb_kv_quantize_e4m3: a streaming kernel, a row across a lane group of 8 (hd <= 64: 4) lanes of 16 elements each (two
 // 16-byte loads, one 16-byte store), 8 or 16 rows per wave, amax by shuffles inside the group.  No workspace, no atomics.
 #include "decode_attn_common.h"
+#include "decode_attn_host.h"
 
 namespace {
 
@@ -75,31 +76,6 @@ __device__ __forceinline__ typename Kv8Raw<E>::raw kv8_pack(const float (&v)[E],
   return r;
 }
 
-// max(v, v of the lane the DPP control names), and the maximum / the sum over an aligned group of 4 / 8 / 16 lanes in every
-// lane of it (group_sum's controls, with the 4-lane group it does not have; all 64 lanes must be active)
-template <int CTRL>
-__device__ __forceinline__ float dpp_max(float v) {
-  const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true);
-  return fmaxf(v, __builtin_bit_cast(float, o));
-}
-template <int LPK>
-__device__ __forceinline__ float group_max(float v) {
-  static_assert(LPK == 4 || LPK == 8 || LPK == 16, "lane groups of 4, 8 or 16");
-  v = dpp_max<0xB1>(v);
-  v = dpp_max<0x4E>(v);
-  if (LPK >= 8) v = dpp_max<0x141>(v);
-  if (LPK >= 16) v = dpp_max<0x140>(v);
-  return v;
-}
-template <int LPK>
-__device__ __forceinline__ float group_sum8(float v) {
-  static_assert(LPK == 4 || LPK == 8 || LPK == 16, "lane groups of 4, 8 or 16");
-  v = dpp_add<0xB1>(v);
-  v = dpp_add<0x4E>(v);
-  if (LPK >= 8) v = dpp_add<0x141>(v);       // quads hold equal sums: the mirrored lane is in the other quad
-  if (LPK >= 16) v = dpp_add<0x140>(v);
-  return v;
-}
 // new-token row `x`, bf16: E (8 or 16) roped elements at d0; a piece never straddles HD / 2 (HD / 2 is a multiple of 16)
 template <int HD, int E>
 __device__ __forceinline__ void rope_piece(const bf16_t* x, int d0, const float (&cs)[E], const float (&sn)[E], float (&o)[E]) {
@@ -268,7 +244,7 @@ __global__ void __launch_bounds__(DEC_THREADS) decode_attn_kv8_kernel(const Dec8
     f32x2_t d = {0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < EP; ++j) d = __builtin_elementwise_fma(qg[j], kf[j], d);
-    return group_sum8<LPK>(d[0] + d[1]);
+    return group_sum<LPK>(d[0] + d[1]);
   };
 
   // one online-softmax step over U scored rows: s[u][g] (-inf = not attendable; overwritten with the weights), rv[u] the
@@ -482,22 +458,20 @@ extern "C" int cmb_decode_attn_kv8(const void* q, int64_t q_ld, const void* k, i
                                    int64_t c_sh, int64_t c_st, float* k_inv, float* v_inv, int64_t i_sb, int64_t i_sh, int64_t B,
                                    int32_t nh, int32_t nkv, int32_t hd, int64_t t, const uint8_t* key_valid, int64_t kv_ld,
                                    float scale, int32_t splits, float* ws, int64_t ws_floats, void* out, void* stream) {
-  if (!q || !k || !v || !cos_t || !sin_t || !kcache || !vcache || !k_inv || !v_inv || !key_valid || !out)
-    return CMB_ERR_BAD_ARG;
-  if (B < 0 || B > 65535 || nkv > 65535 || t < 0 || kv_ld < t + 1) return CMB_ERR_BAD_ARG;
-  // the geometry rule (hd 64 / 96 / 128, nh % nkv == 0, at most 8 query heads per KV head), the plan and the workspace need are
-  // cmb_decode_attn's
+  if (!dec_all_set({q, k, v, cos_t, sin_t, kcache, vcache, k_inv, v_inv, key_valid, out})) return CMB_ERR_BAD_ARG;
+  if (!dec_range_ok(B, nkv, t, 1, kv_ld)) return CMB_ERR_BAD_ARG;
+  // the geometry rule, the plan and the workspace need are cmb_decode_attn's.  Unlike it, this entry point has always looked at
+  // `splits` and the cache strides before it returns from B == 0, so an empty batch is planned as a batch of one.
   int32_t s = 0;
   int64_t chunk = 0;
-  const int64_t Bq = B > 0 ? B : 1;
-  const int64_t need = cmb_decode_attn_ws(Bq, nh, nkv, hd, t, splits);
-  if (need < 0 || cmb_decode_attn_plan(Bq, nkv, t, splits, &s, &chunk, nullptr) != CMB_OK) return CMB_ERR_BAD_ARG;
+  if (!dec_geometry_ok(CMB_BF16, nh, nkv, hd) || dec_plan_slots(B > 0 ? B : 1, nkv, t, 1, splits, &s, &chunk, nullptr) != CMB_OK)
+    return CMB_ERR_BAD_ARG;
   if (c_sb < 0 || c_sh < 0 || c_st < hd || i_sb < 0 || i_sh < 0) return CMB_ERR_BAD_ARG;
   if (B == 0) return CMB_OK;
+  const int64_t need = dec_ws_need(B * nh, s, hd);
   if (need > 0 && (!ws || ws_floats < need)) return CMB_ERR_BAD_ARG;
-  if (!cmb_aligned16(q) || !cmb_aligned16(k) || !cmb_aligned16(v) || !cmb_aligned16(kcache) || !cmb_aligned16(vcache) ||
-      !cmb_aligned16(out) || !aligned4(k_inv) || !aligned4(v_inv) || (q_ld * 2) % 16 || (k_ld * 2) % 16 || (v_ld * 2) % 16 ||
-      c_sb % 16 || c_sh % 16 || c_st % 16)
+  if (!dec_aligned16({q, k, v, kcache, vcache, out}, {q_ld, k_ld, v_ld}, 2) || !dec_aligned16({}, {c_sb, c_sh, c_st}, 1) ||
+      !aligned4(k_inv) || !aligned4(v_inv))
     return CMB_ERR_ALIGNMENT;
 
   Dec8Params p;
@@ -511,7 +485,7 @@ extern "C" int cmb_decode_attn_kv8(const void* q, int64_t q_ld, const void* k, i
   p.G = nh / nkv; p.nkv = nkv;
   p.t = t;
   p.key_valid = key_valid; p.kv_ld = kv_ld;
-  p.scale_log2 = scale * 1.4426950408889634f;
+  p.scale_log2 = scale * DEC_LOG2E;
   p.splits = s; p.chunk = chunk;
   p.ws = s == 1 ? nullptr : ws;
   p.out = (bf16_t*)out;
@@ -534,8 +508,7 @@ extern "C" int cmb_decode_attn_kv8(const void* q, int64_t q_ld, const void* k, i
 #undef DEC8_LAUNCH
   CMB_CHECK_LAUNCH();
   if (s > 1) {
-    hipLaunchKernelGGL(decode_combine_kernel<bf16_t>, dim3((unsigned)(B * nh)), dim3(128), 0, st, (const float*)ws, G, (int)hd,
-                       (int)s, (bf16_t*)out);
+    dec_launch_combine<bf16_t>(B * nh, ws, G, hd, s, out, st);
     CMB_CHECK_LAUNCH();
   }
   return CMB_OK;

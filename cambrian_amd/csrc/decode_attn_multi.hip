@@ -24,6 +24,7 @@
 // to bf16, the value later steps read), takes the new v rows from the arguments, stores both and attends to them under the
 // causal rule — no workgroup reads a slot that the launch writes.
 #include "decode_attn_common.h"
+#include "decode_attn_host.h"
 #include "tile_ops.h"
 #include "decode_attn_multi_layout.h"
 
@@ -294,38 +295,26 @@ __global__ void __launch_bounds__(128) decode_multi_combine_kernel(const float* 
   out[((b * Q + j) * (int64_t)nkv * G + (int64_t)kvh * G + g) * hd + d] = (bf16_t)(num / den);
 }
 
+// cmb_decode_attn's geometry rule in bf16, 1 .. DAM_MAX_Q tokens and at most DAM_MAX_ROWS query rows per KV head.  The plan is
+// cmb_decode_attn's over slots 0 .. t0 + Q - 1 (dec_plan_slots): the last chunk holds the step's own slots.
 bool dam_geometry_ok(int32_t nh, int32_t nkv, int32_t hd, int32_t Q) {
-  if (hd != 64 && hd != 96 && hd != 128) return false;
-  if (nh <= 0 || nkv <= 0 || nh % nkv != 0 || nh / nkv > DEC_MAX_GROUP) return false;
-  if (Q < 1 || Q > DAM_MAX_Q || Q * (nh / nkv) > DAM_MAX_ROWS) return false;
-  return true;
-}
-
-// cmb_decode_attn's plan over slots 0 .. t0 + Q - 1: the last chunk holds the step's own slots
-bool dam_plan(int64_t B, int32_t nkv, int64_t t0, int32_t Q, int32_t forced, int32_t* splits, int64_t* chunk) {
-  if (t0 < 0 || Q < 1 || Q > DAM_MAX_Q) return false;
-  return cmb_decode_attn_plan(B, nkv, t0 + Q - 1, forced, splits, chunk, nullptr) == CMB_OK;
+  return dec_geometry_ok(CMB_BF16, nh, nkv, hd) && Q >= 1 && Q <= DAM_MAX_Q && Q * (nh / nkv) <= DAM_MAX_ROWS;
 }
 
 }  // namespace
 
 extern "C" int cmb_decode_attn_multi_plan(int64_t B, int32_t nkv, int64_t t0, int32_t Q, int32_t splits, int32_t* splits_out,
                                           int64_t* chunk_out, int32_t* max_splits_out) {
-  if (max_splits_out) *max_splits_out = DEC_MAX_SPLITS;
-  int32_t s = 0;
-  int64_t ch = 0;
-  if (!dam_plan(B, nkv, t0, Q, splits, &s, &ch)) return CMB_ERR_BAD_ARG;
-  if (splits_out) *splits_out = s;
-  if (chunk_out) *chunk_out = ch;
-  return CMB_OK;
+  // more than DAM_MAX_Q tokens are planned as none, which is rejected
+  return dec_plan_slots(B, nkv, t0, Q > DAM_MAX_Q ? 0 : Q, splits, splits_out, chunk_out, max_splits_out);
 }
 
 extern "C" int64_t cmb_decode_attn_multi_ws(int64_t B, int32_t nh, int32_t nkv, int32_t hd, int32_t Q, int64_t t0,
                                             int32_t splits) {
   int32_t s = 0;
-  int64_t ch = 0;
-  if (!dam_geometry_ok(nh, nkv, hd, Q) || !dam_plan(B, nkv, t0, Q, splits, &s, &ch)) return CMB_ERR_BAD_ARG;
-  return s == 1 ? 0 : B * Q * nh * s * (int64_t)(hd + 2);
+  if (!dam_geometry_ok(nh, nkv, hd, Q) || dec_plan_slots(B, nkv, t0, Q, splits, &s, nullptr, nullptr) != CMB_OK)
+    return CMB_ERR_BAD_ARG;
+  return dec_ws_need(B * Q * nh, s, hd);
 }
 
 extern "C" int cmb_decode_attn_multi(const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v, int64_t v_ld,
@@ -333,19 +322,15 @@ extern "C" int cmb_decode_attn_multi(const void* q, int64_t q_ld, const void* k,
                                      int64_t c_sh, int64_t c_st, int64_t B, int32_t nh, int32_t nkv, int32_t hd, int32_t Q,
                                      int64_t t0, const uint8_t* key_valid, int64_t kv_ld, float scale, int32_t splits, float* ws,
                                      int64_t ws_floats, void* out, void* stream) {
-  if (!q || !k || !v || !cos_t || !sin_t || !kcache || !vcache || !key_valid || !out) return CMB_ERR_BAD_ARG;
-  if (!dam_geometry_ok(nh, nkv, hd, Q) || B < 0 || B > 65535 || nkv > 65535 || t0 < 0 || kv_ld < t0 + Q)
-    return CMB_ERR_BAD_ARG;
+  if (!dec_all_set({q, k, v, cos_t, sin_t, kcache, vcache, key_valid, out})) return CMB_ERR_BAD_ARG;
+  if (!dam_geometry_ok(nh, nkv, hd, Q) || !dec_range_ok(B, nkv, t0, Q, kv_ld)) return CMB_ERR_BAD_ARG;
   if (B == 0) return CMB_OK;
   int32_t s = 0;
   int64_t chunk = 0;
-  if (!dam_plan(B, nkv, t0, Q, splits, &s, &chunk)) return CMB_ERR_BAD_ARG;
-  const int64_t need = s == 1 ? 0 : B * Q * nh * s * (int64_t)(hd + 2);
+  if (dec_plan_slots(B, nkv, t0, Q, splits, &s, &chunk, nullptr) != CMB_OK) return CMB_ERR_BAD_ARG;
+  const int64_t need = dec_ws_need(B * Q * nh, s, hd);
   if (need > 0 && (!ws || ws_floats < need)) return CMB_ERR_BAD_ARG;
-  if (!cmb_aligned16(q) || !cmb_aligned16(k) || !cmb_aligned16(v) || !cmb_aligned16(kcache) || !cmb_aligned16(vcache) ||
-      !cmb_aligned16(out) || (q_ld * 2) % 16 || (k_ld * 2) % 16 || (v_ld * 2) % 16 || (c_sb * 2) % 16 || (c_sh * 2) % 16 ||
-      (c_st * 2) % 16)
-    return CMB_ERR_ALIGNMENT;
+  if (!dec_aligned16({q, k, v, kcache, vcache, out}, {q_ld, k_ld, v_ld, c_sb, c_sh, c_st}, 2)) return CMB_ERR_ALIGNMENT;
 
   DamParams p;
   p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v;
@@ -356,7 +341,7 @@ extern "C" int cmb_decode_attn_multi(const void* q, int64_t q_ld, const void* k,
   p.G = nh / nkv; p.nkv = nkv; p.Q = Q; p.R = Q * p.G;
   p.t0 = t0;
   p.key_valid = key_valid; p.kv_ld = kv_ld;
-  p.scale_log2 = scale * 1.4426950408889634f;
+  p.scale_log2 = scale * DEC_LOG2E;
   p.splits = s; p.chunk = chunk;
   p.ws = s == 1 ? nullptr : ws;
   p.out = (bf16_t*)out;

@@ -2151,6 +2151,58 @@ def decode_attention_max_splits() -> int:
     return mx.value
 
 
+def _decode_attention_launch(name: str, symbol: str, ws_symbol: str, supported, q, k, v, cos, sin, kc, vc, factors: tuple,
+                             multi: bool, t0: int, key_valid, scale, splits: int) -> torch.Tensor:
+    """The one body of ``decode_attention``, ``decode_attention_multi`` and ``decode_attention_kv8``: every check in its
+    order, the device's workspace and the launch of ``symbol``.  ``name`` heads the messages, ``supported`` is the caller's
+    geometry test and ``ws_symbol`` its workspace query.  ``kc`` / ``vc``: the cache tensors [B, nkv, Lmax, hd]; of e4m3
+    caches the bytes, their fp32 factors being ``factors`` = (k, v), else ().  ``multi``: q holds Q rows per sequence, the
+    tokens of slots t0 .. t0 + Q - 1; else one row, slot t0."""
+    L.require_gpu(q, k, v, cos, sin, kc, vc, *factors, key_valid)
+    if torch.is_grad_enabled() and any(x.requires_grad for x in (q, k, v, kc, vc)):     # e4m3 caches: bytes, which never do
+        raise L.CambrianAmdError(f"{name} has no backward: call it under torch.no_grad()")
+    B, nkv, Lmax, hd = kc.shape
+    nh = q.shape[1] // hd
+    Q = 1 if not multi else q.shape[0] // B if B > 0 else 0
+    rows, dt = B * Q, q.dtype
+    if not (supported(dt, nh, nkv, hd, Q) if multi else supported(dt, nh, nkv, hd)) or q.shape != (rows, nh * hd) \
+            or k.shape != (rows, nkv * hd) or v.shape != k.shape or vc.shape != kc.shape \
+            or not (k.dtype == v.dtype == dt and kc.dtype == vc.dtype == (torch.uint8 if factors else dt)):
+        raise L.CambrianAmdError(
+            f"{name}: unsupported geometry q {tuple(q.shape)} {dt} k {tuple(k.shape)} cache {tuple(kc.shape)}" if factors else
+            f"{name}: unsupported geometry q {tuple(q.shape)} k {tuple(k.shape)} cache {tuple(kc.shape)} {dt}")
+    if not 0 <= t0 or t0 + Q > Lmax or key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] < t0 + Q:
+        raise L.CambrianAmdError(f"{name}: {'slots t0 .. t0 + Q - 1' if multi else 'slot t'} outside the cache or the key mask")
+    if q.stride(1) != 1 or k.stride(1) != 1 or v.stride(1) != 1 or kc.stride(3) != 1 or vc.stride() != kc.stride() \
+            or (factors and factors[1].stride() != factors[0].stride()) or key_valid.stride(1) != 1:
+        raise L.CambrianAmdError(
+            f"{name}: rows of q / k / v and the key mask must be contiguous, and the two caches of one layout" if factors else
+            f"{name}: rows of q / k / v, the caches and the key mask must be contiguous")
+    if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape != (rows, hd // 2) or sin.shape != cos.shape \
+            or not cos.is_contiguous() or not sin.is_contiguous():
+        raise L.CambrianAmdError(f"{name}: cos / sin are the contiguous fp32 [{'B*Q' if multi else 'B'}, hd/2] tables of rope_table")
+    if key_valid.dtype == torch.bool:
+        key_valid = key_valid.view(torch.uint8)
+    elif key_valid.dtype != torch.uint8:
+        raise L.CambrianAmdError(f"{name}: key_valid is a bool / uint8 mask")
+    scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
+    slots = (Q, t0) if multi else (t0,)
+    need = getattr(L.load(), ws_symbol)(B, nh, nkv, hd, *slots, splits)
+    if need < 0:
+        L.check(int(need), ws_symbol)
+    ws = _DECODE_WS.get(q.device)
+    if need > 0 and (ws is None or ws.numel() < need):
+        ws = _DECODE_WS[q.device] = torch.empty(int(need), dtype=torch.float32, device=q.device)
+    out = torch.empty((rows, nh * hd), dtype=dt, device=q.device)
+    lead = () if multi or factors else (L.dtype_code(dt),)           # the two bf16-only entry points take no dtype code
+    fac = (factors[0].data_ptr(), factors[1].data_ptr(), factors[0].stride(0), factors[0].stride(1)) if factors else ()
+    L.call(symbol, *lead, q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), cos.data_ptr(),
+           sin.data_ptr(), kc.data_ptr(), vc.data_ptr(), kc.stride(0), kc.stride(1), kc.stride(2), *fac, B, nh, nkv, hd, *slots,
+           key_valid.data_ptr(), key_valid.stride(0), scale, splits, L.ptr(ws) if need > 0 else None, int(need),
+           out.data_ptr(), device=q.device)
+    return out
+
+
 def decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
                      kcache: torch.Tensor, vcache: torch.Tensor, t: int, key_valid: torch.Tensor,
                      scale: Optional[float] = None, splits: int = 0) -> torch.Tensor:
@@ -2158,41 +2210,8 @@ def decode_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: tor
     packed row are fine), cos / sin fp32 [B, hd/2], k / v caches [B, nkv, Lmax, hd] -> out [B, nh*hd].  Ropes q and k, stores
     roped k and v into cache slot ``t`` and attends to slots 0..t under ``key_valid`` (bool / uint8 [B, >= t+1], slot t
     always open).  Inference only: there is no backward."""
-    L.require_gpu(q, k, v, cos, sin, kcache, vcache, key_valid)
-    if torch.is_grad_enabled() and any(x.requires_grad for x in (q, k, v, kcache, vcache)):
-        raise L.CambrianAmdError("decode_attention has no backward: call it under torch.no_grad()")
-    B, nkv, Lmax, hd = kcache.shape
-    nh = q.shape[1] // hd
-    dt = q.dtype
-    if not decode_attention_supported(dt, nh, nkv, hd) or q.shape != (B, nh * hd) or k.shape != (B, nkv * hd) \
-            or v.shape != k.shape or vcache.shape != kcache.shape or not (k.dtype == v.dtype == kcache.dtype == vcache.dtype == dt):
-        raise L.CambrianAmdError(f"decode_attention: unsupported geometry q {tuple(q.shape)} k {tuple(k.shape)} "
-                                 f"cache {tuple(kcache.shape)} {dt}")
-    if not 0 <= t < Lmax or key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] < t + 1:
-        raise L.CambrianAmdError("decode_attention: slot t outside the cache or the key mask")
-    if q.stride(1) != 1 or k.stride(1) != 1 or v.stride(1) != 1 or kcache.stride(3) != 1 \
-            or vcache.stride() != kcache.stride() or key_valid.stride(1) != 1:
-        raise L.CambrianAmdError("decode_attention: rows of q / k / v, the caches and the key mask must be contiguous")
-    if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape != (B, hd // 2) or sin.shape != cos.shape \
-            or not cos.is_contiguous() or not sin.is_contiguous():
-        raise L.CambrianAmdError("decode_attention: cos / sin are the contiguous fp32 [B, hd/2] tables of rope_table")
-    if key_valid.dtype == torch.bool:
-        key_valid = key_valid.view(torch.uint8)
-    elif key_valid.dtype != torch.uint8:
-        raise L.CambrianAmdError("decode_attention: key_valid is a bool / uint8 mask")
-    scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
-    need = L.load().cmb_decode_attn_ws(B, nh, nkv, hd, t, splits)
-    if need < 0:
-        L.check(int(need), "cmb_decode_attn_ws")
-    ws = _DECODE_WS.get(q.device)
-    if need > 0 and (ws is None or ws.numel() < need):
-        ws = _DECODE_WS[q.device] = torch.empty(int(need), dtype=torch.float32, device=q.device)
-    out = torch.empty((B, nh * hd), dtype=dt, device=q.device)
-    L.call("cmb_decode_attn", L.dtype_code(dt), q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
-           cos.data_ptr(), sin.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), kcache.stride(0), kcache.stride(1),
-           kcache.stride(2), B, nh, nkv, hd, t, key_valid.data_ptr(), key_valid.stride(0), scale, splits,
-           L.ptr(ws) if need > 0 else None, int(need), out.data_ptr(), device=q.device)
-    return out
+    return _decode_attention_launch("decode_attention", "cmb_decode_attn", "cmb_decode_attn_ws", decode_attention_supported,
+                                    q, k, v, cos, sin, kcache, vcache, (), False, t, key_valid, scale, splits)
 
 
 def decode_attention_enabled() -> bool:
@@ -2231,42 +2250,9 @@ def decode_attention_multi(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, co
     [B, nkv, Lmax, hd] -> out [B*Q, nh*hd].  Ropes q and k, stores roped k and v of token j into cache slot ``t0 + j`` and lets
     token j attend to slots 0 .. t0 + j: cached slots under ``key_valid`` (bool / uint8 [B, >= t0+Q], columns >= t0 are not
     read), the step's own slots always.  Inference only: there is no backward."""
-    L.require_gpu(q, k, v, cos, sin, kcache, vcache, key_valid)
-    if torch.is_grad_enabled() and any(x.requires_grad for x in (q, k, v, kcache, vcache)):
-        raise L.CambrianAmdError("decode_attention_multi has no backward: call it under torch.no_grad()")
-    B, nkv, Lmax, hd = kcache.shape
-    nh = q.shape[1] // hd
-    Q = q.shape[0] // B if B > 0 else 0
-    dt = q.dtype
-    if not decode_attention_multi_supported(dt, nh, nkv, hd, Q) or q.shape != (B * Q, nh * hd) or k.shape != (B * Q, nkv * hd) \
-            or v.shape != k.shape or vcache.shape != kcache.shape or not (k.dtype == v.dtype == kcache.dtype == vcache.dtype == dt):
-        raise L.CambrianAmdError(f"decode_attention_multi: unsupported geometry q {tuple(q.shape)} k {tuple(k.shape)} "
-                                 f"cache {tuple(kcache.shape)} {dt}")
-    if not 0 <= t0 or t0 + Q > Lmax or key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] < t0 + Q:
-        raise L.CambrianAmdError("decode_attention_multi: slots t0 .. t0 + Q - 1 outside the cache or the key mask")
-    if q.stride(1) != 1 or k.stride(1) != 1 or v.stride(1) != 1 or kcache.stride(3) != 1 \
-            or vcache.stride() != kcache.stride() or key_valid.stride(1) != 1:
-        raise L.CambrianAmdError("decode_attention_multi: rows of q / k / v, the caches and the key mask must be contiguous")
-    if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape != (B * Q, hd // 2) or sin.shape != cos.shape \
-            or not cos.is_contiguous() or not sin.is_contiguous():
-        raise L.CambrianAmdError("decode_attention_multi: cos / sin are the contiguous fp32 [B*Q, hd/2] tables of rope_table")
-    if key_valid.dtype == torch.bool:
-        key_valid = key_valid.view(torch.uint8)
-    elif key_valid.dtype != torch.uint8:
-        raise L.CambrianAmdError("decode_attention_multi: key_valid is a bool / uint8 mask")
-    scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
-    need = L.load().cmb_decode_attn_multi_ws(B, nh, nkv, hd, Q, t0, splits)
-    if need < 0:
-        L.check(int(need), "cmb_decode_attn_multi_ws")
-    ws = _DECODE_WS.get(q.device)
-    if need > 0 and (ws is None or ws.numel() < need):
-        ws = _DECODE_WS[q.device] = torch.empty(int(need), dtype=torch.float32, device=q.device)
-    out = torch.empty((B * Q, nh * hd), dtype=dt, device=q.device)
-    L.call("cmb_decode_attn_multi", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
-           cos.data_ptr(), sin.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), kcache.stride(0), kcache.stride(1),
-           kcache.stride(2), B, nh, nkv, hd, Q, t0, key_valid.data_ptr(), key_valid.stride(0), scale, splits,
-           L.ptr(ws) if need > 0 else None, int(need), out.data_ptr(), device=q.device)
-    return out
+    return _decode_attention_launch("decode_attention_multi", "cmb_decode_attn_multi", "cmb_decode_attn_multi_ws",
+                                    decode_attention_multi_supported, q, k, v, cos, sin, kcache, vcache, (), True, t0,
+                                    key_valid, scale, splits)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2349,42 +2335,9 @@ def decode_attention_kv8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos:
     """``decode_attention`` on e4m3 caches: bf16 q [B, nh*hd], k / v [B, nkv*hd], the caches ``KvCacheE4M3`` of one shape and
     stride -> out bf16 [B, nh*hd].  Ropes q and k, quantises roped k (rounded to bf16 first) and raw v into slot ``t`` (bytes
     and factors) and attends to slots 0..t as stored.  Inference only."""
-    L.require_gpu(q, k, v, cos, sin, kcache.q, kcache.inv, vcache.q, vcache.inv, key_valid)
-    if torch.is_grad_enabled() and any(x.requires_grad for x in (q, k, v)):
-        raise L.CambrianAmdError("decode_attention_kv8 has no backward: call it under torch.no_grad()")
-    B, nkv, Lmax, hd = kcache.q.shape
-    nh = q.shape[1] // hd
-    if not decode_attention_kv8_supported(q.dtype, nh, nkv, hd) or q.shape != (B, nh * hd) or k.shape != (B, nkv * hd) \
-            or v.shape != k.shape or vcache.q.shape != kcache.q.shape or not (k.dtype == v.dtype == q.dtype):
-        raise L.CambrianAmdError(f"decode_attention_kv8: unsupported geometry q {tuple(q.shape)} {q.dtype} k {tuple(k.shape)} "
-                                 f"cache {tuple(kcache.q.shape)}")
-    if not 0 <= t < Lmax or key_valid.dim() != 2 or key_valid.shape[0] != B or key_valid.shape[1] < t + 1:
-        raise L.CambrianAmdError("decode_attention_kv8: slot t outside the cache or the key mask")
-    if q.stride(1) != 1 or k.stride(1) != 1 or v.stride(1) != 1 or vcache.q.stride() != kcache.q.stride() \
-            or vcache.inv.stride() != kcache.inv.stride() or key_valid.stride(1) != 1:
-        raise L.CambrianAmdError("decode_attention_kv8: rows of q / k / v and the key mask must be contiguous, and the two "
-                                 "caches of one layout")
-    if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape != (B, hd // 2) or sin.shape != cos.shape \
-            or not cos.is_contiguous() or not sin.is_contiguous():
-        raise L.CambrianAmdError("decode_attention_kv8: cos / sin are the contiguous fp32 [B, hd/2] tables of rope_table")
-    if key_valid.dtype == torch.bool:
-        key_valid = key_valid.view(torch.uint8)
-    elif key_valid.dtype != torch.uint8:
-        raise L.CambrianAmdError("decode_attention_kv8: key_valid is a bool / uint8 mask")
-    scale = 1.0 / math.sqrt(hd) if scale is None else float(scale)
-    need = L.load().cmb_decode_attn_ws(B, nh, nkv, hd, t, splits)
-    if need < 0:
-        L.check(int(need), "cmb_decode_attn_ws")
-    ws = _DECODE_WS.get(q.device)
-    if need > 0 and (ws is None or ws.numel() < need):
-        ws = _DECODE_WS[q.device] = torch.empty(int(need), dtype=torch.float32, device=q.device)
-    out = torch.empty((B, nh * hd), dtype=q.dtype, device=q.device)
-    L.call("cmb_decode_attn_kv8", q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
-           cos.data_ptr(), sin.data_ptr(), kcache.q.data_ptr(), vcache.q.data_ptr(), kcache.q.stride(0), kcache.q.stride(1),
-           kcache.q.stride(2), kcache.inv.data_ptr(), vcache.inv.data_ptr(), kcache.inv.stride(0), kcache.inv.stride(1), B, nh,
-           nkv, hd, t, key_valid.data_ptr(), key_valid.stride(0), scale, splits, L.ptr(ws) if need > 0 else None, int(need),
-           out.data_ptr(), device=q.device)
-    return out
+    return _decode_attention_launch("decode_attention_kv8", "cmb_decode_attn_kv8", "cmb_decode_attn_ws",
+                                    decode_attention_kv8_supported, q, k, v, cos, sin, kcache.q, vcache.q,
+                                    (kcache.inv, vcache.inv), False, t, key_valid, scale, splits)
 
 
 def decode_attention_any(q, k, v, cos, sin, kcache, vcache, t: int, key_valid) -> torch.Tensor:

@@ -289,3 +289,90 @@ def test_requires_grad_inputs_raise(dev):
     valid = torch.ones(1, 4 + TAIL, dtype=torch.bool, device=dev)
     with pytest.raises(CambrianAmdError, match="no backward"):
         ops.decode_attention(q.to(dev).requires_grad_(), k.to(dev), v.to(dev), cos, sin, kc.to(dev), vc.to(dev), 3, valid)
+
+
+# ------------------------------------------------------------------------------------------------
+# the host path that decode_attention, decode_attention_kv8 and decode_attention_multi share: message texts and the workspace
+# ------------------------------------------------------------------------------------------------
+ENTRIES = ["decode_attention", "decode_attention_kv8", "decode_attention_multi"]
+
+
+def _entry_case(dev, entry):
+    """(call(**overrides) -> out, the call's arguments by name, its workspace need at a forced split in two) on B 1, 4 / 2 heads
+    of 64, 8 cache slots, bf16; ``decode_attention_multi`` with Q = 2 rows."""
+    ops = _ops()
+    B, nh, nkv, hd, Lmax = 1, 4, 2, 64, 8
+    Q = 2 if entry == "decode_attention_multi" else 1
+    g = torch.Generator().manual_seed(11)
+    a = dict(q=torch.randn(B * Q, nh * hd, generator=g).bfloat16().to(dev),
+             k=torch.randn(B * Q, nkv * hd, generator=g).bfloat16().to(dev),
+             v=torch.randn(B * Q, nkv * hd, generator=g).bfloat16().to(dev), t=5,
+             key_valid=torch.ones(B, Lmax, dtype=torch.bool, device=dev), splits=2)
+    a["cos"], a["sin"] = ops.rope_table(torch.arange(5, 5 + Q, device=dev).view(B * Q, 1), hd, THETA)
+    kc, vc = (torch.randn(B, nkv, Lmax, hd, generator=g).bfloat16().to(dev) for _ in range(2))
+    if entry == "decode_attention_kv8":
+        kc, vc = (ops.kv_quantize_e4m3(c, ops.KvCacheE4M3.empty(B, nkv, Lmax, hd, dev)) for c in (kc, vc))
+    a["kc"], a["vc"] = kc, vc
+    fn = getattr(ops, entry)
+
+    def call(**kw):
+        x = dict(a, **kw)
+        return fn(x["q"], x["k"], x["v"], x["cos"], x["sin"], x["kc"], x["vc"], x["t"], x["key_valid"], splits=x["splits"])
+
+    lib = ops.L.load()
+    need = lib.cmb_decode_attn_multi_ws(B, nh, nkv, hd, Q, 5, 2) if Q > 1 else lib.cmb_decode_attn_ws(B, nh, nkv, hd, 5, 2)
+    assert need == B * Q * nh * 2 * (hd + 2)
+    return call, a, need
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+def test_validation_messages_of_the_three_entry_points(dev, entry):
+    """One input per message, the literal texts: they name the public function, and ``decode_attention_kv8`` words two of
+    them in its own way."""
+    import re
+    from cambrian_amd.lib import CambrianAmdError
+    call, a, _ = _entry_case(dev, entry)
+    multi, kv8 = entry == "decode_attention_multi", entry == "decode_attention_kv8"
+    rows = 2 if multi else 1
+
+    def raises(text, **kw):
+        with pytest.raises(CambrianAmdError, match="^" + re.escape(text) + "$"):
+            call(**kw)
+
+    wide = torch.zeros(rows, 2 * 256, dtype=torch.bfloat16, device=dev)
+    if kv8:
+        raises("decode_attention_kv8: unsupported geometry q (1, 320) torch.bfloat16 k (1, 128) cache (1, 2, 8, 64)", q=wide[:, :320])
+        raises("decode_attention_kv8: rows of q / k / v and the key mask must be contiguous, and the two caches of one layout",
+               q=wide[:, ::2])
+    else:
+        raises(f"{entry}: unsupported geometry q ({rows}, 320) k ({rows}, 128) cache (1, 2, 8, 64) torch.bfloat16", q=wide[:, :320])
+        raises(f"{entry}: rows of q / k / v, the caches and the key mask must be contiguous", q=wide[:, ::2])
+    if multi:
+        raises("decode_attention_multi: slots t0 .. t0 + Q - 1 outside the cache or the key mask", t=7)
+        raises("decode_attention_multi: cos / sin are the contiguous fp32 [B*Q, hd/2] tables of rope_table", cos=a["cos"].double())
+    else:
+        raises(f"{entry}: slot t outside the cache or the key mask", t=8)
+        raises(f"{entry}: cos / sin are the contiguous fp32 [B, hd/2] tables of rope_table", cos=a["cos"].double())
+    raises(f"{entry}: key_valid is a bool / uint8 mask", key_valid=a["key_valid"].to(torch.int32))
+    assert torch.is_grad_enabled()
+    raises(f"{entry} has no backward: call it under torch.no_grad()", q=a["q"].clone().requires_grad_())
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+def test_split_call_takes_the_one_workspace_of_the_device(dev, entry, monkeypatch):
+    """A forced split in two at t = 5: the partials go through ``ops._DECODE_WS[device]``, the entry all three functions share
+    — one that is large enough is used as it is, a missing one is made with the size the library asks for — and the same
+    call gives the same bits."""
+    ops = _ops()
+    call, a, need = _entry_case(dev, entry)
+    held = torch.full((need + 64,), float("nan"), dtype=torch.float32, device=dev)
+    monkeypatch.setattr(ops, "_DECODE_WS", {a["q"].device: held})
+    out = call()
+    assert list(ops._DECODE_WS) == [a["q"].device] and ops._DECODE_WS[a["q"].device] is held
+    assert torch.isfinite(held[:need]).all() and torch.isnan(held[need:]).all()      # the partials went there, and only there
+    assert out.shape == a["q"].shape and out.dtype == torch.bfloat16 and torch.isfinite(out).all()
+    assert torch.equal(call(), out)
+    monkeypatch.setattr(ops, "_DECODE_WS", {})
+    assert torch.equal(call(), out)
+    assert list(ops._DECODE_WS) == [a["q"].device] and ops._DECODE_WS[a["q"].device].numel() == need
+    assert torch.equal(call(splits=2), out) and ops._DECODE_WS[a["q"].device].numel() == need
