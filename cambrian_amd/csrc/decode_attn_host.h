@@ -1,5 +1,5 @@
-// decode_attn_host.h — the host side that cmb_decode_attn, cmb_decode_attn_kv8 and cmb_decode_attn_multi share: the argument
-// checks that run before a launch, the workspace need, the base-2 scale and the launch of decode_combine_kernel.  Host code
+// decode_attn_host.h — the host side that cmb_decode_attn, cmb_decode_attn_kv8, cmb_decode_attn_multi and cmb_extend_attn share:
+// the argument checks that run before a launch, the workspace need, the base-2 scale and the launch of decode_combine_kernel.  Host code
 // only; included after decode_attn_common.h.  Each launcher keeps the ORDER of its checks (a call that breaks two rules gets the
 // status it always got, and the three look at B == 0 at different points), so the pieces here are predicates, not a sequence.
 #pragma once

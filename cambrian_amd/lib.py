@@ -309,6 +309,10 @@ SIGNATURES = {
                                         _i64, _p, _i64, _f, _i32, _p, _i64, _p, _p]),
     "cmb_decode_attn_multi_ws": (_i64, [_i64, _i32, _i32, _i32, _i32, _i64, _i32]),
     "cmb_decode_attn_multi_plan": (C.c_int, [_i64, _i32, _i64, _i32, _i32, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i32)]),
+    "cmb_extend_attn": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i64,
+                                  _p, _i64, _f, _i32, _p, _i64, _p, _p]),
+    "cmb_extend_attn_ws": (_i64, [_i64, _i32, _i32, _i32, _i32, _i64, _i32]),
+    "cmb_extend_attn_plan": (C.c_int, [_i64, _i32, _i64, _i32, _i32, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i32)]),
     "cmb_decode_next": (C.c_int, [_p, _i64, _i32, _i64, _i64, _p, _p, _i64, _i64, _p, _p, _p, _i64, _i64, _p, _i64, _i64, _i64, _p,
                                   _i64, _i32, _f, _p, _p, _p]),
     "cmb_decode_sample": (C.c_int, [_p, _i64, _i32, _i64, _f, _i64, _f, _p, _i64, _p, _p, _i64, _i64, _p, _p, _p, _i64, _i64, _p,

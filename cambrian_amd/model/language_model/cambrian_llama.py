@@ -17,6 +17,7 @@ from __future__ import annotations
 import os
 
 import math
+import weakref
 from typing import List, Optional, Tuple
 
 import torch
@@ -33,7 +34,7 @@ except Exception:  # pragma: no cover - transformers is part of the image
 
 from ... import lib as _lib
 from ... import ops
-from ...constants import IGNORE_INDEX
+from ...constants import IGNORE_INDEX, IMAGE_TOKEN_INDEX
 from ..cambrian_arch import CambrianMetaForCausalLM, CambrianMetaModel, SvaContext
 from . import processors as PROC
 from .beam import BeamState, beam_done, beam_fill, beam_result, beam_update
@@ -202,6 +203,12 @@ def use_decode_kernel(x: torch.Tensor, nh: int, nkv: int, hd: int) -> bool:
     back-propagate, and not switched off with ``CAMBRIAN_AMD_DECODE_ATTN=0`` (A/B against the SDPA body)."""
     return (x.is_cuda and ops.decode_attention_enabled() and ops.decode_attention_supported(x.dtype, nh, nkv, hd)
             and not (torch.is_grad_enabled() and x.requires_grad))
+
+
+def use_extend_kernel(x: torch.Tensor, nh: int, nkv: int, hd: int, Q: int) -> bool:
+    """Whether a chunk of Q tokens runs on ``ops.extend_attention``: ``use_decode_kernel``'s conditions (so
+    ``CAMBRIAN_AMD_DECODE_ATTN=0`` switches it off too) and a geometry ``cmb_extend_attn`` takes, which is bf16 only."""
+    return use_decode_kernel(x, nh, nkv, hd) and ops.extend_attention_supported(x.dtype, nh, nkv, hd, Q)
 
 
 def _frozen_plain(*mods) -> bool:
@@ -455,6 +462,32 @@ class LlamaAttention(nn.Module):
                                            attn_mask=lookup_mask(key_mask, t0, Q)[None, None], enable_gqa=self.nkv != self.nh)
         return self.o_proj(o[0].transpose(0, 1).reshape(Q, 1, self.nh * self.hd))
 
+    def extend(self, x, cos, sin, kcache, vcache, t0: int, key_mask):
+        """A chunk of Q consecutive new tokens per sequence against the cache (the suffix of a prompt over a cached prefix):
+        x [B,Q,H]; cos / sin [B*Q, hd/2] at the tokens' positions; caches [B,nkv,Lmax,hd], slots t0 .. t0+Q-1 are filled here;
+        token j attends under ``ops.extend_mask`` (key_mask bool [B, >= t0+Q], read through column t0+Q-1).  On the GPU in
+        bf16 everything between the projections and o_proj is one ``ops.extend_attention`` call (extend_attn.hip); fp32, other
+        geometries and ``CAMBRIAN_AMD_DECODE_ATTN=0`` run the plain torch body below."""
+        B, Q, _ = x.shape
+        if use_extend_kernel(x, self.nh, self.nkv, self.hd, Q):
+            nq, nk = self.nh * self.hd, self.nkv * self.hd
+            w_qkv = _fused_frozen_weight(self, "_w_qkv", (self.q_proj, self.k_proj, self.v_proj))
+            x2 = x.reshape(B * Q, -1)
+            if w_qkv is not None:
+                row = frozen_linear(self, "_w_qkv_t", x2, w_qkv)             # q heads | k heads | v heads per token
+                q, k, v = row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:]
+            else:
+                q, k, v = self.q_proj(x2), self.k_proj(x2), self.v_proj(x2)
+            o = ops.extend_attention(q, k, v, cos, sin, kcache, vcache, t0, key_mask)
+            return _lin(self.o_proj, o.view(B, Q, nq))
+        q = ops.rope(self.q_proj(x).view(B * Q, self.nh, self.hd), cos, sin).view(B, Q, self.nh, self.hd).transpose(1, 2)
+        k = ops.rope(self.k_proj(x).view(B * Q, self.nkv, self.hd), cos, sin).view(B, Q, self.nkv, self.hd).transpose(1, 2)
+        kcache[:, :, t0:t0 + Q] = k
+        vcache[:, :, t0:t0 + Q] = self.v_proj(x).view(B, Q, self.nkv, self.hd).transpose(1, 2)
+        o = F.scaled_dot_product_attention(q, kcache[:, :, :t0 + Q], vcache[:, :, :t0 + Q],
+                                           attn_mask=ops.extend_mask(key_mask, t0, Q)[:, None], enable_gqa=self.nkv != self.nh)
+        return self.o_proj(o.transpose(1, 2).reshape(B, Q, self.nh * self.hd))
+
 
 class LlamaDecoderLayer(nn.Module):
     def __init__(self, cfg, device, dtype):
@@ -471,6 +504,16 @@ class LlamaDecoderLayer(nn.Module):
         a = self.self_attn(xn, cos, sin, attn_mask, kv_out)
         n2 = self.post_attention_layernorm
         x, h = ops.add_rmsnorm(x, a, n2.weight, n2.variance_epsilon)  # x + a and norm(x + a) in one pass
+        return self.mlp(h, residual=x)
+
+    def extend(self, x, cos, sin, kcache, vcache, t0: int, key_mask):
+        """``forward`` for a chunk x [B,Q,H] of new tokens against the cache (``self_attn.extend``): the same norms, MLP and
+        frozen-linear route — GEMM-sized rows, so the weight-streaming decode linears and their reduced formats play no part."""
+        n1 = self.input_layernorm
+        x, xn = ops.rmsnorm_fork(x, n1.weight, n1.variance_epsilon)
+        a = self.self_attn.extend(xn, cos, sin, kcache, vcache, t0, key_mask)
+        n2 = self.post_attention_layernorm
+        x, h = ops.add_rmsnorm(x, a, n2.weight, n2.variance_epsilon)
         return self.mlp(h, residual=x)
 
     def decode_entries(self, fmt=None):
@@ -934,7 +977,8 @@ class DecodeStepPlan:
 
 def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: int = 16, do_sample: bool = False,
               temperature: float = 1.0, eos_token_id=None, attention_mask=None, position_ids=None, top_p=None, top_k=None,
-              num_beams: int = 1, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, _draft_fn=None, **kwargs):
+              num_beams: int = 1, prompt_lookup_num_tokens=None, max_matching_ngram_size=None, _draft_fn=None, prefix=None,
+              **kwargs):
     """cambrian_llama.py:437-483: ``generate(input_ids, images=, image_sizes=)`` of the eval harness
     (eval/eval/*/…_eval.py, e.g. gqa_eval.py:108-117: do_sample / temperature / top_p / num_beams / max_new_tokens /
     use_cache).  Prefill = the eval branch of prepare_inputs_labels_for_multimodal + the decoder with the per-sample in-LLM
@@ -954,7 +998,12 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
     processors define them over the GENERATED ids (``processors.py``; one ``ops.decode_process`` launch per token before the
     selection, on both loops), and ``eos_token_id`` may be a list: a row is done from its first id of the set and then emits
     ``eos[0]``.  They do not combine with beam search or prompt-lookup decoding (NotImplementedError); switched off, anything
-    but their off values raises a ValueError that names the switch."""
+    but their off values raises a ValueError that names the switch.
+    ``prefix`` (a ``PrefixCache`` of ``prefill_prefix``): ``inputs`` [N, Q] are then N >= 1 suffixes of the ONE cached prompt
+    head, left-padded under ``attention_mask``; the head's K / V is copied into every row's cache, one ``extend_step`` runs the
+    suffixes against it and the loops below go on from slot P + Q.  Row n returns what ``generate(cat(prefix_ids, suffix_n),
+    images=...)`` returns for that prompt alone (``_prefix_args`` has what is refused)."""
+    _prefix_args(self, prefix, inputs, attention_mask, images, num_beams, prompt_lookup_num_tokens, position_ids, image_sizes)
     if "inputs_embeds" in kwargs:
         raise NotImplementedError("`inputs_embeds` is not supported")          # cambrian_llama.py:447-448
     beams = 1 if num_beams is None else int(num_beams)
@@ -985,34 +1034,24 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
     prompt_ids, prompt_mask = inputs, attention_mask        # what the lookup drafts from (the multimodal prefill replaces both)
     with torch.no_grad():
         model = self.model
-        if images is not None:
-            self._dynamic_path = True
-            try:
-                (_, position_ids, attention_mask, _, inputs_embeds, _, kv, masks, final_size, ctx) = \
-                    self.prepare_inputs_labels_for_multimodal(inputs, position_ids, attention_mask, None, None, images,
-                                                              image_sizes=image_sizes)
-            finally:
-                self._dynamic_path = False
-            sva = None if kv is None else SvaDynamic(kv, masks, final_size, ctx)
-        else:
-            inputs_embeds, sva = model.embed_tokens(inputs), None
-        B, L, _ = inputs_embeds.shape
-        dev = inputs_embeds.device
-        valid = torch.ones(B, L, dtype=torch.bool, device=dev) if attention_mask is None else attention_mask.bool()
-        pos = (valid.long().cumsum(1) - 1).clamp_min(0) if position_ids is None else position_ids
-        kv_out: list = []
-        hidden = model(inputs_embeds.to(model.llm_dtype), pos, attention_mask, sva, kv_out=kv_out)
-        last = valid.long().sum(1) - 1                                              # last real token of every row
-        if not bool((valid[:, 1:] <= valid[:, :-1]).all()):
-            last = torch.full_like(last, L - 1)                                      # left padding: the last column
-        logits = self.lm_head(hidden[torch.arange(B, device=dev), last]).float()
         nh_kv, hd = model.layers[0].self_attn.nkv, model.layers[0].self_attn.hd
-        if beams > 1:
-            return _beam_search(self, logits, kv_out, valid, L, int(max_new_tokens), eos_token_id, kwargs.get("pad_token_id"),
-                                beams, _kv8_wanted(self, dev, kv_out))
-        Lmax = L + max_new_tokens
-        # e4m3 K / V cache, opt-in: resolved once per call
-        caches = (_kv8_prefill if _kv8_wanted(self, dev, kv_out) else _bf16_prefill)(kv_out, B, 1, nh_kv, L, Lmax, hd, dev)
+        if prefix is not None:
+            logits, caches, valid = _prefix_extend(self, prefix, inputs, attention_mask, int(max_new_tokens))
+            (B, L), dev = valid.shape, valid.device
+            Lmax = L + max_new_tokens
+        else:
+            hidden, kv_out, valid = _prefill(self, inputs, images, image_sizes, attention_mask, position_ids)
+            (B, L), dev = valid.shape, valid.device
+            last = valid.long().sum(1) - 1                                              # last real token of every row
+            if not bool((valid[:, 1:] <= valid[:, :-1]).all()):
+                last = torch.full_like(last, L - 1)                                      # left padding: the last column
+            logits = self.lm_head(hidden[torch.arange(B, device=dev), last]).float()
+            if beams > 1:
+                return _beam_search(self, logits, kv_out, valid, L, int(max_new_tokens), eos_token_id,
+                                    kwargs.get("pad_token_id"), beams, _kv8_wanted(self, dev, kv_out))
+            Lmax = L + max_new_tokens
+            # e4m3 K / V cache, opt-in: resolved once per call
+            caches = (_kv8_prefill if _kv8_wanted(self, dev, kv_out) else _bf16_prefill)(kv_out, B, 1, nh_kv, L, Lmax, hd, dev)
         key_mask = torch.zeros(B, Lmax, dtype=torch.bool, device=dev)
         key_mask[:, :L] = valid
         n_tok = valid.long().sum(1)
@@ -1064,6 +1103,138 @@ def _generate(self, inputs=None, images=None, image_sizes=None, max_new_tokens: 
             else:
                 logits = _decode_token(self, x, cos, sin, caches, t, key_mask, fp8, fp4)
         return torch.stack(out_ids, 1)
+
+
+def _prefill(self, inputs, images, image_sizes, attention_mask, position_ids):
+    """The prefill of ``generate`` and ``prefill_prefix``: the eval branch of prepare_inputs_labels_for_multimodal (with
+    ``images``) and the decoder with the per-sample in-LLM SVA hook, K / V of every layer kept.  -> (hidden [B, L, H], kv_out:
+    (k, v) [B, nkv, L, hd] per layer, valid bool [B, L]); L is the length after the image expansion.  Under no_grad."""
+    model = self.model
+    if images is not None:
+        self._dynamic_path = True
+        try:
+            (_, position_ids, attention_mask, _, inputs_embeds, _, kv, masks, final_size, ctx) = \
+                self.prepare_inputs_labels_for_multimodal(inputs, position_ids, attention_mask, None, None, images,
+                                                          image_sizes=image_sizes)
+        finally:
+            self._dynamic_path = False
+        sva = None if kv is None else SvaDynamic(kv, masks, final_size, ctx)
+    else:
+        inputs_embeds, sva = model.embed_tokens(inputs), None
+    B, L, _ = inputs_embeds.shape
+    dev = inputs_embeds.device
+    valid = torch.ones(B, L, dtype=torch.bool, device=dev) if attention_mask is None else attention_mask.bool()
+    pos = (valid.long().cumsum(1) - 1).clamp_min(0) if position_ids is None else position_ids
+    kv_out: list = []
+    hidden = model(inputs_embeds.to(model.llm_dtype), pos, attention_mask, sva, kv_out=kv_out)
+    return hidden, kv_out, valid
+
+
+class PrefixCache:
+    """What ``prefill_prefix`` keeps of ONE prompt head, read-only: ``kv`` — every layer's (k, v) [1, nkv, P, hd] after RoPE;
+    ``key_mask`` bool [1, P]; ``n_tok`` — its valid tokens (the position of the next one); ``last_hidden`` [1, H] — the final
+    norm's row of the last valid token; ``P`` — the length AFTER the image expansion; and the model (a weak reference), dtype,
+    device and (layers, nkv, hd) it was made with, for ``generate(prefix=...)``'s compatibility check.  ``generate`` copies
+    from it and never writes it, so one cache serves any number of calls."""
+
+    def __init__(self, owner, kv, key_mask, n_tok: int, last_hidden, dtype, device):
+        self.owner = weakref.ref(owner)
+        self.kv, self.key_mask, self.n_tok, self.last_hidden = kv, key_mask, int(n_tok), last_hidden
+        self.P = int(key_mask.shape[1])
+        self.dtype, self.device = dtype, device
+        self.geometry = (len(kv),) + ((kv[0][0].shape[1], kv[0][0].shape[3]) if kv else (0, 0))
+
+
+def prefill_prefix(self, inputs, images=None, image_sizes=None, attention_mask=None) -> PrefixCache:
+    """The prefill of ONE prompt head (batch 1) — system text, ``<image>``, anything every question shares — kept as a
+    ``PrefixCache`` for ``generate(suffix_ids, prefix=cache)``: exactly the prefill ``generate(inputs, images=...)`` runs
+    (towers, connector SVA, the in-LLM hook, every layer's K / V).  Attention is causal and the hook rewrites only the image
+    block's rows, so nothing in the head depends on what follows it."""
+    if inputs is None or inputs.dim() != 2 or inputs.shape[0] != 1 or inputs.shape[1] < 1:
+        raise ValueError("prefill_prefix: one prompt of at least one token, input ids [1, P]")
+    with torch.no_grad():
+        hidden, kv_out, valid = _prefill(self, inputs, images, image_sizes, attention_mask, None)
+        n_tok = int(valid.long().sum())
+        left_padded = not bool((valid[:, 1:] <= valid[:, :-1]).all())
+        last = valid.shape[1] - 1 if left_padded else max(n_tok - 1, 0)
+        return PrefixCache(self, [(k, v) for k, v in kv_out], valid, n_tok, hidden[:, last].clone(), self.model.llm_dtype,
+                           hidden.device)
+
+
+def _prefix_args(self, prefix, inputs, attention_mask, images, num_beams, lookup_tokens, position_ids=None,
+                 image_sizes=None) -> None:
+    """``generate(prefix=...)``'s refusals, all before the model is touched.  ValueError: no ``PrefixCache``, one of another
+    model, dtype or device, ``images`` / ``image_sizes`` / ``position_ids`` beside it, no suffix token, an image token in a suffix, a suffix mask that is not
+    left-padded.  NotImplementedError: beams, prompt lookup and the e4m3 K / V cache, which are not built on a prefix."""
+    if prefix is None:
+        return
+    if not isinstance(prefix, PrefixCache):
+        raise ValueError(f"generate(prefix=...): expected the PrefixCache of prefill_prefix, got {type(prefix).__name__}")
+    if images is not None:
+        raise ValueError("generate(prefix=..., images=...): images belong to the prefix (prefill_prefix(inputs, images=...)); a "
+                         "suffix holds text only")
+    if image_sizes is not None:
+        raise ValueError("generate(prefix=..., image_sizes=...): image sizes belong to the prefix "
+                         "(prefill_prefix(inputs, images=..., image_sizes=...))")
+    if position_ids is not None:
+        raise ValueError("generate(prefix=..., position_ids=...): suffix positions follow the prefix (its valid tokens + the "
+                         "running count of the suffix mask); explicit position ids are not taken")
+    if inputs is None or inputs.dim() != 2 or inputs.shape[0] < 1 or inputs.shape[1] < 1:
+        raise ValueError("generate(prefix=...): suffix ids [N, Q] with N >= 1 and Q >= 1 (Q == 0: there is nothing to extend "
+                         "the prefix with)")
+    if bool((inputs == IMAGE_TOKEN_INDEX).any()):
+        raise ValueError("generate(prefix=...): an image token in a suffix; images belong to the prefix")
+    if attention_mask is not None:
+        m = attention_mask.bool()
+        if m.shape != inputs.shape or not bool(m[:, -1].all()) or not bool((m[:, 1:] >= m[:, :-1]).all()):
+            raise ValueError("generate(prefix=...): the suffix mask has to be left-padded, [N, Q] with every row's valid tokens "
+                             "right-aligned")
+    layers = self.model.layers
+    a0 = layers[0].self_attn if len(layers) else None
+    if prefix.owner() is not self or prefix.dtype != self.model.llm_dtype or prefix.device != inputs.device \
+            or prefix.geometry != (len(layers), getattr(a0, "nkv", 0), getattr(a0, "hd", 0)):
+        raise ValueError("generate(prefix=...): the PrefixCache was made by another model, or in another dtype or on another "
+                         "device than this call's")
+    if num_beams is not None and int(num_beams) > 1:
+        raise NotImplementedError(f"generate(prefix=..., num_beams={num_beams}): beam search over a cached prefix is not "
+                                  "implemented (the caches would have to be spread over the beams)")
+    if not (lookup_tokens is None or (not isinstance(lookup_tokens, bool) and lookup_tokens == 0)):
+        raise NotImplementedError("generate(prefix=..., prompt_lookup_num_tokens=...): prompt-lookup decoding over a cached "
+                                  "prefix is not implemented")
+    if ops.decode_kv_fp8_enabled(getattr(getattr(self, "config", None), "decode_kv_fp8", False)):
+        raise NotImplementedError("generate(prefix=...): the chunk step reads and writes bf16 K / V caches; switch the e4m3 K / V "
+                                  "cache off (config.decode_kv_fp8 / CAMBRIAN_AMD_DECODE_KV_FP8)")
+
+
+def extend_step(self, ids, caches, t0: int, pos, key_mask) -> torch.Tensor:
+    """Final-norm hidden states [B, Q, H] of a chunk of Q new tokens ``ids`` [B, Q] per sequence against the caches:
+    embeddings, the RoPE table at ``pos`` [B, Q], every layer's ``extend`` (K / V of token j into cache slot t0 + j, attention
+    under ``ops.extend_mask`` of ``key_mask`` [B, >= t0 + Q]) and the final norm.  No SVA hook: a chunk holds no image tokens."""
+    model = self.model
+    hd = model.layers[0].self_attn.hd
+    cos, sin = ops.rope_table(pos, hd, float(getattr(self.config, "rope_theta", 10000.0)))
+    x = model.embed_tokens(ids).to(model.llm_dtype)
+    for layer, (kc, vc) in zip(model.layers, caches):
+        x = layer.extend(x, cos, sin, kc, vc, t0, key_mask)
+    return model.norm(x)
+
+
+def _prefix_extend(self, prefix: PrefixCache, ids, attention_mask, max_new_tokens: int):
+    """The prefill of ``generate(prefix=...)``: every layer's cache of P + Q + max_new_tokens slots per suffix row with the
+    prefix's columns copied in (``_bf16_prefill`` spreading one prompt over N rows; the ``PrefixCache`` is only read), then one
+    ``extend_step`` over the N suffixes.  -> (fp32 logits [N, V] of the last column, caches, valid bool [N, P + Q])."""
+    model = self.model
+    N, Q = ids.shape
+    P, dev = prefix.P, ids.device
+    a0 = model.layers[0].self_attn
+    caches = _bf16_prefill(prefix.kv, 1, N, a0.nkv, P, P + Q + max_new_tokens, a0.hd, dev)
+    valid = torch.ones(N, P + Q, dtype=torch.bool, device=dev)
+    valid[:, :P] = prefix.key_mask
+    if attention_mask is not None:
+        valid[:, P:] = attention_mask.bool()
+    pos = (prefix.n_tok + valid[:, P:].long().cumsum(1) - 1).clamp_min(0)
+    hidden = extend_step(self, ids, caches, P, pos, valid)
+    return self.lm_head(hidden[:, -1]).float(), caches, valid
 
 
 def _decode_token(self, x, cos, sin, caches, t: int, key_mask, fp8: bool, fp4: bool) -> torch.Tensor:
@@ -1360,6 +1531,8 @@ def _beam_fused(plan, emb, logits, key_mask, n_tok, L0: int, max_new_tokens: int
 
 
 CambrianLlamaForCausalLM.generate = _generate
+CambrianLlamaForCausalLM.prefill_prefix = prefill_prefix
+CambrianLlamaForCausalLM.extend_step = extend_step
 
 
 def llama3_8b_config(**overrides) -> CambrianConfig:

@@ -33,7 +33,7 @@ except Exception:  # pragma: no cover
 from ... import lib as L
 from ... import ops
 from .cambrian_llama import (CambrianLlamaForCausalLM, CambrianLlamaModel, HipRMSNorm, LlamaDecoderLayer, _down_proj,
-                             _frozen_plain, _lin, lookup_mask, use_decode_kernel)
+                             _frozen_plain, _lin, lookup_mask, use_decode_kernel, use_extend_kernel)
 
 
 class CambrianConfig(Phi3Config):
@@ -120,6 +120,22 @@ class Phi3Attention(nn.Module):
                                            attn_mask=lookup_mask(key_mask, t0, Q)[None, None], enable_gqa=self.nkv != self.nh)
         return self.o_proj(o[0].transpose(0, 1).reshape(Q, 1, self.nh * self.hd))
 
+    def extend(self, x, cos, sin, kcache, vcache, t0: int, key_mask):
+        """A chunk of Q consecutive new tokens per sequence against the cache (see LlamaAttention.extend): x [B,Q,H]; the
+        kernel takes q / k / v as views into the packed ``qkv_proj`` rows."""
+        B, Q, _ = x.shape
+        if use_extend_kernel(x, self.nh, self.nkv, self.hd, Q):
+            nq, nk = self.nh * self.hd, self.nkv * self.hd
+            row = _lin(self.qkv_proj, x.reshape(B * Q, -1))
+            o = ops.extend_attention(row[:, :nq], row[:, nq:nq + nk], row[:, nq + nk:], cos, sin, kcache, vcache, t0, key_mask)
+            return _lin(self.o_proj, o.view(B, Q, nq))
+        q, k, v = ops.qkv_rope(_lin(self.qkv_proj, x).contiguous(), cos, sin, self.nh, self.nkv, self.hd)   # [B,h,Q,hd]
+        kcache[:, :, t0:t0 + Q] = k
+        vcache[:, :, t0:t0 + Q] = v
+        o = F.scaled_dot_product_attention(q, kcache[:, :, :t0 + Q], vcache[:, :, :t0 + Q],
+                                           attn_mask=ops.extend_mask(key_mask, t0, Q)[:, None], enable_gqa=self.nkv != self.nh)
+        return _lin(self.o_proj, o.transpose(1, 2).reshape(B, Q, self.nh * self.hd))
+
 
 class Phi3DecoderLayer(nn.Module):
     def __init__(self, cfg, device, dtype):
@@ -150,8 +166,8 @@ class Phi3DecoderLayer(nn.Module):
         return w, tuple((m, "_w_" + fmt, wi, "swiglu" if m is mlp.gate_up_proj else None) for m, wi in zip(mods, w))
 
     # the step itself is the Llama layer's: one condition (decode_step_operands), one body
-    decode, decode_multi, decode_operands = (LlamaDecoderLayer.decode, LlamaDecoderLayer.decode_multi,
-                                             LlamaDecoderLayer.decode_operands)
+    decode, decode_multi, decode_operands, extend = (LlamaDecoderLayer.decode, LlamaDecoderLayer.decode_multi,
+                                                     LlamaDecoderLayer.decode_operands, LlamaDecoderLayer.extend)
 
 
 class CambrianPhi3Model(CambrianLlamaModel):

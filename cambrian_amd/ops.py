@@ -2256,6 +2256,47 @@ def decode_attention_multi(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, co
 
 
 # ------------------------------------------------------------------------------------------------
+# a chunk of Q new tokens per sequence against the cache (extend_attn.hip): the suffix of a prompt over a cached prefix
+# ------------------------------------------------------------------------------------------------
+EXTEND_MAX_ROWS = 4096          # tokens of a chunk
+
+
+def extend_attention_supported(dtype: torch.dtype, nh: int, nkv: int, hd: int, Q: int) -> bool:
+    """The geometries ``cmb_extend_attn`` takes: bf16, head_dim 64 / 96 / 128, G = nh / nkv <= 8, 1 <= Q <= 4096."""
+    return dtype == torch.bfloat16 and decode_attention_supported(dtype, nh, nkv, hd) and 1 <= Q <= EXTEND_MAX_ROWS
+
+
+def extend_attention_plan(B: int, nkv: int, t0: int, Q: int, splits: int = 0) -> Tuple[int, int]:
+    """(splits, chunk) of a Q-token chunk over cache slots 0 .. t0 + Q - 1, ``splits * chunk >= t0 + Q > (splits - 1) * chunk``.
+    ``splits`` = 0: the library's choice, a pure function of (B, nkv, t0, Q, CU count) that counts the chunk's row blocks as
+    batch rows, so long chunks split little or not at all."""
+    s, ch = C.c_int32(0), C.c_int64(0)
+    L.check(L.load().cmb_extend_attn_plan(B, nkv, t0, Q, splits, C.byref(s), C.byref(ch), None), "cmb_extend_attn_plan")
+    return s.value, ch.value
+
+
+def extend_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                     kcache: torch.Tensor, vcache: torch.Tensor, t0: int, key_valid: torch.Tensor,
+                     scale: Optional[float] = None, splits: int = 0) -> torch.Tensor:
+    """A chunk of Q consecutive new tokens per sequence: ``decode_attention_multi``'s arguments and stores (bf16 q [B*Q, nh*hd],
+    k / v [B*Q, nkv*hd] un-roped, cos / sin fp32 [B*Q, hd/2], caches [B, nkv, Lmax, hd] -> out [B*Q, nh*hd]; roped k and v of
+    token j into cache slot ``t0 + j``) for any 1 <= Q <= 4096, under ONE mask rule for cached and new slots: token j attends
+    slot s iff s <= t0 + j and (``key_valid[b, s]`` or s == t0 + j) — ``extend_mask``.  ``key_valid`` (bool / uint8
+    [B, >= t0+Q]) is read for slots 0 .. t0 + Q - 1, so suffixes left-padded inside the chunk are legal.  Inference only."""
+    return _decode_attention_launch("extend_attention", "cmb_extend_attn", "cmb_extend_attn_ws", extend_attention_supported,
+                                    q, k, v, cos, sin, kcache, vcache, (), True, t0, key_valid, scale, splits)
+
+
+def extend_mask(key_mask: torch.Tensor, t0: int, Q: int) -> torch.Tensor:
+    """bool [B, Q, t0 + Q]: what token j of a chunk may attend (``cmb_extend_attn``'s rule) — slot s iff s <= t0 + j and
+    (``key_mask[b, s]`` or s == t0 + j).  For the torch bodies of ``extend`` and the tests."""
+    S = t0 + Q
+    s = torch.arange(S, device=key_mask.device)
+    limit = t0 + torch.arange(Q, device=key_mask.device)[:, None]
+    return (s[None, :] <= limit)[None] & (key_mask[:, None, :S].bool() | (s[None, :] == limit)[None])
+
+
+# ------------------------------------------------------------------------------------------------
 # the same step on an e4m3 K / V cache (decode_attn_kv8.hip): one byte per element plus one fp32 factor per cache row, about
 # half the cache's memory and stream.  Opt-in (``config.decode_kv_fp8`` / CAMBRIAN_AMD_DECODE_KV_FP8): it changes numerics
 # (profiles/decode_kv8.md has what was measured).

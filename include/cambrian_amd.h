@@ -76,7 +76,8 @@ const char* cmb_version(void);
  * (cmb_kv_quantize_e4m3, cmb_decode_attn_kv8, cmb_decode_step_kv8 and cmb_decode_kv8_factors), and then the multi-token
  * decode attention of prompt-lookup decoding (cmb_decode_attn_multi, cmb_decode_attn_multi_ws, cmb_decode_attn_multi_plan), and then the decode-step linear for up to
  * 64 rows (cmb_decode_linear_wide, cmb_decode_linear_wide_supported, cmb_decode_linear_wide_plan), and then the logits
- * processors of generate() (cmb_decode_process) were
+ * processors of generate() (cmb_decode_process), and then chunk attention on the K / V cache (cmb_extend_attn,
+ * cmb_extend_attn_ws, cmb_extend_attn_plan) were
  * ADDED under revision 13: no existing
  * signature or layout changed, which is the rule for a bump, so a binding written against 13 still calls everything it
  * knows correctly.  Bindings must compare it
@@ -938,6 +939,38 @@ int cmb_decode_attn_multi(const void* q, int64_t q_ld, const void* k, int64_t k_
 int64_t cmb_decode_attn_multi_ws(int64_t B, int32_t nh, int32_t nkv, int32_t hd, int32_t Q, int64_t t0, int32_t splits);
 int cmb_decode_attn_multi_plan(int64_t B, int32_t nkv, int64_t t0, int32_t Q, int32_t splits, int32_t* splits_out,
                                int64_t* chunk_out, int32_t* max_splits_out);
+/* Attention of a CHUNK of Q >= 1 consecutive new tokens per cache row against the bf16 K / V cache: the suffix of a prompt
+ * whose head is already cached (generate(prefix=...)), the next turn of a chat.  Arguments, layouts and stores are
+ * cmb_decode_attn_multi's: q [B*Q, nh*hd], k / v [B*Q, nkv*hd] (un-roped, row strides in elements), cos_t / sin_t fp32
+ * [B*Q, hd/2], out [B*Q, nh*hd] contiguous, row b*Q + j is token j of sequence b; roped k (fp32 rotate-half RoPE, rounded to
+ * bf16 once) and raw v (bit for bit) of row (b, j) go into slot t0 + j of cache row b, and nothing outside slots
+ * t0 .. t0 + Q - 1 of the caches is written.
+ * The mask is the one difference: query (b, j) sees slot s iff s <= t0 + j and (key_valid[b][s] != 0 or s == t0 + j), the same
+ * rule for cached slots and the chunk's own — cmb_flash_attn_fwd's "causal AND key padding, diagonal open", so a batch whose
+ * suffixes are left-padded inside the chunk is legal and a padded query row still gives a finite row (it sees itself).
+ * key_valid is read for slots 0 .. t0 + Q - 1 (kv_ld >= t0 + Q); a slot no query may see (a masked cached slot, any slot past
+ * t0 + Q - 1) may hold anything, NaN included.  The attention launch reads the new slots from the cache: an earlier launch of
+ * the same call on the same stream wrote them.
+ * hd 64 | 96 | 128; nh % nkv == 0, G = nh / nkv <= 8; 1 <= Q <= 4096; t0 <= 2^31 - 1 - 4096 (so that t0 + Q < 2^31 whatever Q is); B, nkv <= 65535; bf16 only; pointers and
+ * strides 16-byte aligned.  Launches: the stores; attention over a grid of (batch row, KV head, row block of min(16, 64 / G)
+ * tokens, chunk of keys) with cmb_decode_attn_multi's workgroup (fp32 scores, running max / sum and accumulators, both
+ * products on the bf16 MFMA), every row under its own causal limit; when split, a merge of the fp32 partials in chunk order
+ * (no atomics, the same bits on every run).  The cache of a KV head is read once per row block.
+ * splits / ws / ws_floats as cmb_decode_attn_multi.  cmb_extend_attn_plan: the split of slots 0 .. t0 + Q - 1, splits * chunk
+ * >= t0 + Q > (splits - 1) * chunk; splits == 0 asks for the library's choice, a pure function of (B, nkv, t0, Q, CU count)
+ * that counts the ceil(Q / 16) row blocks as batch rows, so long chunks split little or not at all.  cmb_extend_attn_ws: floats
+ * of `ws` (0 when unsplit; B * Q * nh * splits * (hd + 2) otherwise) or a negative status; both queries are host functions.
+ * Statuses and check order of cmb_decode_attn_multi, everything before any launch: CMB_ERR_BAD_ARG for a NULL pointer (ws may
+ * be NULL when the call runs unsplit), a geometry or Q outside the rule, B or nkv out of range, t0 < 0, kv_ld < t0 + Q; then
+ * B == 0 is CMB_OK; then CMB_ERR_BAD_ARG for splits outside 0 .. the maximum, t0 > 2^31 - 1 - 4096 or ws_floats below the need; then
+ * CMB_ERR_ALIGNMENT. */
+int cmb_extend_attn(const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v, int64_t v_ld, const float* cos_t,
+                    const float* sin_t, void* kcache, void* vcache, int64_t c_sb, int64_t c_sh, int64_t c_st, int64_t B,
+                    int32_t nh, int32_t nkv, int32_t hd, int32_t Q, int64_t t0, const uint8_t* key_valid, int64_t kv_ld,
+                    float scale, int32_t splits, float* ws, int64_t ws_floats, void* out, void* stream);
+int64_t cmb_extend_attn_ws(int64_t B, int32_t nh, int32_t nkv, int32_t hd, int32_t Q, int64_t t0, int32_t splits);
+int cmb_extend_attn_plan(int64_t B, int32_t nkv, int64_t t0, int32_t Q, int32_t splits, int32_t* splits_out, int64_t* chunk_out,
+                         int32_t* max_splits_out);
 /* Greedy token selection and the next step's inputs in one launch (+ the cmb_rope_table launch), one workgroup per row b:
  *   nxt = argmax(logits[b, 0..V))       fp32 logits, row stride logits_ld; ties: the lowest index; a NaN is greater than
  *                                       every number and the first NaN wins (torch.argmax's rules); -0 == +0
